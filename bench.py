@@ -14,7 +14,12 @@ value = all ranks' frames / max-over-ranks time.
 Workload (BASELINE.json configs[1]): plane-sweep grid 256x192 (image
 1024x768), 64 depth candidates, 5-frame window (1 reference + 4 sources), fp32.
 
-The JSON line carries
+A plain run sets up, warms up, times exactly --steps steps and prints the headline line (metric, value in frames/s,
+ms_per_step, ...).  `--dump-outputs DIR` then also writes what the last timed step returned to its caller (refined DPV and
+DPV of every stream of rank 0; float32 .npy, at most 64 MB: see dump_outputs) — inputs and weights are seeded, so two builds can be
+compared output for output.  `--full` adds everything else below, each taking runs of its own after the timed steps.
+
+With --full the JSON line also carries
   roofline      HBM roofline of the dominant sampling kernel (fused warp + cost volume + log-softmax):
                 algorithmic bytes 4[(V+1)*67*hw + D*hw] per launch / its mean launch duration, measured
                 with HIP events on the launch stream inside the timed steps (peak 8.0 TB/s);
@@ -25,8 +30,11 @@ The JSON line carries
                 + the C sampling oracle) timed on this node's host cores on update frames of the same
                 workload: 1 warm-up + median of 2 (rank 0, N=1 only);
   parity        the GPU frame vs that oracle frame on the same window and filter state: max / mean |d| and
-                arg-max depth-index mismatches of BV_cur, DPV, BV_predict and the refined DPV.
-`--mode train` prints a separate, labelled line for the training iteration at BASELINE config 4's shape.
+                arg-max depth-index mismatches of BV_cur, DPV, BV_predict and the refined DPV;
+  config.sequential_frames_per_s  the same stream without the pipelining of consecutive frames;
+  other_configs short child runs of configs S / K / H and of the training step (config B, N = 1).
+`--mode train` prints a separate, labelled line for the training iteration at BASELINE config 4's shape (with --full: the
+K-Net layer's roofline, the all-reduce alone at N > 1 and the CPU baseline).
 """
 import argparse
 import json
@@ -114,7 +122,7 @@ def live_pmc_traffic(cfg, timeout_s=240):
         for tag, counters in (("FETCH_SIZE", ("FETCH_SIZE",)), ("WRITE_SIZE", ("WRITE_SIZE",)), ("SQ", SQ_PASS)):
             out = os.path.join(root, tag)
             cmd = [exe, "--pmc"] + list(counters) + ["--output-format", "csv", "-d", out, "-o", "p", "--", sys.executable,
-                   os.path.abspath(__file__), "--config", cfg, "--steps", "2", "--warmup", "1", "--no-graph", "--no-cpu-baseline",
+                   os.path.abspath(__file__), "--config", cfg, "--steps", "2", "--warmup", "1", "--no-graph", "--full", "--no-cpu-baseline",
                    "--no-live-traffic"]
             try:
                 subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=timeout_s, check=True)
@@ -319,7 +327,7 @@ def other_configs(skip, timeout_s=240):
     plus one `--mode train` step pair at config 4's shape.  Driver-visible companions of the headline number, not part of it."""
     import subprocess
     out = {}
-    base = [sys.executable, os.path.abspath(__file__), "--no-cpu-baseline", "--no-live-traffic", "--no-other-configs"]
+    base = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu-baseline", "--no-live-traffic", "--no-other-configs"]
     for cfg in [c for c in ("S", "K", "H") if c != skip]:
         steps = 300 if cfg == "H" else 5        # BASELINE config 5 IS a 300-frame sequence of one stream (state resident): sustained rate
         try:
@@ -546,6 +554,29 @@ def timed_steps(frame, steps, world, device):
     return dt
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """{name: tensor} -> out_dir/<name>.npy in float32, at most `limit` bytes in all.  An array larger than its equal share of
+    the limit is written as <name>_sampled.npy instead: every leading entry (the depth candidates) at a fixed, seeded
+    sample of its pixel positions (the last two dimensions), sorted, [numel / pixels, P] — the same positions for the same
+    shape in every run, and arg-max over depth stays comparable."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = limit // max(1, len(arrays)) - 1024        # room for the .npy header
+    for name, t in arrays.items():
+        a = t.detach().float()
+        if a.numel() * 4 <= share:
+            np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy())
+            continue
+        pix = a.shape[-1] * a.shape[-2]
+        rows = a.numel() // pix
+        keep = min(pix, share // (4 * rows))
+        idx = np.sort(np.random.RandomState(0).choice(pix, keep, replace=False))
+        sample = a.reshape(rows, pix).index_select(1, torch.from_numpy(idx).to(a.device))
+        np.save(os.path.join(out_dir, name + "_sampled.npy"), sample.cpu().numpy())
+
+
 def stub_main(args):
     """Harness self-test without a GPU (tests/test_dist_cpu.py): the same init / barrier / MAX-over-ranks / rank-0 JSON
     path as the real run on a gloo group, with a frame function that only sleeps (rank r sleeps (r+1) x 5 ms, so the MAX
@@ -603,7 +634,8 @@ def train_main(args):
         wins.append(ring)
     # the K-Net's 64 -> 64 layers run through ops.conv_wino_dw (forward and data gradient: autograd.Conv3dCL)
     knet_timer = KernelTimer(keep=lambda a, k: a[0].shape[-1] == 64)
-    ops.conv_wino_dw = knet_timer.wrap(ops.conv_wino_dw)
+    if args.full:
+        ops.conv_wino_dw = knet_timer.wrap(ops.conv_wino_dw)
     state = {"pred": [None] * A, "loss": None}
 
     def step(i, eager=False):
@@ -626,9 +658,13 @@ def train_main(args):
     for i in range(max(args.warmup, 2)):
         step(i + 2)
     dt = timed_steps(step, args.steps, world, dev)
+    if args.dump_outputs and rank == 0:
+        # what train() hands its caller: the loss of the last window and the predicted filter state of every accumulation slot
+        dump_outputs(args.dump_outputs, dict([("loss", state["loss"].reshape(1))] +
+                                             [("bv_predict_slot%d" % k, p_) for k, p_ in enumerate(state["pred"])]))
     assert bool(torch.isfinite(state["loss"])), "training loss went non-finite"
     per_rank = rank_times(world, args.steps, dev)
-    ar = allreduce_probe(reducer, world, dev)
+    ar = allreduce_probe(reducer, world, dev) if args.full else None
     if rank == 0:
         line = {"metric": "training windows/sec @grid 96x64x64cand, 5-view window, N=1 per forward (BASELINE config 4 shape)",
                 "value": args.steps * A * world / dt, "unit": "windows/s", "n_gpus": world, "rccl_ranks": ranks, "steps": args.steps,
@@ -656,7 +692,7 @@ def train_main(args):
                                 "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / MFMA_F32_PEAK_TFLOPS,
                                 "flops": flops, "direct_conv_flops": 2.0 * a0.shape[0] * a0.shape[1] * a0.shape[2] * 64 * 64 * 27,
                                 "traffic": None, "kernel_ms": c_ms}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             flat = [([ref], [src], p) for ring in wins for (ref, src, p) in ring]
             line["cpu_baseline"] = cpu_baseline_train(model, cam, d_candi, flat, 10.0)
         print(json.dumps(line))
@@ -678,11 +714,16 @@ def main():
     ap.add_argument("--streams", type=int, default=1, help="independent video streams per GPU, each on its own HIP stream "
                     "(a step is then one frame of EVERY stream; the extra streams fill the tails of each other's kernels)")
     ap.add_argument("--back-to-back", action="store_true", help="(kept for old command lines: roofline.back_to_back_ms — the sampling kernel re-launched "
-                    "20x back to back between one pair of events, the figure of rounds 1-4 — is always reported now)")
+                    "20x back to back between one pair of events, the figure of rounds 1-4 — is always reported with --full now)")
     ap.add_argument("--no-pipeline", action="store_true", help="strictly sequential frames (one hipGraph per frame) instead of the default: the D-Net "
                     "of frame t + 1 on a second HIP stream under the K-Net / R-Net / PREDICT of frame t (same video, same kernels, same bits)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the short companion runs of configs S / K / H and of one "
                     "training step (N = 1, headline config only; about a minute)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need, each in runs of its own "
+                    "after the timed steps: the kernel rooflines, the strictly sequential rate, the CPU baseline and parity, the other "
+                    "configurations (the --no-* options above switch single parts off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one returned to its caller as "
+                    "DIR/<name>.npy (float32, at most 64 MB: larger outputs as a fixed, seeded sample of their pixels)")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)   # CPU self-test of the N>1 harness
     ap.add_argument("--accum", type=int, default=4, help="--mode train: windows per GPU and optimizer step (gradient accumulation; "
                     "BASELINE config 4 = global batch 32 = 8 GPUs x 4)")
@@ -692,6 +733,8 @@ def main():
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         respawn_under_torchrun(args.gpus)          # never print n_gpus: 1 for --gpus N
     if args.stub:
+        if args.dump_outputs:
+            ap.error("--dump-outputs: the --stub self-test computes nothing")
         return stub_main(args)
     if args.mode == "train":
         return train_main(args)
@@ -720,15 +763,17 @@ def main():
     # a short ring of synthetic windows per rank, resident in HBM (different video per rank)
     ring = [tuple(t.to(dev) for t in synth.noise_window(1000 * rank + i, H, W, V)) for i in range(2)]
 
+    # --full: the kernels of the two rooflines, timed where they sit in eager frames after the timed region
     timer = KernelTimer()
-    ops.costvol = timer.wrap(ops.costvol)
     # the K-Net's plain 64->64 layer (BatchNorm+ReLU prologue, no residual operand, nothing materialised): 5 of its 12 layers
     knet_timer = KernelTimer(keep=lambda a, k: a[0].shape[-1] == 64 and k.get("res") is None and k.get("x_ss") is not None
                              and not k.get("materialize"))
-    ops.conv_wino_dw = knet_timer.wrap(ops.conv_wino_dw)
     # ... which runs on csrc/wino_dw4.hip (F(4,3) along depth) where D % 4 == 0: the same filter picks its clamped-FMA-ReLU launches
     knet_timer4 = KernelTimer(keep=lambda a, k: a[0].shape[-1] == 64 and k.get("x_ss") is not None and bool(k.get("x_unit")))
-    ops.conv_wino_dw4 = knet_timer4.wrap(ops.conv_wino_dw4)
+    if args.full:
+        ops.costvol = timer.wrap(ops.costvol)
+        ops.conv_wino_dw = knet_timer.wrap(ops.conv_wino_dw)
+        ops.conv_wino_dw4 = knet_timer4.wrap(ops.conv_wino_dw4)
 
     # the streaming driver: same per-frame work as test_utils/test_KVNet.py::test (R_net=True), state resident,
     # the update-branch frame captured into one hipGraph after an eager warm-up frame.  Extra streams per GPU are
@@ -742,12 +787,13 @@ def main():
     stream = streams[0]
 
     def frame(i):
-        out = None
+        out = []
         for k in range(S):
             r, s_, p = ring[(i + k) % len(ring)]
             with torch.cuda.stream(hip_streams[k]):
-                out = streams[k].step(r, s_, p)
-        return out
+                out.append(streams[k].step(r, s_, p))
+        frame.last = out                 # what every stream's step() returned: --dump-outputs
+        return out[-1]
 
     frame(0)                       # first window of the stream: D-Net only, creates the filter state
     # >= 2: one eager update frame, then the capture frame; pipelined: two eager frames, the capture, one replay of either slot
@@ -755,8 +801,17 @@ def main():
         frame(i + 1)
 
     dt = timed_steps(frame, args.steps, world, dev)
+    if args.dump_outputs and rank == 0:
+        # the (refined DPV, DPV) pair step() returned in the last timed step (pipelined: the frame before it), every stream;
+        # graph outputs are static buffers, so they are read before anything else runs on the streams
+        outs = {}
+        for k, o in enumerate(frame.last):
+            if o is not None:
+                sfx = "" if S == 1 else "_stream%d" % k
+                outs["refined_dpv" + sfx], outs["dpv" + sfx] = o
+        dump_outputs(args.dump_outputs, outs)
     seq_fps = None
-    if pipe:
+    if pipe and args.full:
         # the same stream once more WITHOUT the overlap (one hipGraph per frame, strictly sequential): reported beside the headline
         for st_ in streams:
             st_.flush()
@@ -776,44 +831,6 @@ def main():
     per_rank = rank_times(world, args.steps, dev)
 
     if rank == 0:
-        # ---- the two roofline kernels WHERE THEY SIT: consecutive EAGER frames of one window and filter state right behind the timed
-        # region (the timed frames are hipGraph replays, inside which a single kernel cannot be bracketed), every matching launch
-        # between its own pair of HIP events on the launch stream.  Until round 5 the sampling kernel was re-launched 20x back to back
-        # between ONE pair of events instead: that loop measures 0.235 ms where the kernel takes 0.20 ms in the frame and 0.193 ms per
-        # launch once events separate the launches (tools/r5_cv_gap.py) — without anything between them a launch runs into the previous
-        # one's end-of-kernel write-back of 25 MB of dirty cost / log-probability lines.  `--back-to-back` still reports that figure.
-        from neuralrgbd_amd import homography as warp_homo
-        pred = pred.clone()
-        r_, s_, p_ = ring[0]
-
-        def eager_frame():
-            with torch.no_grad():
-                _, r_kv_, bv_cur_, dpv_ = model(r_, s_, p_, torch.zeros(1), cam_intrinsics=[cam], BV_predict=pred, dpv_valid=True)
-                nxt_ = warp_homo.resample_vol_cuda(dpv_, ops.pose_inverse(p_[0, 2].contiguous()), cam_intrinsic=cam, d_candi=d_candi,
-                                                   padding_value=float(np.log(1.0 / D)), clamp=(-1000., 0.)).unsqueeze(0)
-            return r_kv_, dpv_, bv_cur_, nxt_
-        for _ in range(2):       # untimed: the allocator's blocks outside the graph's pool are created here (a hipMalloc drains the GPU)
-            eager_frame()
-        torch.cuda.synchronize()
-        timer.in_frame, knet_timer.in_frame, knet_timer4.in_frame = [], [], []
-        n_eager = max(8, min(args.steps, 20))
-        for _ in range(n_eager):
-            gpu_out = eager_frame()
-        torch.cuda.synchronize()
-        k_ms, n_k = timer.in_frame_ms()
-        got4 = knet_timer4.in_frame_ms()
-        got = got4 if got4 is not None else knet_timer.in_frame_ms()
-        depth_f43 = got4 is not None
-        c_ms, n_c = got if got is not None else (None, 0)
-        b2b_ms = timer.measure(20, warm=20)      # rounds 1-4's figure, always beside the in-frame one (rounds stay comparable)
-        algo = costvol_bytes(V, 67, D, h, w)
-        achieved = algo / (k_ms * 1e-3) / 1e9
-        traffic, traffic_note, sq = (None, "", None)
-        if world == 1 and not args.no_live_traffic and not args.no_graph and S == 1:
-            traffic, traffic_note, sq = live_pmc_traffic(args.config)      # measured now, by three rocprofv3 --pmc child passes
-        if traffic is None:
-            t2, n2 = pmc_traffic(args.config)                          # the committed measurement (refused if the kernel changed)
-            traffic, traffic_note = t2, (n2 if not traffic_note else "%s; live measurement unavailable: %s" % (n2, traffic_note))
         line = {
             "metric": "depth frames/sec @256x192x64cand, 5-view window; warp-kernel HBM GB/s vs peak",
             "value": args.steps * S * world / dt, "unit": "frames/s", "n_gpus": world, "rccl_ranks": ranks, "steps": args.steps,
@@ -825,59 +842,99 @@ def main():
                                   "frame t+1 on a second HIP stream under K-Net + DPV update + R-Net + PREDICT of frame t; every frame computed in full, "
                                   "outputs bit-identical to the sequential order (tests/test_gpu_fullsize.py), one frame of latency"
                                   if pipe and stream._graph is not None else "hipGraph replay" if stream._graph is not None else "eager"),
-                       "sequential_frames_per_s": seq_fps,
                        "parallelism": "replicas x%d (independent video streams)" % world,
                        "peak_hbm_gb": torch.cuda.max_memory_allocated(dev) / 1e9},
-            "roofline": {"bound": "hbm", "kernel": "costvol_quad<L2,3> (fused warp + cost volume + log-softmax over depth, one launch)",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "algorithmic_bytes": algo, "kernel_ms": k_ms, "launches_timed": n_k,
-                         "timing": "mean over the kernel's launches in %d consecutive eager frames right behind the timed region (2 untimed ones first), each "
-                                   "launch between its own pair of HIP events on the launch stream; the log-softmax is part of the launch" % n_eager,
-                         "traffic": traffic, "traffic_source": traffic_note},
         }
-        if b2b_ms is not None:
-            line["roofline"]["back_to_back_ms"] = b2b_ms
         if per_rank is not None:
             line["per_rank"] = per_rank
-        if sq:
-            # the HBM target is structurally out of reach for this kernel (118 flop/B against a machine balance of 20, SURVEY.md
-            # 8d): what binds it is VALU issue and the LDS gather — their utilisation from the kernel's own SQ counters
-            line["roofline"].update(sq_fractions(sq))
-            line["roofline"]["sq_counters_per_launch"] = sq
-        if c_ms is not None:   # secondary roofline: the matrix-core kernel that takes most of the frame
-            # F(2x2,3x3) in the plane and F(2,3) along depth: 64 multiplies per 2x2x2 outputs and (ci, co) instead of 216 -> the
-            # MFMAs the kernel actually issues; the 27-tap figure is what a direct convolution would need for the same layer
-            nominal = 2.0 * D * h * w * 64 * 64 * 27
-            if depth_f43:   # F(4,3) along depth: 6 x 16 transform points per 4 x 2 x 2 outputs and (ci, co)
-                blocks = (-(-D // 4)) * (-(-h // 2)) * (-(-w // 2))
-                flops = 2.0 * blocks * 64 * 64 * 96
-            else:
-                blocks = (-(-D // 2)) * (-(-h // 2)) * (-(-w // 2))
-                flops = 2.0 * blocks * 64 * 64 * 64
-            tf = flops / (c_ms * 1e-3) / 1e12
-            line["roofline_mfma"] = {"bound": "mfma", "kernel": ("conv_wino_dw4_kernel<CLAMP> (F(2x2,3x3) in the plane x F(4,3) along depth: 6 multiplies per "
-                                     "output voxel)" if depth_f43 else "conv_wino_dw_kernel<CLAMP> (F(2x2,3x3) x F(2,3): 8 multiplies per output voxel)") +
-                                     ", the frame's own calls: one K-Net 3x3x3 64->64 layer with a BatchNorm + ReLU input (the 10 64->64 layers are ~50 % of the "
-                                     "frame); `achieved` counts the MFMA flops the kernel ISSUES", "achieved": tf,
-                                     "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / MFMA_F32_PEAK_TFLOPS,
-                                     "flops": flops, "direct_conv_flops": nominal,
-                                     "direct_conv_equivalent_tflops": nominal / (c_ms * 1e-3) / 1e12, "kernel_ms": c_ms,
-                                     "launches_timed": n_c, "timing": "mean over the 5 matching layer launches of each of the same eager frames, every launch "
-                                     "between its own pair of HIP events (no idle gap in front of them: steady state, profiles/r4_inframe_gap.txt)"}
-        if world == 1 and not args.no_cpu_baseline:
-            # the same frame on both sides: window ring[0] filtered with the stream's state — the last of the eager frames above
-            r_kv, dpv, bv_cur, nxt = gpu_out
-            line["cpu_baseline"], o = cpu_baseline(args.config, cam, d_candi, sd, ring[0], pred, sigma)
-            line["parity"] = parity_block(args.config, (r_kv, dpv, bv_cur, nxt), o)
-            line["parity"]["tolerance_policy"] = TOLERANCE_POLICY
-            f64 = fp64_block(args.config, model, cam, d_candi, H, W, dev)
-            if f64 is not None:
-                line["parity"]["fp64"] = f64
-            rs = ref_self_block()
-            if rs is not None:
-                line["parity"]["ref_self"] = rs
-        if world == 1 and args.config == "B" and not args.no_other_configs and not args.no_graph and S == 1:
-            line["other_configs"] = other_configs(args.config)
+        if args.full:
+            # ---- the two roofline kernels WHERE THEY SIT: consecutive EAGER frames of one window and filter state right behind the timed
+            # region (the timed frames are hipGraph replays, inside which a single kernel cannot be bracketed), every matching launch
+            # between its own pair of HIP events on the launch stream.  Until round 5 the sampling kernel was re-launched 20x back to back
+            # between ONE pair of events instead: that loop measures 0.235 ms where the kernel takes 0.20 ms in the frame and 0.193 ms per
+            # launch once events separate the launches (tools/r5_cv_gap.py) — without anything between them a launch runs into the previous
+            # one's end-of-kernel write-back of 25 MB of dirty cost / log-probability lines.  `--back-to-back` still reports that figure.
+            from neuralrgbd_amd import homography as warp_homo
+            pred = pred.clone()
+            r_, s_, p_ = ring[0]
+
+            def eager_frame():
+                with torch.no_grad():
+                    _, r_kv_, bv_cur_, dpv_ = model(r_, s_, p_, torch.zeros(1), cam_intrinsics=[cam], BV_predict=pred, dpv_valid=True)
+                    nxt_ = warp_homo.resample_vol_cuda(dpv_, ops.pose_inverse(p_[0, 2].contiguous()), cam_intrinsic=cam, d_candi=d_candi,
+                                                       padding_value=float(np.log(1.0 / D)), clamp=(-1000., 0.)).unsqueeze(0)
+                return r_kv_, dpv_, bv_cur_, nxt_
+            for _ in range(2):       # untimed: the allocator's blocks outside the graph's pool are created here (a hipMalloc drains the GPU)
+                eager_frame()
+            torch.cuda.synchronize()
+            timer.in_frame, knet_timer.in_frame, knet_timer4.in_frame = [], [], []
+            n_eager = max(8, min(args.steps, 20))
+            for _ in range(n_eager):
+                gpu_out = eager_frame()
+            torch.cuda.synchronize()
+            k_ms, n_k = timer.in_frame_ms()
+            got4 = knet_timer4.in_frame_ms()
+            got = got4 if got4 is not None else knet_timer.in_frame_ms()
+            depth_f43 = got4 is not None
+            c_ms, n_c = got if got is not None else (None, 0)
+            b2b_ms = timer.measure(20, warm=20)      # rounds 1-4's figure, always beside the in-frame one (rounds stay comparable)
+            algo = costvol_bytes(V, 67, D, h, w)
+            achieved = algo / (k_ms * 1e-3) / 1e9
+            traffic, traffic_note, sq = (None, "", None)
+            if world == 1 and not args.no_live_traffic and not args.no_graph and S == 1:
+                traffic, traffic_note, sq = live_pmc_traffic(args.config)      # measured now, by three rocprofv3 --pmc child passes
+            if traffic is None:
+                t2, n2 = pmc_traffic(args.config)                          # the committed measurement (refused if the kernel changed)
+                traffic, traffic_note = t2, (n2 if not traffic_note else "%s; live measurement unavailable: %s" % (n2, traffic_note))
+            line["config"]["sequential_frames_per_s"] = seq_fps
+            line["config"]["peak_hbm_gb"] = torch.cuda.max_memory_allocated(dev) / 1e9      # with the eager frames' blocks
+            line["roofline"] = {"bound": "hbm", "kernel": "costvol_quad<L2,3> (fused warp + cost volume + log-softmax over depth, one launch)",
+                                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                                "algorithmic_bytes": algo, "kernel_ms": k_ms, "launches_timed": n_k,
+                                "timing": "mean over the kernel's launches in %d consecutive eager frames right behind the timed region (2 untimed ones first), each "
+                                          "launch between its own pair of HIP events on the launch stream; the log-softmax is part of the launch" % n_eager,
+                                "traffic": traffic, "traffic_source": traffic_note}
+            if b2b_ms is not None:
+                line["roofline"]["back_to_back_ms"] = b2b_ms
+            if sq:
+                # the HBM target is structurally out of reach for this kernel (118 flop/B against a machine balance of 20, SURVEY.md
+                # 8d): what binds it is VALU issue and the LDS gather — their utilisation from the kernel's own SQ counters
+                line["roofline"].update(sq_fractions(sq))
+                line["roofline"]["sq_counters_per_launch"] = sq
+            if c_ms is not None:   # secondary roofline: the matrix-core kernel that takes most of the frame
+                # F(2x2,3x3) in the plane and F(2,3) along depth: 64 multiplies per 2x2x2 outputs and (ci, co) instead of 216 -> the
+                # MFMAs the kernel actually issues; the 27-tap figure is what a direct convolution would need for the same layer
+                nominal = 2.0 * D * h * w * 64 * 64 * 27
+                if depth_f43:   # F(4,3) along depth: 6 x 16 transform points per 4 x 2 x 2 outputs and (ci, co)
+                    blocks = (-(-D // 4)) * (-(-h // 2)) * (-(-w // 2))
+                    flops = 2.0 * blocks * 64 * 64 * 96
+                else:
+                    blocks = (-(-D // 2)) * (-(-h // 2)) * (-(-w // 2))
+                    flops = 2.0 * blocks * 64 * 64 * 64
+                tf = flops / (c_ms * 1e-3) / 1e12
+                line["roofline_mfma"] = {"bound": "mfma", "kernel": ("conv_wino_dw4_kernel<CLAMP> (F(2x2,3x3) in the plane x F(4,3) along depth: 6 multiplies per "
+                                         "output voxel)" if depth_f43 else "conv_wino_dw_kernel<CLAMP> (F(2x2,3x3) x F(2,3): 8 multiplies per output voxel)") +
+                                         ", the frame's own calls: one K-Net 3x3x3 64->64 layer with a BatchNorm + ReLU input (the 10 64->64 layers are ~50 % of the "
+                                         "frame); `achieved` counts the MFMA flops the kernel ISSUES", "achieved": tf,
+                                         "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / MFMA_F32_PEAK_TFLOPS,
+                                         "flops": flops, "direct_conv_flops": nominal,
+                                         "direct_conv_equivalent_tflops": nominal / (c_ms * 1e-3) / 1e12, "kernel_ms": c_ms,
+                                         "launches_timed": n_c, "timing": "mean over the 5 matching layer launches of each of the same eager frames, every launch "
+                                         "between its own pair of HIP events (no idle gap in front of them: steady state, profiles/r4_inframe_gap.txt)"}
+            if world == 1 and not args.no_cpu_baseline:
+                # the same frame on both sides: window ring[0] filtered with the stream's state — the last of the eager frames above
+                r_kv, dpv, bv_cur, nxt = gpu_out
+                line["cpu_baseline"], o = cpu_baseline(args.config, cam, d_candi, sd, ring[0], pred, sigma)
+                line["parity"] = parity_block(args.config, (r_kv, dpv, bv_cur, nxt), o)
+                line["parity"]["tolerance_policy"] = TOLERANCE_POLICY
+                f64 = fp64_block(args.config, model, cam, d_candi, H, W, dev)
+                if f64 is not None:
+                    line["parity"]["fp64"] = f64
+                rs = ref_self_block()
+                if rs is not None:
+                    line["parity"]["ref_self"] = rs
+            if world == 1 and args.config == "B" and not args.no_other_configs and not args.no_graph and S == 1:
+                line["other_configs"] = other_configs(args.config)
         print(json.dumps(line))
     if world > 1:
         torch.distributed.barrier()      # rank 0 is still measuring kernels / printing: nobody tears its communicator down before that

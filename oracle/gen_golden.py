@@ -32,6 +32,10 @@ CPU under the installed torch.  Outputs (small, committed):
   ref_selfnoise_ST.npz  the same at config S with the TRAINED-LIKE weight family (synth.trained_like_state_dict): envelope + golden
   train_small.npz  two iterations of the reference's train() (first-frame + update branch, SGD): losses, predicted states,
                    weight deltas (= lr x gradient) of six probe tensors
+  ref_live.npz     what tests/test_oracle_vs_reference.py compares the oracle with (fresh shapes of the cost volume and of the
+                   resample, camera rays, torch's host K.R_v / K.t_v and pose inverses, PREDICT at every 4th pixel with the
+                   inverses it used, d_candi_new), inputs included except seeded features and the PREDICT DPV (their sums)
+  state_keys_D64.json  the state-dict keys and shapes of the reference KVNET at D = 64
 
     python -m oracle.gen_golden [ops net scene ops67 fp64 fp64S lba export]      (default: all)
 """
@@ -530,6 +534,89 @@ def gen_pose_inv(ref):
     print("pose_inv_ref: written")
 
 
+LIVE_OPS_SHAPES = ((16, 24, 8, 2, 5, 21), (20, 36, 12, 5, 7, 22), (9, 13, 4, 1, 3, 23))    # (h, w, D, V, C, seed)
+LIVE_RAY_GRIDS = ((40, 24), (96, 64))                                                      # (w, h)
+LIVE_PREDICT_SUB = 4                                                                       # pixel stride of the stored PREDICT outputs
+
+
+def gen_live(ref):
+    """The reference's outputs behind tests/test_oracle_vs_reference.py, so that those tests run from the repository alone:
+    est_swp_volume_v4 and resample_vol_cuda (+ clamp) on three fresh shapes, normalised_pixel_to_ray_array, the KVNET
+    state-dict keys at D = 64, torch's host K.R_v / K.t_v products and pose inverses, the PREDICT resample through the
+    reference's own inverse, and resample_vol_cuda with d_candi_new.  Every input is stored beside the output it produced
+    (the host-side log_softmax / inverse / trig of another machine may differ in the last bit), except the seeded normal
+    features of the cost volumes and the PREDICT DPV, which the test regenerates and checks against a stored sum."""
+    out = {}
+    H = ref.homography
+    for i, (h, w, D, V, C, seed) in enumerate(LIVE_OPS_SHAPES):
+        cam = camera.scannet_intrinsics(w, h)
+        rng = np.random.RandomState(seed)
+        feat_ref = torch.from_numpy(rng.standard_normal((1, C, h, w)).astype(np.float32))
+        feat_src = torch.from_numpy(rng.standard_normal((1, V, C, h, w)).astype(np.float32))
+        poses = torch.from_numpy(synth.random_poses(rng, V, rot_sigma=0.05, trans_sigma=0.2))
+        d_candi = np.linspace(0.3, 8, D)
+        R, t = poses[:, :3, :3].contiguous(), poses[:, :3, 3].contiguous()
+        cost = H.est_swp_volume_v4(feat_ref, feat_src, d_candi, R, t, cam, 3.0)[0]
+        dpv = torch.log_softmax(torch.from_numpy(rng.standard_normal((1, D, h, w)).astype(np.float32)) * 4, 1)
+        T = torch.from_numpy(synth.random_pose(rng, 0.05, 0.2).astype(np.float32)).inverse()
+        pred = H.resample_vol_cuda(dpv, T, cam_intrinsic=cam, d_candi=d_candi, padding_value=math.log(1. / D)) \
+            .clamp(max=0, min=-1000.)
+        p = "ops%d_" % i
+        out.update({p + "feat_checksum": checksum([feat_ref, feat_src]), p + "poses": poses.numpy(),
+                    p + "cost": cost.numpy(), p + "dpv": dpv[0].numpy(), p + "T": T.numpy(), p + "pred": pred.numpy()})
+    for (w, h) in LIVE_RAY_GRIDS:
+        cam = camera.scannet_intrinsics(w, h)
+        out["rays_%dx%d" % (w, h)] = ref.View.normalised_pixel_to_ray_array(width=w, height=h, hfov=cam["hfov"],
+                                                                           vfov=cam["vfov"], normalize_z=True)
+    # torch's host matmul of K and (R_v, t_v): the products the oracle's fixed order (oracle_homography_terms) reproduces
+    rng = np.random.RandomState(0)
+    K = camera.scannet_intrinsics(96, 64)["intrinsic_M_cuda"]
+    poses = np.stack([synth.random_poses(rng, 4, rot_sigma=0.3, trans_sigma=0.5) for _ in range(50)])
+    pt = torch.from_numpy(poses)
+    out["hterms_poses"] = poses
+    out["hterms_KR"] = np.stack([torch.stack([K.matmul(pt[n, v, :3, :3]) for v in range(4)]).reshape(4, 9).numpy() for n in range(50)])
+    out["hterms_Kt"] = np.stack([torch.stack([K.matmul(pt[n, v, :3, 3]) for v in range(4)]).numpy() for n in range(50)])
+    # test_utils/test_KVNet.py:50 `.inverse()`: torch's host LAPACK
+    rng = np.random.RandomState(77)
+    poses = np.stack([synth.random_pose(rng, 0.3, 1.0).astype(np.float32) for _ in range(500)])
+    out["inv_poses"], out["inv_ref"] = poses, torch.from_numpy(poses).inverse().numpy()
+    # the PREDICT step of the reference (inverse + resample + clamp) on a peaked DPV
+    h, w, D = 48, 64, 64
+    cam = camera.scannet_intrinsics(w, h)
+    d_candi = np.linspace(0.1, 5, D)
+    rng = np.random.RandomState(31)
+    dpv = torch.log_softmax(torch.from_numpy(rng.standard_normal((1, D, h, w)).astype(np.float32)) * 6, 1)
+    poses = [torch.from_numpy(synth.random_pose(rng, 0.05, 0.2).astype(np.float32)) for _ in range(5)]
+    # the DPV is regenerated from the seed by the test (checked by its sum); the volumes are kept small by storing the inverse the
+    # reference resampled with (its resample is bit-identical to the oracle's given the matrix: test_ops_fresh_shapes) and its
+    # own output at every LIVE_PREDICT_SUB-th pixel, which the oracle's rebuild of the whole volume must match
+    inv = [p.inverse() for p in poses]
+    ref_out = [H.resample_vol_cuda(dpv, T, cam_intrinsic=cam, d_candi=d_candi, padding_value=math.log(1. / D)).clamp(max=0, min=-1000.)
+               for T in inv]
+    out["predict_dpv_sum"] = dpv.double().sum().numpy()
+    out["predict_poses"], out["predict_inv_ref"] = torch.stack(poses).numpy(), torch.stack(inv).numpy()
+    out["predict_ref_sub"] = np.stack([o.numpy()[:, ::LIVE_PREDICT_SUB, ::LIVE_PREDICT_SUB] for o in ref_out])
+    # resample_vol_cuda(..., d_candi_new=...): the LBA driver's form (test_KVNet_LBA.py:414-417)
+    h, w, D, Dn = 20, 28, 12, 9
+    cam = camera.scannet_intrinsics(w, h)
+    rng = np.random.RandomState(8)
+    d_candi, d_new = np.linspace(0.3, 8, D), np.linspace(0.5, 6.5, Dn)
+    dpv = torch.log_softmax(torch.from_numpy(rng.standard_normal((1, D, h, w)).astype(np.float32)) * 4, 1)
+    T = torch.from_numpy(synth.random_pose(rng, 0.05, 0.2).astype(np.float32)).inverse()
+    pad = math.log(1. / D)
+    out["newcand_dpv"], out["newcand_T"] = dpv[0].numpy(), T.numpy()
+    out["newcand_new"] = H.resample_vol_cuda(dpv, T, cam_intrinsic=cam, d_candi=d_candi, d_candi_new=d_new, padding_value=pad).numpy()
+    out["newcand_same"] = H.resample_vol_cuda(dpv, T, cam_intrinsic=cam, d_candi=d_candi, d_candi_new=d_candi, padding_value=pad).numpy()
+    np.savez_compressed(os.path.join(OUT, "ref_live.npz"), **out)
+    # the state-dict contract at D = 64 (state_keys.json holds D = 16: the R-Net's widths follow D)
+    cam = camera.scannet_intrinsics(96, 64)
+    with ref_shim.quiet():
+        model = ref.KVNET.KVNET(64, cam, np.linspace(.1, 5, 64), 10., 64, None, if_refined=True, refineNet_name="DPV", t_win_r=2)
+    with open(os.path.join(OUT, "state_keys_D64.json"), "w") as f:
+        json.dump({k: list(v.shape) for k, v in model.state_dict().items()}, f, indent=0, sort_keys=True)
+    print("ref_live: %d arrays, %.1f MB" % (len(out), os.path.getsize(os.path.join(OUT, "ref_live.npz")) / 1e6))
+
+
 def main():
     if not ref_shim.available():
         raise SystemExit("reference not present: golden vectors can only be generated in the build container")
@@ -539,7 +626,7 @@ def main():
     which = sys.argv[1:] or ["ops", "net", "scene", "ops67", "fp64", "fp64S", "lba", "export", "train", "pose_inv"]
     for name in which:
         {"ops": gen_ops, "net": gen_net, "scene": gen_scene, "ops67": gen_ops67, "fp64": gen_fp64, "fp64S": gen_fp64_S, "lba": gen_lba, "export": gen_export, "train": gen_train, "pose_inv": gen_pose_inv,
-         "scene_stream": gen_scene_stream, "fp64B": gen_fp64_B, "selfnoise": gen_selfnoise,
+         "scene_stream": gen_scene_stream, "fp64B": gen_fp64_B, "selfnoise": gen_selfnoise, "live": gen_live,
          "selfnoiseK": lambda r: gen_selfnoise(r, "K"), "selfnoiseST": lambda r: gen_selfnoise(r, "ST")}[name](ref)
 
 

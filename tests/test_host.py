@@ -244,6 +244,27 @@ def test_live_traffic_measurement_parses_the_counter_files_and_fails_soft(tmp_pa
     assert val is None and "failed" in note and sq is None
 
 
+def test_bench_dump_outputs_stays_within_its_limit_and_samples_fixed_pixels(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): one float32 .npy per output; an output larger than its share of the limit is
+    written as whole depth columns at a seeded sample of its pixels, the same pixels in every run."""
+    import bench
+    small = torch.arange(2 * 3 * 4, dtype=torch.float64).reshape(1, 2, 3, 4)
+    big = torch.randn(1, 8, 64, 64)
+    limit = 40 << 10
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"small": small, "big": big}, limit=limit)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["big_sampled.npy", "small.npy"] and files == sorted(os.listdir(tmp_path / "b"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= limit
+    got = np.load(tmp_path / "a" / "small.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy().astype(np.float32))
+    a, b = np.load(tmp_path / "a" / "big_sampled.npy"), np.load(tmp_path / "b" / "big_sampled.npy")
+    assert a.dtype == np.float32 and a.shape[0] == 8 and 0 < a.shape[1] < 64 * 64 and np.array_equal(a, b)
+    cols = big.reshape(8, -1).numpy().T
+    pos = [int(np.flatnonzero((cols == c).all(1))[0]) for c in a.T]       # every sampled column is a column of the output ...
+    assert pos == sorted(set(pos))                                         # ... once, in pixel order
+
+
 def test_conv_embeddings_of_the_training_path_are_exact(monkeypatch):
     """autograd.conv2d_module / conv_transpose2d_module express the stride-2 3x3, the 1x1 (stride 1 / 2), the odd-width (67
     channel) and the ConvTranspose2d(k4, s2, p1) layers as ONE 3x3 stride-1 convolution on padded / space-to-depth tensors with

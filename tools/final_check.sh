@@ -6,11 +6,11 @@ timeout 1500 python -m pytest tests -m gpu -q -s 2>&1 | grep -v "amdgpu.ids" > $
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1
 # the kernels smoke() launches (no miopen / Cijk row may appear): a kernel trace of the same call
 ( cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT && rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_smoke -- python -c "import __graft_entry__ as g; g.smoke()" > $O/prof_smoke.log 2>&1; cp $(find $O/prof_smoke -name "*kernel_stats.csv" | head -1) $O/smoke_kernel_stats.csv; rm -rf $O/prof_smoke )
-python bench.py 2>$O/bench.err | tail -1 > $O/bench_B.json
-for c in S K H; do python bench.py --config $c --no-other-configs 2>/dev/null | tail -1 > $O/bench_$c.json; done
-python bench.py --mode train 2>/dev/null | tail -1 > $O/bench_train.json
-python bench.py --mode train --accum 1 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_train_accum1.json
-python bench.py --config H --steps 300 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_H_300frames.json
+python bench.py --full 2>$O/bench.err | tail -1 > $O/bench_B.json
+for c in S K H; do python bench.py --full --config $c --no-other-configs 2>/dev/null | tail -1 > $O/bench_$c.json; done
+python bench.py --full --mode train 2>/dev/null | tail -1 > $O/bench_train.json
+python bench.py --full --mode train --accum 1 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_train_accum1.json
+python bench.py --full --config H --steps 300 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_H_300frames.json
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for c in B S K; do
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$c -- python bench.py --config $c --steps 6 --warmup 2 --no-cpu-baseline --no-graph --no-other-configs > $O/prof_$c.log 2>&1

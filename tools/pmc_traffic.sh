@@ -13,7 +13,7 @@ CFGS=${@:-B}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for c in $CFGS; do
-  CMD="python $R/bench.py --config $c --steps 3 --warmup 2 --no-graph --no-cpu-baseline --no-live-traffic"
+  CMD="python $R/bench.py --config $c --steps 3 --warmup 2 --no-graph --full --no-cpu-baseline --no-live-traffic"
   rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/$c/fetch -o p -- $CMD > $OUT/$c.fetch.log 2>&1 || true
   rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/$c/write -o p -- $CMD > $OUT/$c.write.log 2>&1 || true
 done
