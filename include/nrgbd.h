@@ -47,8 +47,10 @@ extern "C" {
  * were built for.  0.4 (round 4): nrgbd_costvol_bwd takes (workspace, workspace_bytes) before `stream` (since round 3: query
  * nrgbd_costvol_bwd_workspace first); nrgbd_conv3d_wino_* and nrgbd_conv_wino_dw_bn_f32 are gone; nrgbd_upsample_bilinear_ac
  * is new.  0.5 (round 6): the three BatchNorm finalisers take (collapse_count, batches_tracked) before `stream`; nrgbd_pack_nhwc takes
- * rgb4, nrgbd_conv2d_taps_f32 takes in_stride; nrgbd_avgpool_cl, nrgbd_scatter_channels and nrgbd_conv2d_few_f32 are new. */
-#define NRGBD_INTERFACE_VERSION "0.5"
+ * rgb4, nrgbd_conv2d_taps_f32 takes in_stride; nrgbd_avgpool_cl, nrgbd_scatter_channels and nrgbd_conv2d_few_f32 are new.
+ * 0.6: the local bundle adjustment entries nrgbd_lba_pyramid, nrgbd_lba_workgroups, nrgbd_lba_grad and nrgbd_lba_update are new;
+ * no existing entry changed. */
+#define NRGBD_INTERFACE_VERSION "0.6"
 const char* nrgbd_version(void);
 const char* nrgbd_strerror(int code);
 
@@ -286,6 +288,41 @@ int nrgbd_warp_depth_bwd_workgroups(int H, int W);
 int nrgbd_warp_depth_bwd(const float* src, const float* dmap, const float* K, const float* R, const float* t,
                          const float* rays, const float* g_out, float* partial, float* g_R, float* g_t,
                          int N, int C, int H, int W, void* stream);
+
+/*
+ * Local bundle adjustment (pose refinement): the Adam loop of ICP/opt_pose_numerical.py:28-170 (_opt_pose_warping, one view)
+ * and :172-303 (_opt_pose_warping_parallel, N views jointly), called by local_BA_direct (:358-417) / _parallel (:306-355).
+ * One iteration = nrgbd_lba_grad + nrgbd_lba_update; nothing is read back or uploaded between iterations.
+ *
+ * nrgbd_lba_pyramid — every level of mutils/misc.py:139 downsample_img (F.avg_pool2d(x, k), floor sizes, each level pooled from
+ * the full-resolution input; k = 1 copies) of `nplanes` planes [H][W] (for the LBA: ref 3, sources 3 N, depth, confidence) in one
+ * launch.  Replaces opt_pose_numerical.py:320-322, :338 / :387-389, :400.
+ *   planes: HOST array of nplanes device pointers (nplanes <= 5 + 3 NRGBD_MAX_V); ks [nlevels] host (nlevels <= NRGBD_LBA_MAX_LEVELS)
+ *   out: level l at element offset nplanes * sum_{j<l} (H/k_j)(W/k_j), laid out [nplanes][H/k_l][W/k_l]
+ *
+ * nrgbd_lba_grad — one fused pass for the loss and its gradient at the current poses (replaces :245-294 / :99-160: quaternion
+ * chain aside, back_warp_th_Rt(_msrc), the mask, nn.L1Loss and what autograd runs for them).  Per (view n, pixel p, channel c):
+ * warped w = bilinear(src[n,c], K (R_n dmap[p] ray_p + t_n)) (= nrgbd_warp_depth_fwd); where w != 0: r = w conf[p] - ref[c,p] conf[p].
+ *   ref [3][H][W]; src [N][3][H][W]; dmap, conf [H][W]; K [3][3]; rays [3][HW]; state [N][NRGBD_LBA_STATE] (R_n, t_n read)
+ *   partial [N][nrgbd_lba_workgroups(H, W)][13]: per workgroup sum_p sign(r) conf d(w)/d(R_n) [9], d/d(t_n) [3], and sum |r| [1]
+ *   nrgbd_lba_workgroups(H, W) = min(ceil(HW / 256), 256): a fixed cap, larger images are covered by a grid-stride loop.
+ *
+ * nrgbd_lba_update — one workgroup.  step == 0: state[n] <- init[n] = (uq_n [3], t_n [3]), Adam moments 0, R_n = quaternion2Rotation(
+ * unitQ_to_quat(uq_n)) (mutils/misc.py:295, :459) in the reference's fp32 order.  step >= 1: fixed-order double reduction of the
+ * partials, normaliser 3 H W (x N when joint: the mean of nn.L1Loss), loss -> loss_log[log_slot] (joint) or
+ * loss_log[n * log_stride + log_slot], chain rule to d/d uq, then the Adam step number `step` (torch.optim.Adam, betas .9/.999,
+ * eps 1e-8, learning rate lr; the arithmetic of nrgbd_adam_step) of t_n when opt_t, of uq_n when opt_R (then R_n is rebuilt).
+ *   state [N][NRGBD_LBA_STATE] floats: uq [0,3) t [3,6) R [6,15) Adam m_t [15,18) v_t [18,21) m_uq [21,24) v_uq [24,27)
+ */
+#define NRGBD_LBA_STATE      32
+#define NRGBD_LBA_MAX_LEVELS  8
+int nrgbd_lba_pyramid(const float* const* planes, int nplanes, int H, int W, const int* ks, int nlevels, float* out,
+                      void* stream);
+int nrgbd_lba_workgroups(int H, int W);
+int nrgbd_lba_grad(const float* ref, const float* src, const float* dmap, const float* conf, const float* K, const float* rays,
+                   const float* state, float* partial, int N, int H, int W, void* stream);
+int nrgbd_lba_update(const float* partial, int nwg, const float* init, float* state, float* loss_log, int log_stride,
+                     int log_slot, int N, int H, int W, int joint, int step, double lr, int opt_R, int opt_t, void* stream);
 
 /*
  * K-Net: 3x3x3 convolution (stride 1, padding 1, no bias) on the fp32 matrix cores, with the

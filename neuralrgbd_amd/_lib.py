@@ -44,6 +44,10 @@ SIGNATURES = {
     "nrgbd_warp_depth_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "nrgbd_warp_depth_bwd_workgroups": (_I, [_I, _I]),
     "nrgbd_warp_depth_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "nrgbd_lba_pyramid": (_I, [_P, _I, _I, _I, _P, _I, _P, _P]),
+    "nrgbd_lba_workgroups": (_I, [_I, _I]),
+    "nrgbd_lba_grad": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "nrgbd_lba_update": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _D, _I, _I, _P]),
     "nrgbd_conv3d_workgroups": (_I, [_I, _I, _I]),
     "nrgbd_conv3d_pack_weights": (_I, [_P, _P, _I, _P]),
     "nrgbd_conv3d_3x3x3_f32": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),

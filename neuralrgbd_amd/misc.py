@@ -1,4 +1,6 @@
 """Small helpers of the depth path (the used part of code/mutils/misc.py)."""
+import math
+
 import torch
 
 from . import homography as _homo
@@ -50,3 +52,99 @@ def split_frame_list(frame_list, t_win_r):
 
 def get_entries_list_dict(list_dict, keyname):
     return [d[keyname] for d in list_dict]
+
+
+# ---- the pose helpers of the local bundle adjustment (opt_pose.py).  Host-side, fp32, operation for operation the reference's
+# torch code, so the bits agree; only downsample_img runs on the device.
+
+def downsample_img(img, kernel_size=4):
+    """F.avg_pool2d(img, kernel_size) of an NCHW CUDA tensor (mutils/misc.py:139-144): nrgbd_lba_pyramid with one level."""
+    if kernel_size <= 1:
+        return img
+    N, C, H, W = img.shape
+    x = ops._need(img, "img").reshape(N * C, H, W)
+    (out,) = ops.lba_pyramid([x[i] for i in range(N * C)], [kernel_size])
+    return out.view(N, C, H // kernel_size, W // kernel_size)
+
+
+def quaternion2Rotation(q, R_tensor=None):
+    """TUM-format quaternion [x y z w] tensor -> 3x3 (mutils/misc.py:295-331, is_tensor=True): s = 1/|q|^2 on the diagonal only."""
+    Rot = torch.zeros(3, 3) if R_tensor is None else R_tensor
+    w, x, y, z = q[3], q[0], q[1], q[2]
+    s = 1 / (w**2 + x**2 + y**2 + z**2)
+    Rot[0, 0] = 1 - 2 * s * (y**2 + z**2)
+    Rot[1, 1] = 1 - 2 * s * (x**2 + z**2)
+    Rot[2, 2] = 1 - 2 * s * (x**2 + y**2)
+    Rot[0, 1] = 2 * (x*y - w * z)
+    Rot[1, 0] = 2 * (x*y + w * z)
+    Rot[0, 2] = 2 * (x*z + w * y)
+    Rot[2, 0] = 2 * (x*z - w * y)
+    Rot[1, 2] = 2 * (y*z - w * x)
+    Rot[2, 1] = 2 * (y*z + w * x)
+    return Rot
+
+
+def Rotation2Quaternion(R, quat):
+    """mutils/misc.py:365-402, branches as written (the last three divide by quat[0] whatever they computed)."""
+    assert quat.dim() == 1 and len(quat) == 4, 'quat should be of right shape !'
+    if R[0, 0] + R[1, 1] + R[2, 2] + 1 > 0:
+        quat[3] = .5 * math.sqrt(R[0, 0] + R[1, 1] + R[2, 2] + 1)
+        s = 1 / 4 / quat[3]
+        quat[0] = s * (R[2, 1] - R[1, 2])
+        quat[1] = s * (R[0, 2] - R[2, 0])
+        quat[2] = s * (R[1, 0] - R[0, 1])
+    elif R[0, 0] - R[1, 1] - R[2, 2] + 1 > 0:
+        quat[0] = .5 * math.sqrt(R[0, 0] - R[1, 1] - R[2, 2] + 1)
+        s = 1 / 4 / quat[0]
+        quat[1] = s * (R[1, 0] + R[0, 1])
+        quat[2] = s * (R[0, 2] + R[2, 0])
+        quat[3] = s * (R[2, 1] + R[1, 2])
+    elif R[1, 1] - R[0, 0] - R[2, 2] + 1 > 0:
+        quat[1] = .5 * math.sqrt(R[1, 1] - R[0, 0] - R[2, 2] + 1)
+        s = 1 / 4 / quat[0]
+        quat[0] = s * (R[1, 0] + R[0, 1])
+        quat[2] = s * (R[1, 2] + R[2, 1])
+        quat[3] = s * (R[0, 2] - R[2, 0])
+    elif R[2, 2] - R[0, 0] - R[1, 1] + 1 > 0:
+        quat[2] = .5 * math.sqrt(R[2, 2] - R[0, 0] - R[1, 1] + 1)
+        s = 1 / 4 / quat[0]
+        quat[0] = s * (R[2, 0] + R[0, 2])
+        quat[1] = s * (R[2, 1] + R[1, 2])
+        quat[3] = s * (R[1, 0] - R[0, 1])
+
+
+def unitQ_to_quat(unitQ, quat):
+    """3-vector unit-quaternion parameter -> TUM quaternion (mutils/misc.py:459-472): the parameter's x goes into w."""
+    x, y, z = unitQ[0], unitQ[1], unitQ[2]
+    alpha2 = x**2 + y**2 + z**2
+    quat[3] = 2 * x / (alpha2 + 1)
+    quat[0] = 2 * y / (alpha2 + 1)
+    quat[1] = 2 * z / (alpha2 + 1)
+    quat[2] = (1 - alpha2) / (1 + alpha2)
+
+
+def quat_to_unitQ(quat, unitQ):
+    """mutils/misc.py:487-502."""
+    q1, q2, q3, q0 = quat[0], quat[1], quat[2], quat[3]
+    alpha2 = (1 - q3) / (1 + q3)
+    unitQ[0] = q0 * (alpha2 + 1) * .5
+    unitQ[1] = q1 * (alpha2 + 1) * .5
+    unitQ[2] = q2 * (alpha2 + 1) * .5
+
+
+def UnitQ2Rotation(r_uq):
+    """uq [3] -> R [3,3] on the host in fp32 (mutils/misc.py:404-409)."""
+    assert isinstance(r_uq, torch.Tensor)
+    r_q = torch.zeros(4)
+    unitQ_to_quat(r_uq.detach().cpu(), r_q)
+    return quaternion2Rotation(r_q)
+
+
+def Rotation2UnitQ(R):
+    """R [3,3] -> uq [3] on the host in fp32 (mutils/misc.py:411-416)."""
+    R = torch.as_tensor(R, dtype=torch.float32).cpu()
+    r_q = torch.zeros(4)
+    r_uq = torch.zeros(3)
+    Rotation2Quaternion(R, r_q)
+    quat_to_unitQ(r_q, r_uq)
+    return r_uq

@@ -291,6 +291,126 @@ def warp_depth_bwd(src, dmap, K, R, t, rays, g_out):
     return g_R, g_t
 
 
+# ----------------------------------------------------------------------------- local bundle adjustment (opt_pose.py)
+LBA_STATE = 32          # NRGBD_LBA_STATE: floats per view of the optimiser state (uq, t, R, Adam moments)
+LBA_MAX_LEVELS = 8      # NRGBD_LBA_MAX_LEVELS
+MAX_V = 16              # NRGBD_MAX_V
+
+
+def lba_pyramid(planes, ks):
+    """Every level F.avg_pool2d(plane, k) (floor sizes, each from the full-resolution plane) of the [H,W] planes in one launch
+    (nrgbd_lba_pyramid) -> list over levels of [nplanes, H//k, W//k] views into one buffer."""
+    planes = [_need(x, "plane %d" % i) for i, x in enumerate(planes)]
+    H, W = planes[0].shape
+    for x in planes:
+        if tuple(x.shape) != (H, W) or x.device != planes[0].device:
+            raise ValueError("lba_pyramid: every plane must be [%d,%d] on %s" % (H, W, planes[0].device))
+    ks = [int(k) for k in ks]
+    if not 1 <= len(ks) <= LBA_MAX_LEVELS or min(ks) < 1 or H // max(ks) == 0 or W // max(ks) == 0:
+        raise ValueError("lba_pyramid: kernel sizes %s invalid for %dx%d" % (ks, H, W))
+    P = len(planes)
+    sizes = [(H // k, W // k) for k in ks]
+    out = torch.empty(P * sum(h * w for h, w in sizes), dtype=torch.float32, device=planes[0].device)
+    ptrs = (ctypes.c_void_p * P)(*[x.data_ptr() for x in planes])
+    karr = (ctypes.c_int * len(ks))(*ks)
+    with torch.cuda.device(out.device):
+        rc = _lib.load().nrgbd_lba_pyramid(ptrs, P, H, W, karr, len(ks), _p(out), _stream(out))
+    _lib.check(rc, "nrgbd_lba_pyramid")
+    levels, off = [], 0
+    for h, w in sizes:
+        levels.append(out[off:off + P * h * w].view(P, h, w))
+        off += P * h * w
+    return levels
+
+
+def lba_workgroups(H, W):
+    return int(_lib.load().nrgbd_lba_workgroups(H, W))
+
+
+def lba_grad(ref, src, dmap, conf, K, rays, state, partial):
+    """One fused loss + gradient pass at the poses held in state [N, LBA_STATE] (nrgbd_lba_grad): ref [3,H,W], src [N,3,H,W],
+    dmap / conf [H,W], K [3,3], rays [3,HW] -> partial [N, lba_workgroups(H, W), 13] (a flat buffer at least that large)."""
+    src = _need(src, "src")
+    N, C, H, W = src.shape
+    if C != 3 or not 1 <= N <= MAX_V:
+        raise ValueError("lba_grad: src must be [N<=%d,3,H,W], got %s" % (MAX_V, tuple(src.shape)))
+    ref = _need(ref, "ref", (3, H, W)); dmap = _need(dmap, "dmap", (H, W)); conf = _need(conf, "conf", (H, W))
+    K = _need(K, "K", (3, 3)); rays = _need(rays, "rays", (3, H * W)); state = _need(state, "state", (N, LBA_STATE))
+    partial = _need(partial, "partial")
+    if partial.numel() < N * lba_workgroups(H, W) * 13:
+        raise ValueError("lba_grad: partial holds %d floats, %d needed" % (partial.numel(), N * lba_workgroups(H, W) * 13))
+    with torch.cuda.device(src.device):
+        rc = _lib.load().nrgbd_lba_grad(_p(ref), _p(src), _p(dmap), _p(conf), _p(K), _p(rays), _p(state), _p(partial),
+                                        N, H, W, _stream(src))
+    _lib.check(rc, "nrgbd_lba_grad")
+    return partial
+
+
+def lba_init(init, state):
+    """state[n] <- (uq, t) = init [N,6], Adam moments 0, R from uq (nrgbd_lba_update, step 0)."""
+    state = _need(state, "state")
+    N = state.shape[0]
+    init = _need(init, "init", (N, 6))
+    if tuple(state.shape) != (N, LBA_STATE) or not 1 <= N <= MAX_V:
+        raise ValueError("lba_init: state must be [N<=%d,%d]" % (MAX_V, LBA_STATE))
+    with torch.cuda.device(state.device):
+        rc = _lib.load().nrgbd_lba_update(None, 1, _p(init), _p(state), None, 1, 0, N, 1, 1, 1, 0, 0.0, 0, 0, _stream(state))
+    _lib.check(rc, "nrgbd_lba_update")
+    return state
+
+
+def lba_update(partial, state, loss_log, log_slot, H, W, joint, step, lr, opt_R, opt_t):
+    """Adam step number `step` (>= 1) from the partials of lba_grad at an H x W level (nrgbd_lba_update); the loss goes to
+    loss_log[0, log_slot] (joint) or loss_log[n, log_slot]."""
+    state = _need(state, "state")
+    N = state.shape[0]
+    if tuple(state.shape) != (N, LBA_STATE) or not 1 <= N <= MAX_V:
+        raise ValueError("lba_update: state must be [N<=%d,%d]" % (MAX_V, LBA_STATE))
+    partial = _need(partial, "partial")
+    loss_log = _need(loss_log, "loss_log")
+    if loss_log.dim() != 2 or loss_log.shape[0] != (1 if joint else N) or not 0 <= log_slot < loss_log.shape[1]:
+        raise ValueError("lba_update: loss_log %s / slot %d" % (tuple(loss_log.shape), log_slot))
+    if step < 1:
+        raise ValueError("lba_update: step counts from 1 (lba_init is step 0)")
+    with torch.cuda.device(state.device):
+        rc = _lib.load().nrgbd_lba_update(_p(partial), lba_workgroups(H, W), None, _p(state), _p(loss_log),
+                                          int(loss_log.shape[1]), int(log_slot), N, H, W, int(bool(joint)), int(step),
+                                          float(lr), int(bool(opt_R)), int(bool(opt_t)), _stream(state))
+    _lib.check(rc, "nrgbd_lba_update")
+    return state
+
+
+class LbaLevel:
+    """The two launches of one LBA iteration at one pyramid level with their arguments checked once (lba_grad / lba_update's
+    checks) and kept as ctypes values: the optimiser calls them scales x iterations times."""
+
+    def __init__(self, ref, src, dmap, conf, K, rays, state, partial, loss_log, joint, opt_R, opt_t):
+        lba_grad(ref, src, dmap, conf, K, rays, state, partial)            # validates (and runs) the first pass
+        self._keep = (ref, src, dmap, conf, K, rays, state, partial, loss_log)
+        N, _, H, W = src.shape
+        self.H, self.W = H, W
+        self._lib = _lib.load()
+        self._g = (_p(ref), _p(src), _p(dmap), _p(conf), _p(K), _p(rays), _p(state), _p(partial), N, H, W, _stream(src))
+        self._u = (_p(partial), lba_workgroups(H, W), None, _p(state), _p(loss_log), int(loss_log.shape[1]))
+        self._u2 = (N, H, W, int(bool(joint)))
+        self._u3 = (int(bool(opt_R)), int(bool(opt_t)), _stream(src))
+        self._args = (state, loss_log, joint, opt_R, opt_t)
+        self._first = True
+
+    def grad(self):
+        if self._first:            # the constructor ran this iteration's pass
+            self._first = False
+            return
+        _lib.check(self._lib.nrgbd_lba_grad(*self._g), "nrgbd_lba_grad")
+
+    def update(self, log_slot, step, lr):
+        state, loss_log, joint, opt_R, opt_t = self._args
+        if not 0 <= log_slot < loss_log.shape[1] or step < 1:
+            raise ValueError("LbaLevel.update: slot %d / step %d" % (log_slot, step))
+        _lib.check(self._lib.nrgbd_lba_update(*self._u, int(log_slot), *self._u2, int(step), float(lr), *self._u3),
+                   "nrgbd_lba_update")
+
+
 # ----------------------------------------------------------------------------- K-Net convolutions
 def conv3d_workgroups(D, H, W):
     return int(_lib.load().nrgbd_conv3d_workgroups(D, H, W))
