@@ -295,20 +295,23 @@ def warp_depth_bwd(src, dmap, K, R, t, rays, g_out):
 LBA_STATE = 32          # NRGBD_LBA_STATE: floats per view of the optimiser state (uq, t, R, Adam moments)
 LBA_MAX_LEVELS = 8      # NRGBD_LBA_MAX_LEVELS
 MAX_V = 16              # NRGBD_MAX_V
+LBA_MAX_PLANES = 5 + 3 * MAX_V     # lba.hip kLbaMaxPlanes: ref (3) + sources (3 N) + depth + confidence
 
 
 def lba_pyramid(planes, ks):
     """Every level F.avg_pool2d(plane, k) (floor sizes, each from the full-resolution plane) of the [H,W] planes in one launch
     (nrgbd_lba_pyramid) -> list over levels of [nplanes, H//k, W//k] views into one buffer."""
-    planes = [_need(x, "plane %d" % i) for i, x in enumerate(planes)]
+    P = len(planes)
+    if not 1 <= P <= LBA_MAX_PLANES:                  # checked before anything touches the device
+        raise ValueError("lba_pyramid: %d planes, 1 to %d" % (P, LBA_MAX_PLANES))
     H, W = planes[0].shape
-    for x in planes:
-        if tuple(x.shape) != (H, W) or x.device != planes[0].device:
-            raise ValueError("lba_pyramid: every plane must be [%d,%d] on %s" % (H, W, planes[0].device))
     ks = [int(k) for k in ks]
     if not 1 <= len(ks) <= LBA_MAX_LEVELS or min(ks) < 1 or H // max(ks) == 0 or W // max(ks) == 0:
         raise ValueError("lba_pyramid: kernel sizes %s invalid for %dx%d" % (ks, H, W))
-    P = len(planes)
+    planes = [_need(x, "plane %d" % i) for i, x in enumerate(planes)]
+    for x in planes:
+        if tuple(x.shape) != (H, W) or x.device != planes[0].device:
+            raise ValueError("lba_pyramid: every plane must be [%d,%d] on %s" % (H, W, planes[0].device))
     sizes = [(H // k, W // k) for k in ks]
     out = torch.empty(P * sum(h * w for h, w in sizes), dtype=torch.float32, device=planes[0].device)
     ptrs = (ctypes.c_void_p * P)(*[x.data_ptr() for x in planes])

@@ -3,7 +3,8 @@
 Same names, arguments, defaults and return values as the reference's four functions.  The whole Adam schedule (scales x
 iterations) runs on the device as two launches per iteration (lba.hip: the fused loss + gradient pass and the one-workgroup
 pose update) with no host synchronisation; the host reads back only what the return values need (the poses, the last level's
-reference image) and the loss log behind the reference's d_loss prints, which it prints after the run.
+reference image) and the loss log behind the reference's d_loss prints, which it prints after the run.  local_BA_direct takes
+any number of source frames (the LBA driver passes 20) in groups of at most ops.MAX_V; the joint forms take at most ops.MAX_V.
 
 Not reproduced (a clear error instead): bi_direct_warp=True (unimplemented in the parallel form, and its single-view branch
 needs the inverse-warp quaternion the optimiser never uses), r_para other than 'unit_quat' (the reference's other branches test
@@ -201,8 +202,12 @@ def local_BA_direct_parallel(ref_frame, src_frames, dmap_ref, conf_map_ref, cams
                              step, opt_vars):
     """Optimise the poses of all source frames jointly (opt_pose_numerical.py:306-355).  ref_frame [1,3,H,W], src_frames list
     of [1,3,H,W], dmap_ref / conf_map_ref [1,1,H,W], cams_intrin per scale (the pooled sizes), dw_scales e.g. [4, 2, 1],
-    rel_pose_inits 4x4 (ref -> src).  Returns the list of refined 4x4 CPU float tensors."""
+    rel_pose_inits 4x4 (ref -> src).  Returns the list of refined 4x4 CPU float tensors.  The views share one loss normaliser,
+    so they run in one group: at most ops.MAX_V source frames."""
     assert len(src_frames) > 1  # should have more than one src view (:198)
+    if len(src_frames) > ops.MAX_V:
+        raise ValueError("local_BA_direct_parallel: %d source frames, at most %d (the views share one loss normaliser and "
+                         "run in one group; local_BA_direct takes any number)" % (len(src_frames), ops.MAX_V))
     opt_R, opt_t = _flags(opt_vars, False, conf_map_ref, 'unit_quat', max_iter)
     levels, init = _prepare(ref_frame, src_frames, dmap_ref, conf_map_ref, cams_intrin, dw_scales, rel_pose_inits)
     state, log = _run(levels, init, int(max_iter), step, opt_R, opt_t, joint=True)
@@ -212,12 +217,23 @@ def local_BA_direct_parallel(ref_frame, src_frames, dmap_ref, conf_map_ref, cams
 
 def local_BA_direct(ref_frame, src_frames, dmap_ref, conf_map_ref, cams_intrin, dw_scales, rel_pose_inits, max_iter, step,
                     opt_vars):
-    """Optimise the pose of each source frame on its own (opt_pose_numerical.py:358-417); the N independent optimisations run
-    in the same launches, each with its own normaliser 3 h w.  Arguments and return value as local_BA_direct_parallel."""
+    """Optimise the pose of each source frame on its own (opt_pose_numerical.py:358-417); arguments and return value as
+    local_BA_direct_parallel, any number of source frames (the driver passes 20).  Each view has its own normaliser 3 h w and
+    its own Adam state, so the views run in groups of at most ops.MAX_V, each group's independent optimisations in the same
+    launches; a view's result does not depend on its group (the grad kernel indexes views by blockIdx.y, the update reduces
+    each view's rows on their own).  The d_loss lines are printed in view order after the last group."""
     opt_R, opt_t = _flags(opt_vars, False, conf_map_ref, 'unit_quat', max_iter)
-    levels, init = _prepare(ref_frame, src_frames, dmap_ref, conf_map_ref, cams_intrin, dw_scales, rel_pose_inits)
-    state, log = _run(levels, init, int(max_iter), step, opt_R, opt_t, joint=False)
-    log = log.cpu().numpy()
+    N = len(src_frames)
+    if N < 1 or len(rel_pose_inits) != N:
+        raise ValueError("local BA: %d source frames / %d initial poses (equal, at least 1)" % (N, len(rel_pose_inits)))
+    poses, logs = [], []
+    for g0 in range(0, N, ops.MAX_V):
+        levels, init = _prepare(ref_frame, src_frames[g0:g0 + ops.MAX_V], dmap_ref, conf_map_ref, cams_intrin, dw_scales,
+                                rel_pose_inits[g0:g0 + ops.MAX_V])
+        state, log = _run(levels, init, int(max_iter), step, opt_R, opt_t, joint=False)
+        poses += _poses(state)
+        logs.append(log)
+    log = torch.cat(logs).cpu().numpy()
     for i_src in range(log.shape[0]):
         _print_d_loss(log[i_src], len(levels), int(max_iter))
-    return _poses(state)
+    return poses

@@ -205,6 +205,19 @@ def warp_depth_bwd(src, dmap, K, R, t, rays, g_out):
     return gR, gt
 
 
+def warp_depth_bwd_abs(src, dmap, K, R, t, rays, g_out):
+    """Absolute sums (float64) of the per-pixel terms of warp_depth_bwd with |g_out| -> (a_R [N,3,3], a_t [N,3])."""
+    s_, ps = _f(src); d_, pd = _f(dmap); k_, pk = _f(K); r_, pr = _f(np.asarray(R, np.float32).reshape(-1, 9))
+    t_, pt = _f(np.asarray(t, np.float32).reshape(-1, 3)); y_, py = _f(rays); g_, pg = _f(g_out)
+    N, C, H, W = s_.shape
+    aR = np.empty((N, 3, 3), np.float64); at = np.empty((N, 3), np.float64)
+    rc = lib().oracle_warp_depth_bwd_abs(ps, pd, pk, pr, pt, py, pg, N, C, H, W,
+                                         aR.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                         at.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    assert rc == 0
+    return aR, at
+
+
 def div_const_mismatches(c, stride=1):
     """Dividends for which the kernels' 3-instruction division by the constant c differs from IEEE a / c (must be 0)."""
     f = lib().oracle_div_const_mismatches

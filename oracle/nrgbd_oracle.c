@@ -509,6 +509,51 @@ int oracle_warp_depth_bwd(const float* src, const float* dmap, const float* K, c
     return 0;
 }
 
+/* The magnitude companion of oracle_warp_depth_bwd: the same per-pixel chain with every term replaced by its absolute value
+ * and |g_out| for g_out, summed in double -> (a_R [N][9], a_t [N][3]).  With g_out = the upstream gradient it is the absolute
+ * sum of the per-pixel terms every intermediate rounding of an fp32 evaluation is relative to (the summation bound of the
+ * LBA tests); with g_out = 2 c at a set of pixels it bounds what a sign change of g_out there can move the gradient by. */
+int oracle_warp_depth_bwd_abs(const float* src, const float* dmap, const float* K, const float* R, const float* t,
+                              const float* rays, const float* g_out, int N, int C, int H, int W, double* a_R, double* a_t) {
+    size_t hw = (size_t)H * W;
+    for (int n = 0; n < N; ++n) {
+        double aR[9] = {0}, at[3] = {0};
+        for (size_t p = 0; p < hw; ++p) {
+            float X[3], Y[3], P[3], ix, iy;
+            depth_warp_coords(K, R + 9 * n, t + 3 * n, rays[p], rays[hw + p], rays[2 * hw + p], dmap[p], W, H, X, Y, P, &ix, &iy);
+            taps2d tp;
+            bilinear_taps(ix, iy, W, H, &tp);
+            float x0 = floorf(ix), y0 = floorf(iy);
+            float fx = ix - x0, fy = iy - y0;
+            double gix = 0, giy = 0;
+            for (int c = 0; c < C; ++c) {
+                const float* pl = src + ((size_t)n * C + c) * hw;
+                double g = fabs((double)g_out[((size_t)n * C + c) * hw + p]);
+                if (g == 0.0) continue;
+                float v00 = (tp.vx[0] && tp.vy[0]) ? pl[(size_t)tp.y[0] * W + tp.x[0]] : 0.f;
+                float v01 = (tp.vx[1] && tp.vy[0]) ? pl[(size_t)tp.y[0] * W + tp.x[1]] : 0.f;
+                float v10 = (tp.vx[0] && tp.vy[1]) ? pl[(size_t)tp.y[1] * W + tp.x[0]] : 0.f;
+                float v11 = (tp.vx[1] && tp.vy[1]) ? pl[(size_t)tp.y[1] * W + tp.x[1]] : 0.f;
+                gix += g * (fabs((double)v01 - v00) * (1.0 - fy) + fabs((double)v11 - v10) * fy);
+                giy += g * (fabs((double)v10 - v00) * (1.0 - fx) + fabs((double)v11 - v01) * fx);
+            }
+            if (gix == 0.0 && giy == 0.0) continue;
+            double cx = K[2], cy = K[5];
+            double du = gix * (W * 0.5) / fabs(cx), dv = giy * (H * 0.5) / fabs(cy);
+            double pz = fabs((double)P[2]);
+            double dP[3] = {du / pz, dv / pz, (du * fabs((double)P[0]) + dv * fabs((double)P[1])) / (pz * pz)};
+            for (int i = 0; i < 3; ++i) {
+                double dY = fabs((double)K[i]) * dP[0] + fabs((double)K[3 + i]) * dP[1] + fabs((double)K[6 + i]) * dP[2];
+                at[i] += dY;
+                for (int j2 = 0; j2 < 3; ++j2) aR[3 * i + j2] += dY * fabs((double)X[j2]);
+            }
+        }
+        for (int i = 0; i < 9; ++i) a_R[9 * n + i] = aR[i];
+        for (int i = 0; i < 3; ++i) a_t[3 * n + i] = at[i];
+    }
+    return 0;
+}
+
 /* Check of csrc/common.hpp::div_by_const (a / c for a loop-invariant c as q = a rc, r = fma(-q, c, a), q + r rc): number of
  * finite fp32 dividends a (every `stride`-th bit pattern, |a| in [1e-30, 1e30] or 0) whose result differs from a / c. */
 long oracle_div_const_mismatches(float c, long stride) {

@@ -19,18 +19,31 @@ MAX_ITER = 4
 STEP = 0.01
 OPT_VARS = ([1, 1], [1, 0], [0, 1])
 
+# tests/golden/lba_opt_wide.npz: (a) local_BA_direct with the LBA driver's window (t_win 2 x dat_indx_step 5 on each side: 20
+# sources) at its img_size 384 x 256; (b) local_BA_direct_parallel with 16 sources (every block of 4 of the update's reduction)
+WIDE_H, WIDE_W, WIDE_V, WIDE_SEED = 256, 384, 20, 31
+WIDE_OPT_VARS = ([1, 1], [0, 1])
+PAR16_H, PAR16_W, PAR16_V, PAR16_SEED = 32, 48, 16, 41
+DRIVER_D = 64
+
 
 def cams(H_, W_, dw_scales=DW_SCALES):
     return [camera.scannet_intrinsics(W_ // k, H_ // k) for k in dw_scales]
 
 
-def inputs(seed=SEED, H_=H, W_=W, V_=V, rot_sigma=0.01, trans_sigma=0.02):
+def inputs(seed=SEED, H_=H, W_=W, V_=V, rot_sigma=0.01, trans_sigma=0.02, conf_kind="sigmoid"):
     """(ref_frame [1,3,H,W], src_frames [V x [1,3,H,W]], dmap_ref [1,1,H,W], conf_map_ref [1,1,H,W], rel_pose_inits [V,4,4]
-    float32, true poses [V,4,4] float32) — all CPU."""
+    float32, true poses [V,4,4] float32) — all CPU.  conf_kind "sigmoid": a smooth map in (0, 1); "driver": built as
+    test_KVNet_LBA.py builds it, exp(max over the depth candidates of the log-probability) ** 2, from a 64-candidate
+    log_softmax of smooth logits — values in [1/64^2, 1] (down to 1.2e-2 on the recorded 20-view window)."""
     cam = camera.scannet_intrinsics(W_, H_)
     ref, src, poses, depth = synth.rendered_window(seed, H_, W_, cam, V=V_)
     rng = np.random.RandomState(seed + 1000)
-    conf = 1.0 / (1.0 + np.exp(-synth.smooth_texture(rng, 1, H_, W_, octaves=2)))          # in (0, 1), like a DPV confidence
+    if conf_kind == "driver":
+        logits = torch.from_numpy(4.0 * synth.smooth_texture(rng, DRIVER_D, H_, W_, octaves=2).astype(np.float32))
+        conf = (torch.exp(F.log_softmax(logits, 0).max(0)[0]) ** 2).numpy()[None]
+    else:
+        conf = 1.0 / (1.0 + np.exp(-synth.smooth_texture(rng, 1, H_, W_, octaves=2)))      # in (0, 1), like a DPV confidence
     pert = synth.random_poses(rng, V_, rot_sigma, trans_sigma).astype(np.float64)
     true = poses[0].numpy().astype(np.float64)
     inits = np.stack([pert[v] @ true[v] for v in range(V_)]).astype(np.float32)

@@ -82,7 +82,9 @@ def test_host_pose_helpers_are_bit_equal_to_the_reference(golden):
         assert np.array_equal(misc.UnitQ2Rotation(torch.from_numpy(golden["parallel_11_uq"][n].copy())).numpy(), P[:3, :3])
 
 
-def test_argument_errors_raise_before_device_work(scene, monkeypatch):
+def test_argument_errors_raise_before_device_work_with_20_views_allowed(scene, monkeypatch):
+    """The errors raise before device work; local_BA_direct accepts the driver's 20 views (it runs them in groups of at most
+    ops.MAX_V), the joint form keeps the limit."""
     from neuralrgbd_amd import opt_pose, ops
     ref_frame, src_frames, dmap, conf, inits, _, _ = scene
     cams = lf.cams(lf.H, lf.W)
@@ -100,10 +102,18 @@ def test_argument_errors_raise_before_device_work(scene, monkeypatch):
             fn(ref_frame, src_frames, dmap, conf, cams, [4, 2, 1], poses, 0, 0.01, [1, 1])
         with pytest.raises(ValueError, match="rays"):
             fn(ref_frame, src_frames, dmap, conf, lf.cams(lf.H, lf.W, [2, 2, 1]), [4, 2, 1], poses, 3, 0.01, [1, 1])
-        with pytest.raises(ValueError, match="at most"):
-            fn(ref_frame, src_frames * 5, dmap, conf, cams, [4, 2, 1], poses * 5, 3, 0.01, [1, 1])
+        with pytest.raises(ValueError, match="initial poses"):
+            fn(ref_frame, src_frames * 2, dmap, conf, cams, [4, 2, 1], poses, 3, 0.01, [1, 1])
         with pytest.raises(Exception, match="undefined optmization variable option"):
             fn(ref_frame, src_frames, dmap, conf, cams, [4, 2, 1], poses, 3, 0.01, [1, 2])
+    # the joint form couples the views through one normaliser: one group, at most ops.MAX_V (local_BA_direct takes any number)
+    with pytest.raises(ValueError, match="at most"):
+        opt_pose.local_BA_direct_parallel(ref_frame, src_frames * 5, dmap, conf, cams, [4, 2, 1], poses * 5, 3, 0.01, [1, 1])
+    with pytest.raises(AssertionError, match="device work started"):      # valid: the checks pass, the first group starts
+        opt_pose.local_BA_direct(ref_frame, src_frames * 5, dmap, conf, cams, [4, 2, 1], poses * 5, 3, 0.01, [1, 1])
+    with pytest.raises(ValueError, match="local_BA_direct_parallel: 17 source frames, at most 16"):
+        opt_pose.local_BA_direct_parallel(ref_frame, (src_frames * 5)[:17], dmap, conf, cams, [4, 2, 1], (poses * 5)[:17], 3,
+                                          0.01, [1, 1])
     levels = [[x] for x in (ref_frame, dmap[0, 0], torch.cat(src_frames), conf[0, 0])]
     uq = torch.zeros(4, 3)
     t = torch.zeros(4, 3)
@@ -128,3 +138,87 @@ def test_restatement_converges_on_the_rendered_scene(scene):
     print("[lba] rendered scene: pose error (t, rad) %.4f %.4f -> %.4f %.4f; loss %.4f -> %.4f"
           % (e0[0], e0[1], e1[0], e1[1], r["loss"][0][0], r["loss"][-1][0]))
     assert e1[0] < e0[0] and e1[1] < e0[1]
+
+
+@pytest.fixture(scope="module")
+def wide():
+    return dict(np.load(os.path.join(GOLDEN, "lba_opt_wide.npz")))
+
+
+def _wide_inputs(which):
+    if which == "wide":
+        return lf.inputs(lf.WIDE_SEED, lf.WIDE_H, lf.WIDE_W, lf.WIDE_V, conf_kind="driver"), lf.cams(lf.WIDE_H, lf.WIDE_W)
+    return lf.inputs(lf.PAR16_SEED, lf.PAR16_H, lf.PAR16_W, lf.PAR16_V), lf.cams(lf.PAR16_H, lf.PAR16_W)
+
+
+# The float64 restatement against the reference's recorded wide runs.  Measured spreads (fp32 reference vs float64): the
+# driver's 20-view local_BA_direct (a), opt_vars [1, 1]: loss 9.0e-4 rel, g_t 2.5e-3 rel, |t| 5.3e-5, |uq| 2.3e-5, |pose| 5.3e-5;
+# [0, 1]: loss 4.8e-5, g_t 4.1e-4, |t| 4.8e-6.  The 16-view local_BA_direct_parallel (b): loss 1.2e-6, g_t 3.7e-4, g_uq 7.5e-4,
+# |t| 8.6e-7, |uq| 1.4e-6, |pose| 2.7e-6.  At 256 x 384 with 20 views more pixels sit where fp32 and fp64 select different taps
+# (partly out of frame, confidence down to 1e-2) than in the 4-view 64 x 96 fixture, hence the wider gates of (a).
+WIDE_GATES = {"wide": (2e-3, 5e-3, 1e-4), "par16": (2e-5, 2e-3, 1e-5)}      # loss rel, gradient rel, |t| |uq| |pose|
+
+
+@pytest.mark.parametrize("tag", ["wide_11", "wide_01", "par16_11"])
+def test_fp64_restatement_vs_reference_wide_golden(wide, tag):
+    which = tag.split("_")[0]
+    (ref_frame, src_frames, dmap, conf, inits, _), cams = _wide_inputs(which)
+    assert abs(float(ref_frame.double().sum()) - float(wide[which + "_cks_ref"])) < 1e-6
+    assert abs(float(torch.cat(src_frames).double().sum()) - float(wide[which + "_cks_src"])) < 1e-6
+    assert abs(float(dmap.double().sum()) - float(wide[which + "_cks_dmap"])) < 1e-6
+    assert abs(float(conf.double().sum()) - float(wide[which + "_cks_conf"])) < 1e-6
+    assert np.array_equal(inits.numpy(), wide[which + "_inits"])
+    if which == "wide":                      # the driver's confidence exp(max log-prob)^2: in (0, 1]
+        assert float(conf.min()) > 0 and float(conf.max()) <= 1 and float(conf.min()) < 0.02
+    ov = [int(tag[-2]), int(tag[-1])]
+    levels = lf.level_inputs(ref_frame, src_frames, dmap, conf, cams)
+    r = lf.run(levels, wide[which + "_uq0"], inits[:, :3, 3].numpy(), lf.MAX_ITER, lf.STEP, ov, joint=(which == "par16"))
+    g_loss, g_grad, g_pose = WIDE_GATES[which]
+    e_loss = np.abs(r["loss"] - wide[tag + "_loss"]).max() / np.abs(wide[tag + "_loss"]).max()
+    e_gt = np.abs(r["g_t"] - wide[tag + "_g_t"]).max() / np.abs(wide[tag + "_g_t"]).max()
+    e_guq = np.abs(r["g_uq"] - wide[tag + "_g_uq"]).max() / np.abs(wide[tag + "_g_uq"]).max() if ov[0] == 1 else 0.0
+    e_t = np.abs(r["t"] - wide[tag + "_t"]).max()
+    e_uq = np.abs(r["uq"] - wide[tag + "_uq"]).max()
+    e_P = np.abs(np.stack(lf.uq_to_pose(r["uq"], r["t"])) - wide[tag + "_poses"]).max()
+    print("[parity] LBA %s fp32 reference vs fp64: loss rel %.2e  g_t rel %.2e  g_uq rel %.2e  |t| %.2e  |uq| %.2e  |pose| %.2e"
+          % (tag, e_loss, e_gt, e_guq, e_t, e_uq, e_P))
+    assert e_loss < g_loss and e_gt < g_grad and e_guq < g_grad
+    assert max(e_t, e_uq, e_P) <= g_pose
+    nv = wide[tag + "_poses"].shape[0]
+    assert len(wide[tag + "_prints"]) == len(lf.DW_SCALES) * (nv if which == "wide" else 1)
+
+
+def test_lba_pyramid_rejects_bad_arguments_before_device_work():
+    """ops.lba_pyramid checks the plane count and the kernel sizes before it touches a tensor's device: these raise on CPU
+    tensors with ValueError, not with the no-CPU-fallback error."""
+    from neuralrgbd_amd import ops
+    x = torch.zeros(64, 96)
+    with pytest.raises(ValueError, match="54 planes"):
+        ops.lba_pyramid([x] * (5 + 3 * ops.MAX_V + 1), [2])
+    with pytest.raises(ValueError, match="0 planes"):
+        ops.lba_pyramid([], [2])
+    with pytest.raises(ValueError, match="kernel sizes"):
+        ops.lba_pyramid([x], [1] * (ops.LBA_MAX_LEVELS + 1))
+    with pytest.raises(ValueError, match="kernel sizes"):
+        ops.lba_pyramid([x], [65])                          # a level of 0 rows
+    with pytest.raises(ValueError, match="kernel sizes"):
+        ops.lba_pyramid([x], [4, 0])
+
+
+def test_lba_pyramid_c_abi_rejects_bad_shapes_before_device_work():
+    """nrgbd_lba_pyramid checks its arguments before any launch: 54 planes (> 5 + 3 MAX_V), 9 levels, a level of size 0."""
+    import ctypes
+    from neuralrgbd_amd import _lib, ops
+    lib = _lib.load()
+    fake = (ctypes.c_void_p * 64)(*([16] * 64))            # never dereferenced: the calls must return before a launch
+    out = ctypes.c_void_p(16)
+
+    def call(nplanes, H, W, ks):
+        k = (ctypes.c_int * max(1, len(ks)))(*ks)
+        return lib.nrgbd_lba_pyramid(fake, nplanes, H, W, k, len(ks), out, None)
+    e_shape = call(5 + 3 * ops.MAX_V + 1, 64, 96, [4])
+    assert e_shape == -2                                     # NRGBD_E_SHAPE
+    assert call(1, 64, 96, [1] * (ops.LBA_MAX_LEVELS + 1)) == e_shape
+    assert call(1, 64, 96, [65]) == e_shape                 # 64 // 65 = 0 rows
+    assert call(1, 64, 96, [0]) == e_shape
+    assert call(0, 64, 96, [2]) == e_shape
