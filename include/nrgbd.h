@@ -49,8 +49,8 @@ extern "C" {
  * is new.  0.5 (round 6): the three BatchNorm finalisers take (collapse_count, batches_tracked) before `stream`; nrgbd_pack_nhwc takes
  * rgb4, nrgbd_conv2d_taps_f32 takes in_stride; nrgbd_avgpool_cl, nrgbd_scatter_channels and nrgbd_conv2d_few_f32 are new.
  * 0.6: the local bundle adjustment entries nrgbd_lba_pyramid, nrgbd_lba_workgroups, nrgbd_lba_grad and nrgbd_lba_update are new;
- * no existing entry changed. */
-#define NRGBD_INTERFACE_VERSION "0.6"
+ * no existing entry changed.  0.7: nrgbd_bn_small_stats (the SPP branches' BatchNorm statistics) is new; no existing entry changed. */
+#define NRGBD_INTERFACE_VERSION "0.7"
 const char* nrgbd_version(void);
 const char* nrgbd_strerror(int code);
 
@@ -555,7 +555,9 @@ int nrgbd_rnet_pack(const float* dpv_log, const float* feat, int feat_planar, fl
  *   Cin % 16 == 0; (Cout, dilation) in {(32,1), (64,1), (96,1), (128,1), (128,2)}; N*H*W*Cin < 2^32.
  * nrgbd_bn_finalize: partials [num_workgroups][2*C] -> scale_shift [C][2] = (gamma*invstd, beta - mean*gamma*invstd),
  *   reduced in double; running_mean / running_var (both or neither) get the train-mode update.
- *   VARIANCE COLLAPSE (all three finalisers): the variance is E[y^2] - mean^2 over fp32 per-tile partials; a channel whose computed
+ *   VARIANCE COLLAPSE (all three finalisers, i.e. wherever the statistics are unshifted fp32 partials of a long reduction: the
+ *   feature-CNN trunk, its 1x1 shortcuts and the K-Net; NOT the SPP branches, which use nrgbd_bn_small_stats): the variance is
+ *   E[y^2] - mean^2 over fp32 per-tile partials; a channel whose computed
  *   variance is below 1e-5 mean^2 (std / |mean| < 3.2e-3: no correct digit left; the reference's two-pass statistics would still
  *   normalise it) gets scale = shift = NaN AND is counted into *collapse_count (device word, may be NULL; atomicAdd of 1 per
  *   channel) — the kernels' ReLU maps NaN to 0, so the NaN alone could vanish again; the host mirror raises on a non-zero word.
@@ -609,10 +611,27 @@ int nrgbd_bn_finalize(const float* stats, int num_workgroups, int C, long count,
  * bilinear, align_corners=True) (:153-158), and the torch.cat of (output_raw, output_skip, branch4, branch3, branch2, branch1)
  * (:160).  out[pixel] = [ quarter (Cq) | deep (Cd) | up(relu(bz0 * s + t)) | up(.. bz1) | up(.. bz2) | up(.. bz3) ].
  *   quarter [N][h][w][Cq], deep [N][h][w][Cd]; branch i: raw 1x1-conv output bz_i [N][bh_i][bw_i][Cb] and the (scale, shift)
- *   [Cb][2] of its BatchNorm (nrgbd_bn_finalize); out [N][h][w][Cq + Cd + 4 Cb]; all channel counts % 4 == 0,
+ *   [Cb][2] of its BatchNorm (nrgbd_bn_small_stats); out [N][h][w][Cq + Cd + 4 Cb]; all channel counts % 4 == 0,
  *   Cq + Cd + 4 Cb <= 512 (a workgroup = four pixels' 16-byte words: 320 channels in models/psm_submodule.py), h, N <= 65535.
  * Interpolation arithmetic = ATen upsample_bilinear2d (fp32 scale (in-1)/(out-1), lambda clamped to [0,1]).
  */
+/*
+ * nrgbd_bn_small_stats — BatchNorm batch statistics of up to four SMALL channels-last maps in one launch: the SPP branches of the
+ * feature CNN (models/psm_submodule.py:100-117 convbn behind AvgPool2d((64,64)) .. ((8,8)); the reference never leaves train
+ * mode, so their BatchNorm2d normalises with the statistics of the V + 1 frames: 5 values per channel at the 64-window of a
+ * 256x384 image).  Segment i: x[i] [rows[i]][C] contiguous (the raw 1x1-conv output of nrgbd_conv2d_taps_f32, no statistics
+ * epilogue needed) -> scale_shift[i] [C][2] = (gamma*invstd, beta - mean*gamma*invstd), the operand of nrgbd_spp_concat.
+ *   Mean and variance are sums in double over the values themselves, shifted by the channel's row-0 value k (sum (y - k),
+ *   sum (y - k)^2): ~50 correct bits
+ *   relative even when the five frames of a static camera agree to a few ulps, where E[y^2] - mean^2 has no digit left.  So
+ *   there is no collapse guard and no status word: an exactly constant channel normalises to beta, as in the reference.
+ *   running_mean / running_var (arrays of nseg pointers or NULL; per segment both or neither): the train-mode update with
+ *   momentum[i] and the unbiased variance; batches_tracked (NULL or nseg pointers, each may be NULL): `+= 1`.
+ *   nseg in 1..4, 1 <= C <= 1024, rows[i] >= 1.  The pointer arrays are host memory read during the call (capture-safe).
+ */
+int nrgbd_bn_small_stats(int nseg, const float* const* x, const long* rows, int C, const float* const* gamma, const float* const* beta,
+                     const float* eps, const float* momentum, float* const* running_mean, float* const* running_var,
+                     long long* const* batches_tracked, float* const* scale_shift, void* stream);
 int nrgbd_spp_concat(const float* quarter, int Cq, const float* deep, int Cd,
                      const float* bz0, const float* bss0, int bh0, int bw0, const float* bz1, const float* bss1, int bh1, int bw1,
                      const float* bz2, const float* bss2, int bh2, int bw2, const float* bz3, const float* bss3, int bh3, int bw3,

@@ -99,6 +99,7 @@ SIGNATURES = {
     "nrgbd_bias_lrelu_cl_fwd": (_I, [_P, _P, _F, _P, _L, _I, _P]),
     "nrgbd_bias_lrelu_cl_bwd": (_I, [_P, _P, _F, _P, _P, _P, _L, _I, _P]),
     "nrgbd_upsample_bilinear_ac": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "nrgbd_bn_small_stats": (_I, [_I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "nrgbd_spp_concat": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _I, _I, _I, _P]),
     "nrgbd_nhwc_stats_workgroups": (_I, [_L]),
     "nrgbd_nhwc_stats": (_I, [_P, _L, _I, _P, _P]),

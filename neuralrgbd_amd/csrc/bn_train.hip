@@ -232,6 +232,69 @@ static int bias_lrelu_groups(long rows, int C) {
     return (int)(g < 1 ? 1 : (g > 512 ? 512 : g));
 }
 
+// ---- exact batch statistics of up to four SMALL channels-last maps in one launch: the BatchNorms of the SPP branches
+// (models/psm_submodule.py:100-117 convbn after AvgPool2d 64/32/16/8), whose statistics run over a handful of values per channel
+// (V + 1 = 5 at the 64-window of a 256x384 image: one cell per frame).  When the camera stands still those values agree to a few
+// ulps, and E[y^2] - mean^2 over the conv epilogue's fp32 partials (bn_finalize_channel) has no digit left; the reference (ATen:
+// two-pass on the CPU, Welford on the GPU) still normalises such a channel to ~beta.  Here each value is shifted by the channel's
+// row-0 value k in double (exact for two floats within 2^29 of each other) and sum (y - k), sum (y - k)^2 are added in double:
+// the variance E[(y-k)^2] - E[y-k]^2 keeps ~50 bits when |mean| >> std, so there is no collapse guard.  grid (ceil(C/32),
+// segments), block 1024 = 32 channels x 32 row slices (the loads of a slice are unrolled: at config B the 8-window branch has
+// 3840 rows and a one-load-at-a-time loop was latency bound at ~100 us), slices added in a fixed order (bitwise reproducible).
+constexpr int kSmallStatsThreads = 1024, kSmallStatsLanes = 32, kSmallStatsSlices = kSmallStatsThreads / kSmallStatsLanes;
+constexpr int kSmallStatsMaxSeg = 4;
+struct BnSmallArgs {
+    const float* x[kSmallStatsMaxSeg];
+    long rows[kSmallStatsMaxSeg];
+    const float* gamma[kSmallStatsMaxSeg];
+    const float* beta[kSmallStatsMaxSeg];
+    float eps[kSmallStatsMaxSeg], momentum[kSmallStatsMaxSeg];
+    float* running_mean[kSmallStatsMaxSeg];
+    float* running_var[kSmallStatsMaxSeg];
+    long long* batches_tracked[kSmallStatsMaxSeg];
+    float* ss[kSmallStatsMaxSeg];
+};
+
+__global__ __launch_bounds__(kSmallStatsThreads) void bn_small_stats_kernel(const BnSmallArgs a, int C) {
+    __shared__ double sh[2][kSmallStatsSlices][kSmallStatsLanes];
+    const int seg = blockIdx.y, lane = threadIdx.x % kSmallStatsLanes, sl = threadIdx.x / kSmallStatsLanes;
+    const int c = blockIdx.x * kSmallStatsLanes + lane;
+    const float* __restrict__ x = a.x[seg];
+    const long rows = a.rows[seg];
+    const double k = c < C ? (double)x[c] : 0.0;              // pivot: the channel's value in row 0
+    double s1 = 0.0, s2 = 0.0;
+    if (c < C) {
+#pragma unroll 8
+        for (long r = sl; r < rows; r += kSmallStatsSlices) {
+            const double d = (double)x[r * C + c] - k;
+            s1 += d;
+            s2 = __builtin_fma(d, d, s2);
+        }
+    }
+    sh[0][sl][lane] = s1; sh[1][sl][lane] = s2;
+    __syncthreads();
+    if (sl != 0 || c >= C) return;
+    for (int q = 1; q < kSmallStatsSlices; ++q) { s1 += sh[0][q][lane]; s2 += sh[1][q][lane]; }
+    const double dm = s1 / (double)rows;
+    const double mean = k + dm;
+    double var = s2 / (double)rows - dm * dm;   // biased: what normalises (train mode)
+    var = var > 0.0 ? var : 0.0;
+    const float invstd = (float)(1.0 / sqrt(var + (double)a.eps[seg]));
+    const float sc = a.gamma[seg][c] * invstd;
+    float* ss = a.ss[seg];
+    ss[2 * c] = sc;
+    ss[2 * c + 1] = (float)((double)a.beta[seg][c] - mean * (double)sc);
+    if (a.running_mean[seg]) {
+        const float mom = a.momentum[seg];
+        float* rm = a.running_mean[seg];
+        float* rv = a.running_var[seg];
+        rm[c] = (1.f - mom) * rm[c] + mom * (float)mean;
+        const double unbiased = rows > 1 ? var * (double)rows / (double)(rows - 1) : var;
+        rv[c] = (1.f - mom) * rv[c] + mom * (float)unbiased;
+    }
+    if (c == 0 && a.batches_tracked[seg]) *a.batches_tracked[seg] += 1;   // nn.BatchNorm's num_batches_tracked side effect
+}
+
 static bool bn_cl_shape_ok(long rows, int C) {
     return rows > 0 && C >= 4 && C <= 1024 && (C & 3) == 0 && kBnclThreads % (C >> 2) == 0;
 }
@@ -310,6 +373,32 @@ extern "C" int nrgbd_bias_lrelu_cl_bwd(const float* y, const float* gy, float sl
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(bias_lrelu_bwd_kernel, dim3(G), dim3(kBnclThreads), 0, s, y, gy, slope, gx, partial, rows, C);
     hipLaunchKernelGGL(bias_lrelu_finalize_kernel, dim3((C + 15) / 16), dim3(kBnclThreads), 0, s, partial, G, C, g_bias);
+    NRGBD_CHECK_LAUNCH();
+    return NRGBD_OK;
+}
+
+/* exact batch statistics of up to four small channels-last maps (the SPP branches): see bn_small_stats_kernel above. */
+extern "C" int nrgbd_bn_small_stats(int nseg, const float* const* x, const long* rows, int C, const float* const* gamma,
+                                const float* const* beta, const float* eps, const float* momentum, float* const* running_mean,
+                                float* const* running_var, long long* const* batches_tracked, float* const* scale_shift, void* stream) {
+    using namespace nrgbd;
+    if (!x || !rows || !gamma || !beta || !eps || !momentum || !scale_shift) return NRGBD_E_NULL;
+    if (nseg < 1 || nseg > kSmallStatsMaxSeg || C < 1 || C > 1024) return NRGBD_E_SHAPE;
+    BnSmallArgs a = {};
+    for (int i = 0; i < nseg; ++i) {
+        if (!x[i] || !gamma[i] || !beta[i] || !scale_shift[i]) return NRGBD_E_NULL;
+        if (rows[i] < 1) return NRGBD_E_SHAPE;
+        float* rm = running_mean ? running_mean[i] : nullptr;
+        float* rv = running_var ? running_var[i] : nullptr;
+        if ((rm == nullptr) != (rv == nullptr)) return NRGBD_E_NULL;
+        a.x[i] = x[i]; a.rows[i] = rows[i]; a.gamma[i] = gamma[i]; a.beta[i] = beta[i];
+        a.eps[i] = eps[i]; a.momentum[i] = momentum[i];
+        a.running_mean[i] = rm; a.running_var[i] = rv;
+        a.batches_tracked[i] = batches_tracked ? batches_tracked[i] : nullptr;
+        a.ss[i] = scale_shift[i];
+    }
+    hipLaunchKernelGGL(bn_small_stats_kernel, dim3((C + kSmallStatsLanes - 1) / kSmallStatsLanes, nseg), dim3(kSmallStatsThreads), 0,
+                       (hipStream_t)stream, a, C);
     NRGBD_CHECK_LAUNCH();
     return NRGBD_OK;
 }

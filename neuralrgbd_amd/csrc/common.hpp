@@ -221,7 +221,13 @@ inline hipError_t set_max_dynamic_lds(const void* func, int bytes) {
 // synchronisation point (neuralrgbd_amd.nets.check_status: KVNET's valid_dpv probe, DepthStream.step) instead of handing out a
 // wrong depth map.  No collapse reported => computed var >= 1e-5 mean^2 and true var <= computed + 1.5e-5 mean^2 <= 2.5 x computed:
 // inside relu_unit's factor 4.
-// (A channel that is exactly constant and non-zero would trip it too; a convolution without bias over a non-constant input has none.)
+// WHERE IT APPLIES: every user of this function — the finalisers of unshifted fp32 partials over long reductions (the feature-CNN
+// trunk and its 1x1 shortcuts, the K-Net).  NOT the SPP branches: their counts are tiny (5 values per channel at the 64-window of a
+// 256x384 image, one cell per frame), a static camera makes those values agree to a few ulps, and the reference still normalises
+// them; they take pivot-shifted fp64 statistics without a guard (bn_train.hip bn_small_stats_kernel, nets._bn_scale_shift_small).
+// (A channel that is exactly constant and non-zero would trip it too; a convolution without bias over a non-constant input has none.
+// Known limit: a textureless region that makes a trunk channel exactly constant over the whole window — zero padding at the map
+// borders makes such channels non-constant in practice.)
 constexpr double kBnCollapse = 1e-5;
 __device__ __forceinline__ void bn_finalize_channel(double sum, double sumsq, double count, float gamma, float beta, float eps,
                                                     float momentum, float* running_mean, float* running_var, float* ss, int c,

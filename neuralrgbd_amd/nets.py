@@ -200,7 +200,8 @@ def status_word(device):
 
 
 def check_status(device):
-    """Raise NrgbdError when a BatchNorm finaliser reported a variance collapse since the last check (one device -> host read of
+    """Raise NrgbdError when a BatchNorm finaliser of the trunk or the K-Net (not the SPP branches: _bn_scale_shift_small)
+    reported a variance collapse since the last check (one device -> host read of
     4 bytes: called where the path synchronises anyway — misc.valid_dpv, DepthStream's deferred probe).  The reference's two-pass
     statistics would still normalise such a channel; this path cannot (E[y^2] - mean^2 has no digit left), and says so instead of
     handing out a wrong depth map."""
@@ -239,6 +240,40 @@ def _bn_scale_shift(bn, stats, count, cm=False):
                    batches_tracked=nbt)
     sc = bn.weight.detach() * torch.rsqrt(bn.running_var + bn.eps)
     return torch.stack((sc, bn.bias.detach() - bn.running_mean * sc), dim=1).contiguous()
+
+
+def _bn_scale_shift_small(bns, zs):
+    """(scale, shift) [C,2] of the BatchNorms `bns` over the small maps `zs` (the SPP branches): train mode = ONE launch of
+    float64 statistics over the values themselves, shifted by each channel's first value (ops.bn_small_stats) incl. the running-statistics side effect.  Their
+    counts are tiny (5 values per channel at the 64-window of a 256x384 image) and agree to a few ulps when the camera stands
+    still; E[y^2] - mean^2 has no digit left there (the collapse guard of _bn_scale_shift would raise), the reference does not
+    fail, and neither does this.  Eval mode: the running statistics, as _bn_scale_shift."""
+    from . import ops
+    out = [None] * len(bns)
+    live = [k for k, bn in enumerate(bns) if _needs_stats(bn)]
+    for k, bn in enumerate(bns):
+        if k not in live:
+            out[k] = _bn_scale_shift(bn, None, 0)
+    if live:
+        eps, mom, rms, rvs, nbts = [], [], [], [], []
+        for k in live:
+            bn = bns[k]
+            upd = bn.training and bn.track_running_stats
+            nbt = None
+            if upd and bn.momentum is None:       # cumulative average: the factor needs the counter's value on the host
+                bn.num_batches_tracked += 1
+            elif upd:
+                nbt = bn.num_batches_tracked      # incremented by the kernel itself
+            eps.append(bn.eps)
+            mom.append(bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked))
+            rms.append(bn.running_mean if upd else None)
+            rvs.append(bn.running_var if upd else None)
+            nbts.append(nbt)
+        sss = ops.bn_small_stats([zs[k] for k in live], [bns[k].weight.detach() for k in live], [bns[k].bias.detach() for k in live],
+                             eps, mom, rms, rvs, nbts)
+        for k, ss in zip(live, sss):
+            out[k] = ss
+    return out
 
 
 def _needs_stats(bn):
@@ -400,16 +435,20 @@ class PSMFeatures(_PackedWeightsMixin, nn.Module):
         count = z.shape[0] * z.shape[1] * z.shape[2]
         return _Act(z, _bn_scale_shift(bn, st, count, cm=wino), relu), mat
 
-    def _pointwise_bn_cl(self, seq, m, stride=1):
-        """1x1 Sequential(conv, bn) on a materialised channels-last tensor: the 1-tap form of csrc/conv2d.hip + statistics."""
+    def _pointwise_cl(self, conv, m, stride=1, want_stats=False):
+        """1x1 convolution on a materialised channels-last tensor: the 1-tap form of csrc/conv2d.hip [+ statistics partials]."""
         from . import ops
-        conv, bn = seq[0], seq[1]
         N, H, W, C = m.shape
         if C % 16 != 0 or conv.out_channels not in (32, 64, 128) or H % stride or W % stride:
             raise _no_kernel("1x1 layer %d -> %d, stride %d on a %d x %d map" % (C, conv.out_channels, stride, H, W))
         # a strided shortcut (psm_submodule.py:127-131) reads every stride-th pixel inside the kernel: no gather pass
-        z, st = ops.conv2d_taps(m.contiguous(), _packed_weights(self, conv), conv.out_channels, 1, want_stats=_needs_stats(bn), stride=stride)
-        return _Act(z, _bn_scale_shift(bn, st, N * (H // stride) * (W // stride)), False)
+        return ops.conv2d_taps(m.contiguous(), _packed_weights(self, conv), conv.out_channels, 1, want_stats=want_stats, stride=stride)
+
+    def _pointwise_bn_cl(self, seq, m, stride=1):
+        """1x1 Sequential(conv, bn) on a materialised channels-last tensor: the 1-tap form of csrc/conv2d.hip + statistics."""
+        conv, bn = seq[0], seq[1]
+        z, st = self._pointwise_cl(conv, m, stride, want_stats=_needs_stats(bn))
+        return _Act(z, _bn_scale_shift(bn, st, z.shape[0] * z.shape[1] * z.shape[2]), False)
 
     def _block_cl(self, blk, a):
         """BasicBlock (psm_submodule.py:31-50): out = bn(conv2(relu(bn(conv1(x))))) + shortcut(x), no ReLU after the add."""
@@ -474,23 +513,18 @@ class PSMFeatures(_PackedWeightsMixin, nn.Module):
             pools = {8: p8, 16: p16, 32: p32, 64: ops.avgpool_cl(p32, 2)}
         else:
             pools = {k: ops.avgpool_cl(deep, k) for k in self.SPP_WINDOWS}
-        pyramid, fused = [], []
+        zs, norms = [], []
         for i in (4, 3, 2, 1):
             branch = getattr(self, "branch%d" % i)
-            pool = pools[self.SPP_WINDOWS[i - 1]]
-            pb = self._pointwise_bn_cl(branch[1], pool)                    # 1x1 conv + BatchNorm statistics on the tiny map
-            if pb.ss is not None:
-                fused.append((pb.z, pb.ss))                                # normalise + ReLU at the taps of spp_concat
-                continue
-            y = ops.nhwc_act(pb.z, pb.ss, True).permute(0, 3, 1, 2)        # eval-mode norm: channels-last memory, NCHW view
-            y = F.interpolate(y, size=(h, w), mode="bilinear", align_corners=True)
-            pyramid.append(y.permute(0, 2, 3, 1))                          # channels-last in memory already
-        if len(fused) == 4:
-            # BatchNorm + ReLU of the four tiny maps, their bilinear up-sampling and the 320-channel concat in ONE launch
-            # (csrc/spp.hip) instead of 4 nhwc_act + 4 upsample_bilinear2d + 3 CatArrayBatchedCopy
-            cat = ops.spp_concat(quarter, deep, fused)
-        else:
-            cat = torch.cat([quarter, deep] + pyramid, dim=3)              # [N,h,w,320]
+            z, _ = self._pointwise_cl(branch[1][0], pools[self.SPP_WINDOWS[i - 1]])   # 1x1 conv on the tiny map
+            zs.append(z)
+            norms.append(branch[1][1])
+        # the four branches' BatchNorm statistics in ONE launch, pivot-shifted in float64 over the tiny maps (a static camera makes
+        # the 64-window's five values per channel agree to a few ulps: see _bn_scale_shift_small) ...
+        sss = _bn_scale_shift_small(norms, zs)
+        # ... then BatchNorm + ReLU of the four tiny maps, their bilinear up-sampling and the 320-channel concat in ONE launch
+        # (csrc/spp.hip) instead of 4 nhwc_act + 4 upsample_bilinear2d + 3 CatArrayBatchedCopy
+        cat = ops.spp_concat(quarter, deep, list(zip(zs, sss)))
         y, _ = self._conv_bn_cl(self.lastconv[0], _Act(cat), relu=True)
         head = self.lastconv[2]
         if head.out_channels not in (32, 64, 128):

@@ -923,6 +923,45 @@ def bn_finalize(stats, count, gamma, beta, eps, momentum, running_mean=None, run
     return ss
 
 
+def bn_small_stats(xs, gammas, betas, eps, momentum, running_means=None, running_vars=None, batches_tracked=None):
+    """Pivot-shifted float64 batch statistics of 1..4 small channels-last maps xs[i] [..., C] in one launch (nrgbd_bn_small_stats: the
+    SPP branches) -> [scale_shift [C,2] per map]; updates the running statistics (unbiased variance) and batches_tracked in
+    place where given.  eps, momentum: one value for all maps or one per map.  No collapse guard: nothing to report."""
+    n = len(xs)
+    if not 1 <= n <= 4 or len(gammas) != n or len(betas) != n:
+        raise ValueError("bn_small_stats: 1 to 4 maps with one gamma and beta each, got %d / %d / %d" % (n, len(gammas), len(betas)))
+    xs = [_need(x, "x") for x in xs]
+    C = xs[0].shape[-1]
+    if any(x.shape[-1] != C for x in xs):
+        raise ValueError("bn_small_stats: the maps must share one channel count, got %s" % [tuple(x.shape) for x in xs])
+    per = lambda v: [float(u) for u in v] if isinstance(v, (list, tuple)) else [float(v)] * n
+    eps, momentum = per(eps), per(momentum)
+    rms = list(running_means) if running_means is not None else [None] * n
+    rvs = list(running_vars) if running_vars is not None else [None] * n
+    nbts = list(batches_tracked) if batches_tracked is not None else [None] * n
+    if len(eps) != n or len(momentum) != n or len(rms) != n or len(rvs) != n or len(nbts) != n:
+        raise ValueError("bn_small_stats: one eps / momentum / running statistic per map")
+    dev = xs[0].device
+    ss = [torch.empty((C, 2), dtype=torch.float32, device=dev) for _ in range(n)]
+    ptrs = lambda ts: (ctypes.c_void_p * n)(*[0 if t is None else t.data_ptr() for t in ts])
+    gammas = [_need(g, "gamma", (C,)) for g in gammas]
+    betas = [_need(b, "beta", (C,)) for b in betas]
+    for i in range(n):
+        if (rms[i] is None) != (rvs[i] is None):
+            raise ValueError("bn_small_stats: running_mean and running_var come together")
+        for t, name in ((rms[i], "running_mean"), (rvs[i], "running_var")):
+            if t is not None and _need(t, name, (C,)) is not t:
+                raise ValueError("bn_small_stats: %s must be contiguous (it is updated in place)" % name)
+        _nbt_ptr(nbts[i], xs[i])
+    keep = (ptrs(xs), (ctypes.c_long * n)(*[x.numel() // C for x in xs]), ptrs(gammas), ptrs(betas), (ctypes.c_float * n)(*eps),
+            (ctypes.c_float * n)(*momentum), ptrs(rms), ptrs(rvs), ptrs(nbts), ptrs(ss))
+    with torch.cuda.device(dev):
+        rc = _lib.load().nrgbd_bn_small_stats(n, *[ctypes.cast(a, ctypes.c_void_p) for a in keep[:2]], int(C),
+                                          *[ctypes.cast(a, ctypes.c_void_p) for a in keep[2:]], _stream(xs[0]))
+    _lib.check(rc, "nrgbd_bn_small_stats")
+    return ss
+
+
 def conv_wino_rnet(x, w_wino, cout, bias=None, lrelu=True, out=None, ycoff=0, cout_valid=None):
     """R-Net conv2d_leakyRelu block in the Winograd domain: x [N,H,W,Cin] -> leaky_relu(conv3x3(x) + bias).
     `cout` = columns of the packed weights (% 64, or 32: the HALF form, whose stream is the 64-column one with the upper half zero);

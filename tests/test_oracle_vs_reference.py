@@ -148,3 +148,46 @@ def test_resample_with_new_candidates_vs_live_reference(live):
                           math.tan(math.radians(cam["hfov"]) * .5), math.tan(math.radians(cam["vfov"]) * .5), pad,
                           clamp=None, d_candi_new=d_candi)
     assert np.array_equal(got, want)
+
+
+def test_oracle_on_a_static_window_vs_live_reference():
+    """A camera standing still: five identical images (ordinary poses, so depth is defined).  The SPP 64-window BatchNorm then sees
+    five equal values per channel.  The oracle's feature CNN and two frames of step() against the UNMODIFIED reference run here
+    (oracle/ref_shim.py), with the gates of test_oracle_golden.py::test_whole_path_two_frames (the path's own pose inverse): the
+    checker of tests/test_gpu_static_window.py is valid on such windows, and the reference's outputs there are finite."""
+    from oracle import ref_shim
+    if not ref_shim.available():
+        pytest.skip("the unmodified reference is not present on this machine")
+    from neuralrgbd_amd import synth
+    from oracle import gen_golden
+    from oracle import kvnet_oracle as ko
+    ref = ref_shim.load()
+    H, W, D = 256, 256, 16
+    cam = camera.scannet_intrinsics(W // 4, H // 4)
+    d_candi = np.linspace(0.1, 5.0, D)
+    with ref_shim.quiet():
+        model = ref.KVNET.KVNET(64, cam, d_candi, 10.0, 64, None, if_refined=True, refineNet_name="DPV", t_win_r=2)
+    sd = synth.seeded_state_dict(model, 0)
+    model.load_state_dict(sd)
+    rng = np.random.RandomState(11)
+    img = torch.from_numpy(synth.smooth_texture(rng, 3, H, W))[None]
+    src = img[None].expand(1, 4, 3, H, W).contiguous()
+    poses = torch.from_numpy(synth.random_poses(rng, 4)[None])
+    x = torch.cat((src[0], img), 0)
+    with torch.no_grad():
+        l1_ref, f_ref = model.feature_extractor(x)
+        l1_o, f_o = ko.feature_cnn(sd, "feature_extractor.feature_extraction", x)
+    assert torch.isfinite(f_ref).all()
+    for name, got, want in (("layer1", l1_o, l1_ref), ("feature", f_o, f_ref)):
+        mx, _, _ = report("static window oracle vs reference " + name, got.numpy(), want.numpy())
+        assert mx < 1e-4 * max(1.0, float(want.abs().max()))
+    (dpv1, pred1, _), (dpv2, pred2, _) = gen_golden.run_stream(ref, model, cam, d_candi, [(img, src, poses)] * 2)
+    o1 = ko.step(sd, img, src, poses, cam, d_candi, 10.0, None)
+    o2 = ko.step(sd, img, src, poses, cam, d_candi, 10.0, o1[3])
+    for name, got, want, tol in (("BV_cur f1", o1[2], dpv1, 2e-4), ("BV_predict f1", o1[3], pred1, 1e-3), ("DPV f2", o2[1], dpv2, 1e-3),
+                                 ("BV_predict f2", o2[3], pred2, 1e-3)):
+        assert torch.isfinite(want).all(), name
+        mx, mean, _ = report("static window oracle vs reference " + name, got[0].numpy(), want[0].numpy())
+        assert mx < tol and mean < 1e-4, name
+    assert (o1[2][0].argmax(0) != dpv1[0].argmax(0)).sum() == 0
+    assert (o2[1][0].argmax(0) != dpv2[0].argmax(0)).sum() == 0
