@@ -49,8 +49,9 @@ extern "C" {
  * is new.  0.5 (round 6): the three BatchNorm finalisers take (collapse_count, batches_tracked) before `stream`; nrgbd_pack_nhwc takes
  * rgb4, nrgbd_conv2d_taps_f32 takes in_stride; nrgbd_avgpool_cl, nrgbd_scatter_channels and nrgbd_conv2d_few_f32 are new.
  * 0.6: the local bundle adjustment entries nrgbd_lba_pyramid, nrgbd_lba_workgroups, nrgbd_lba_grad and nrgbd_lba_update are new;
- * no existing entry changed.  0.7: nrgbd_bn_small_stats (the SPP branches' BatchNorm statistics) is new; no existing entry changed. */
-#define NRGBD_INTERFACE_VERSION "0.7"
+ * no existing entry changed.  0.7: nrgbd_bn_small_stats (the SPP branches' BatchNorm statistics) is new; no existing entry changed.
+ * 0.8: nrgbd_dpv_keyframe_maps (the LBA driver's depth / confidence maps in one launch) is new; no existing entry changed. */
+#define NRGBD_INTERFACE_VERSION "0.8"
 const char* nrgbd_version(void);
 const char* nrgbd_strerror(int code);
 
@@ -241,6 +242,28 @@ int nrgbd_dpv_resample_to(const float* dpv, const float* T, const float* rays,
                           float z_half, float z_radius, float pad_value,
                           int do_clamp, float clamp_lo, float clamp_hi,
                           float* out, int D_src, int D_out, int h, int w, void* stream);
+
+/*
+ * nrgbd_dpv_keyframe_maps — the four [h][w] maps the local bundle adjustment reads, from a log-DPV in one launch, without
+ * the resampled volume.
+ * Replaces, per frame of the LBA driver: test_KVNet_LBA.py:414-419 (resample_vol_cuda(..., d_candi_new=d_candi) and its
+ * .clamp), :420 / :422 (mutils/misc.py:532-548 depth_val_regression of BVs_measure and of the resampled volume), :421 / :423
+ * (torch.max over the candidates) and :455 / :495 (torch.exp(conf) ** 2).
+ *   dmap_kf[p]  = sum_k expf(v_k[p]) * d_candi_out[k] in candidate order k = 0 .. D_out-1, v_k = the value
+ *                 nrgbd_dpv_resample_to writes at plane k (same arithmetic, same bits), clamp included;
+ *   conf_kf[p]  = c * c, c = exp(max_k v_k[p]) correctly rounded (as nrgbd_export_depth_u16's confidence);
+ *   dmap_ref / conf_ref: the same two reductions of dpv itself with d_candi_src [D_src].
+ * Either pair may be NULL (both pointers, or one of them): it is not computed.  The driver needs the reference pair only in
+ * the first window after a start or a refresh.  d_candi_src is required only with the reference pair; T, rays and
+ * d_candi_out only with the keyframe pair.  Other arguments and error codes as nrgbd_dpv_resample_to.  No allocation, no
+ * host synchronisation: safe to capture into a hipGraph.
+ */
+int nrgbd_dpv_keyframe_maps(const float* dpv, const float* T, const float* rays,
+                            const float* d_candi_out, const float* d_candi_src,
+                            float tan_hh, float tan_hv, float z_half, float z_radius, float pad_value,
+                            int do_clamp, float clamp_lo, float clamp_hi,
+                            float* dmap_kf, float* conf_kf, float* dmap_ref, float* conf_ref,
+                            int D_src, int D_out, int h, int w, void* stream);
 
 /*
  * nrgbd_logsoftmax_d — log-softmax over the depth axis of scale*a (+ b).

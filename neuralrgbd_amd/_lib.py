@@ -38,6 +38,7 @@ SIGNATURES = {
                                _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "nrgbd_dpv_resample": (_I, [_P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _F, _F, _P, _I, _I, _I, _P]),
     "nrgbd_dpv_resample_to": (_I, [_P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _F, _F, _P, _I, _I, _I, _I, _P]),
+    "nrgbd_dpv_keyframe_maps": (_I, [_P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _F, _F, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "nrgbd_logsoftmax_d": (_I, [_P, _P, _F, _P, _I, _L, _P]),
     "nrgbd_depth_regress": (_I, [_P, _P, _P, _P, _I, _L, _P]),
     "nrgbd_export_depth_u16": (_I, [_P, _P, _F, _F, _P, _P, _P, _P, _I, _L, _P]),

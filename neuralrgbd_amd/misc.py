@@ -1,6 +1,7 @@
 """Small helpers of the depth path (the used part of code/mutils/misc.py)."""
 import math
 
+import numpy as np
 import torch
 
 from . import homography as _homo
@@ -148,3 +149,48 @@ def Rotation2UnitQ(R):
     Rotation2Quaternion(R, r_q)
     quat_to_unitQ(r_q, r_uq)
     return r_uq
+
+
+def get_twin_rel_pose(traj_extMs, ref_indx, t_win_r, dat_indx_step, use_gt_R=False, use_gt_t=False, dataset=None,
+                      add_noise_gt=False, noise_sigmas=None, traj_extMs_dso=None, use_dso_R=False, use_dso_t=False,
+                      opt_next_frame=False):
+    """Initial relative poses (reference -> source, 4x4 CPU float32 tensors) of the source frames of the local time window
+    around ref_indx, and the trajectory indices they will be written back to (mutils/misc.py:21-98; same signature and
+    returns).  The LAST frame of the window has no pose of its own yet: it starts from its neighbour's, index
+    ref_indx + t_win_r * dat_indx_step - 1, while the returned index list names the frame itself.  opt_next_frame adds
+    ref_indx + 1 after the past frames.  traj_extMs_dso (+ use_dso_R / use_dso_t) overrides the last pose's rotation /
+    translation with the tracker's own motion ref -> last; use_gt_R / use_gt_t override every pose from dataset[i]['extM']
+    (optionally with Gaussian noise of noise_sigmas = (sigma_R, sigma_t))."""
+    if use_dso_R or use_dso_t:
+        assert traj_extMs_dso is not None
+    span = t_win_r * dat_indx_step
+    past = list(range(ref_indx - span, ref_indx, dat_indx_step))
+    nxt = [ref_indx + 1] if opt_next_frame else []
+    last = ref_indx + span
+    src_frame_idx = past + nxt + list(range(ref_indx + dat_indx_step, last - dat_indx_step + 1, dat_indx_step)) + [last - 1]
+    src_frame_idx_opt = past + nxt + list(range(ref_indx + dat_indx_step, last + 1, dat_indx_step))
+
+    ref_cam_extM = traj_extMs[ref_indx]
+    src_cam_poses = [torch.from_numpy(_homo.get_rel_extrinsicM(ref_cam_extM, traj_extMs[i]).astype(np.float32))
+                     for i in src_frame_idx]
+
+    if traj_extMs_dso is not None:
+        dRt = torch.FloatTensor(_homo.get_rel_extrinsicM(traj_extMs_dso[ref_indx].copy(), traj_extMs_dso[last].copy()))
+        if use_dso_R:
+            src_cam_poses[-1][:3, :3] = dRt[:3, :3]
+        if use_dso_t:
+            src_cam_poses[-1][:3, 3] = dRt[:3, 3]
+
+    if use_gt_R or use_gt_t:
+        for idx, srcidx in enumerate(src_frame_idx_opt):
+            pose_gt = torch.from_numpy(_homo.get_rel_extrinsicM(dataset[ref_indx]['extM'], dataset[srcidx]['extM']))
+            R_gt, t_gt = pose_gt[:3, :3], pose_gt[:3, 3]
+            if use_gt_R:
+                if add_noise_gt:
+                    R_gt += torch.randn(R_gt.shape).type_as(R_gt) * noise_sigmas[0]
+                src_cam_poses[idx][:3, :3] = R_gt
+            if use_gt_t:
+                if add_noise_gt:
+                    t_gt += torch.randn(t_gt.shape).type_as(t_gt) * noise_sigmas[1]
+                src_cam_poses[idx][:3, 3] = t_gt
+    return src_cam_poses, src_frame_idx_opt

@@ -214,6 +214,41 @@ def dpv_resample(dpv, T, rays, d_candi, tan_hh, tan_hv, z_half, z_radius, pad_va
     return out
 
 
+def dpv_keyframe_maps(dpv, T, rays, d_candi_out, d_candi_src, tan_hh, tan_hv, z_half, z_radius, pad_value,
+                      clamp=(-1000.0, 0.0), want_ref=True, out=None):
+    """dpv [D,h,w] log-DPV, T [4,4] (device) -> (dmap_ref, conf_ref, dmap_kf, conf_kf), each [h,w], in one launch
+    (nrgbd_dpv_keyframe_maps): the keyframe pair is the expected depth and exp(max)^2 of the volume dpv_resample(...,
+    new_candi=True) would return for d_candi_out, which is never written; the reference pair the same of dpv itself with
+    d_candi_src [D].  want_ref=False: the reference pair is not computed (returned as None, or left untouched in `out`).
+    `out`: the four maps of an earlier call to write into (a captured graph's static buffers)."""
+    dpv = _need(dpv, "dpv")
+    if dpv.dim() != 3:
+        raise ValueError("dpv %s, expected [D,h,w]" % (tuple(dpv.shape),))
+    D, h, w = dpv.shape
+    T = _need(T, "T").reshape(16)
+    rays = _need(rays, "rays", (3, h * w))
+    d_candi_out = _need(d_candi_out, "d_candi_out")
+    if d_candi_out.dim() != 1:
+        raise ValueError("d_candi_out must be 1-D")
+    d_candi_src = _need(d_candi_src, "d_candi_src", (D,)) if want_ref else None
+    if out is None:
+        new = lambda: torch.empty((h, w), dtype=torch.float32, device=dpv.device)
+        out = (new() if want_ref else None, new() if want_ref else None, new(), new())
+    dmap_ref, conf_ref, dmap_kf, conf_kf = out
+    for name, t in (("dmap_kf", dmap_kf), ("conf_kf", conf_kf)) + ((("dmap_ref", dmap_ref), ("conf_ref", conf_ref)) if want_ref else ()):
+        if _need(t, name, (h, w)) is not t:
+            raise ValueError("%s must be contiguous" % name)
+    lo, hi = clamp if clamp is not None else (0.0, 0.0)
+    with torch.cuda.device(dpv.device):
+        rc = _lib.load().nrgbd_dpv_keyframe_maps(_p(dpv), _p(T), _p(rays), _p(d_candi_out), _p(d_candi_src), float(tan_hh),
+                                                 float(tan_hv), float(z_half), float(z_radius), float(pad_value),
+                                                 int(clamp is not None), float(lo), float(hi), _p(dmap_kf), _p(conf_kf),
+                                                 _p(dmap_ref if want_ref else None), _p(conf_ref if want_ref else None),
+                                                 D, d_candi_out.shape[0], h, w, _stream(dpv))
+    _lib.check(rc, "nrgbd_dpv_keyframe_maps")
+    return dmap_ref, conf_ref, dmap_kf, conf_kf
+
+
 def logsoftmax_d(a, b=None, scale=1.0):
     """log_softmax over dim 0 of scale*a (+ b); a, b [D, ...]."""
     a = _need(a, "a")
