@@ -85,6 +85,20 @@ def costvol(feat_ref, feat_src, KR, Kt, rays, d_candi, cx, cy, sigma, dist="L2",
     return out
 
 
+def sweep_positions(KR, Kt, rays, d_candi, cx, cy, h, w, align_corners=False):
+    """Sample positions of the plane sweep in texels, before floor: (ix, iy), each [V,D,h,w] fp32 — the ones costvol and
+    warp_volume take their taps at (the same sweep_coords)."""
+    kr, pkr = _f(np.asarray(KR, np.float32).reshape(-1, 9)); kt, pkt = _f(Kt); ry, pry = _f(rays); dc, pdc = _f(d_candi)
+    V, D = kr.shape[0], dc.shape[0]
+    ix = np.empty((V, D, h, w), np.float32)
+    iy = np.empty((V, D, h, w), np.float32)
+    rc = lib().oracle_sweep_positions(pkr, pkt, pry, pdc, ctypes.c_float(cx), ctypes.c_float(cy), int(bool(align_corners)),
+                                      V, D, h, w, ix.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                      iy.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
+    assert rc == 0
+    return ix, iy
+
+
 def warp_volume(src, KR, Kt, rays, d_candi, cx, cy, align_corners=False):
     """src [V,Cs,h,w] -> [V,Cs,D,h,w] (warp_img_feats_v3)."""
     V, Cs, h, w = src.shape

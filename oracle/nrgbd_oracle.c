@@ -178,6 +178,24 @@ int oracle_costvol(const float* feat_ref, const float* feat_src, const float* KR
 }
 
 /*
+ * The sample positions (in texels, before floor) that oracle_costvol and oracle_warp_volume feed to the bilinear taps:
+ * ix, iy [V][D][h][w].  For comparators that continue from the positions in higher precision (tests/costvol_bwd_exact.py).
+ */
+int oracle_sweep_positions(const float* KR, const float* Kt, const float* rays, const float* d_candi, float cx,
+                           float cy, int align_corners, int V, int D, int h, int w, float* ix, float* iy) {
+    const size_t hw = (size_t)h * w;
+#pragma omp parallel for collapse(2) schedule(static)
+    for (int v = 0; v < V; ++v)
+        for (int k = 0; k < D; ++k)
+            for (size_t p = 0; p < hw; ++p) {
+                const size_t o = ((size_t)v * D + k) * hw + p;
+                sweep_coords(KR + 9 * v, Kt + 3 * v, rays[p], rays[hw + p], rays[2 * hw + p], d_candi[k], cx, cy,
+                             w, h, align_corners, ix + o, iy + o);
+            }
+    return 0;
+}
+
+/*
  * K-Net input warp with the samples kept.  warping/homography.py:234-280
  * (warp_img_feats_v3; result transposed to [C][D][h][w], :261).
  * src [V][Cs][h][w] -> out [V][Cs][D][h][w].
