@@ -50,8 +50,10 @@ extern "C" {
  * rgb4, nrgbd_conv2d_taps_f32 takes in_stride; nrgbd_avgpool_cl, nrgbd_scatter_channels and nrgbd_conv2d_few_f32 are new.
  * 0.6: the local bundle adjustment entries nrgbd_lba_pyramid, nrgbd_lba_workgroups, nrgbd_lba_grad and nrgbd_lba_update are new;
  * no existing entry changed.  0.7: nrgbd_bn_small_stats (the SPP branches' BatchNorm statistics) is new; no existing entry changed.
- * 0.8: nrgbd_dpv_keyframe_maps (the LBA driver's depth / confidence maps in one launch) is new; no existing entry changed. */
-#define NRGBD_INTERFACE_VERSION "0.8"
+ * 0.8: nrgbd_dpv_keyframe_maps (the LBA driver's depth / confidence maps in one launch) is new; no existing entry changed.
+ * 0.9: nrgbd_costvol_bwd_det and nrgbd_costvol_bwd_det_workspace (the bit-reproducible cost-volume backward) are new; no existing
+ * entry changed. */
+#define NRGBD_INTERFACE_VERSION "0.9"
 const char* nrgbd_version(void);
 const char* nrgbd_strerror(int code);
 
@@ -161,6 +163,25 @@ int nrgbd_costvol_bwd(const float* ref_nhwc, const float* src_nhwc,
                       float* g_ref, float* g_src,
                       int V, int C, int Cp, int D, int h, int w,
                       void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * nrgbd_costvol_bwd_det — nrgbd_costvol_bwd with bit-reproducible results (opt-in; csrc/costvol_bwd_det.hip).  Same arguments and
+ * return codes.  g_ref is summed per pixel in (view, candidate) order; g_src is summed in fixed point (integer atomics: the sum
+ * does not depend on the order of arrival) and rounded once to fp32.  For the same inputs both outputs are the same bits on every
+ * run, on any stream, whatever the buffers held before, and on any device (no launch parameter comes from the CU count).  One
+ * path for every grid; every output element is written, the lanes C .. Cp-1 are exactly 0.  Every element is within the rounding
+ * bound that holds for nrgbd_costvol_bwd (any summation order).  A g_src element that receives a non-finite term is NaN.
+ *   workspace   always required: nrgbd_costvol_bwd_det_workspace() bytes (12 per element of g_src), 16-byte aligned; cleared by the
+ *               call itself.  NRGBD_E_SHAPE also for h * w * D > 2^29 (the fixed-point sums need the headroom).
+ */
+int nrgbd_costvol_bwd_det_workspace(int V, int Cp, int D, int h, int w, size_t* bytes);
+int nrgbd_costvol_bwd_det(const float* ref_nhwc, const float* src_nhwc,
+                          const float* KR, const float* Kt, const float* rays,
+                          const float* d_candi, float cx, float cy, float sigma,
+                          int dist, int align_corners, const float* g_cost,
+                          float* g_ref, float* g_src,
+                          int V, int C, int Cp, int D, int h, int w,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * nrgbd_bn_cl_fwd / nrgbd_bn_cl_bwd — train-mode BatchNorm (batch statistics, biased variance) with its ReLU and residual add,

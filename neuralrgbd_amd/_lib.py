@@ -31,6 +31,9 @@ SIGNATURES = {
     "nrgbd_costvol_bwd_workspace": (_I, [_I, _I, _I, _I, _I, _P]),
     "nrgbd_costvol_bwd": (_I, [_P, _P, _P, _P, _P, _P, _F, _F, _F, _I, _I, _P, _P, _P,
                                _I, _I, _I, _I, _I, _I, _P, _Z, _P]),
+    "nrgbd_costvol_bwd_det_workspace": (_I, [_I, _I, _I, _I, _I, _P]),
+    "nrgbd_costvol_bwd_det": (_I, [_P, _P, _P, _P, _P, _P, _F, _F, _F, _I, _I, _P, _P, _P,
+                                   _I, _I, _I, _I, _I, _I, _P, _Z, _P]),
     "nrgbd_bn_cl_workgroups": (_I, [_L, _I]),
     "nrgbd_bn_cl_fwd": (_I, [_P, _P, _P, _P, _F, _F, _P, _P, _I, _P, _P, _P, _L, _I, _P]),
     "nrgbd_bn_cl_bwd": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _L, _I, _P]),

@@ -11,6 +11,41 @@ import torch
 from . import _lib, ops
 
 
+# Bit-reproducible training (opt-in).  The one order-dependent reduction of the training path is the scatter of the cost-volume
+# backward (csrc/costvol_bwd.hip: float atomics); with the switch on, PlaneSweepCost takes csrc/costvol_bwd_det.hip instead.  A
+# process-wide flag of this module, nothing else: neither torch's deterministic-algorithms setting nor the environment is consulted.
+_DETERMINISTIC = False
+
+
+def set_deterministic(flag):
+    """Switch the bit-reproducible cost-volume backward on or off for the forwards that follow.  Returns the previous value."""
+    global _DETERMINISTIC
+    prev, _DETERMINISTIC = _DETERMINISTIC, bool(flag)
+    return prev
+
+
+def is_deterministic():
+    return _DETERMINISTIC
+
+
+class deterministic:
+    """Context manager: the switch set to `flag` inside, the previous value restored on exit (also after an exception).
+    flag = None leaves the switch alone (train(..., deterministic=None): follow the switch)."""
+
+    def __init__(self, flag=True):
+        self.flag = flag
+
+    def __enter__(self):
+        self.prev = _DETERMINISTIC
+        if self.flag is not None:
+            set_deterministic(self.flag)
+        return self
+
+    def __exit__(self, *exc):
+        set_deterministic(self.prev)
+        return False
+
+
 class PackNHWC(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat, rgb):
@@ -32,6 +67,7 @@ class PlaneSweepCost(torch.autograd.Function):
                               align_corners=align_corners, want_cost=True, want_logp=False)
         ctx.save_for_backward(texels, KR, Kt, rays, d_candi)
         ctx.meta = (cx, cy, sigma, C, dist, align_corners)
+        ctx.deterministic = _DETERMINISTIC     # the backward follows the forward it belongs to, wherever and whenever it runs
         return cost
 
     @staticmethod
@@ -40,7 +76,7 @@ class PlaneSweepCost(torch.autograd.Function):
         cx, cy, sigma, C, dist, align = ctx.meta
         V = texels.shape[0] - 1
         g_ref, g_src = ops.costvol_bwd(texels[V], texels[:V], KR, Kt, rays, d_candi, cx, cy, sigma, C,
-                                       g_cost.contiguous(), dist=dist, align_corners=align)
+                                       g_cost.contiguous(), dist=dist, align_corners=align, deterministic=ctx.deterministic)
         return (torch.cat((g_src, g_ref.unsqueeze(0)), dim=0),) + (None,) * 10
 
 

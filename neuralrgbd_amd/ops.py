@@ -133,8 +133,11 @@ def costvol(ref_nhwc, src_nhwc, KR, Kt, rays, d_candi, cx, cy, sigma, C, dist="L
     return cost, logp
 
 
-def costvol_bwd(ref_nhwc, src_nhwc, KR, Kt, rays, d_candi, cx, cy, sigma, C, g_cost, dist="L2", align_corners=False):
-    """Gradient of the cost volume w.r.t. the packed features: (g_ref [h,w,Cp], g_src [V,h,w,Cp])."""
+def costvol_bwd(ref_nhwc, src_nhwc, KR, Kt, rays, d_candi, cx, cy, sigma, C, g_cost, dist="L2", align_corners=False,
+                deterministic=False):
+    """Gradient of the cost volume w.r.t. the packed features: (g_ref [h,w,Cp], g_src [V,h,w,Cp]).
+    deterministic: csrc/costvol_bwd_det.hip (fixed-point scatter: the same bits on every run) instead of the atomic kernels of
+    csrc/costvol_bwd.hip; both are within the same rounding bound of the exact gradient."""
     src_nhwc = _need(src_nhwc, "src_nhwc")
     V, h, w, Cp = src_nhwc.shape
     ref_nhwc = _need(ref_nhwc, "ref_nhwc", (h, w, Cp))
@@ -142,16 +145,17 @@ def costvol_bwd(ref_nhwc, src_nhwc, KR, Kt, rays, d_candi, cx, cy, sigma, C, g_c
     D = d_candi.numel()
     g_cost = _need(g_cost, "g_cost", (D, h, w))
     g_ref, g_src = torch.empty_like(ref_nhwc), torch.empty_like(src_nhwc)
+    name = "nrgbd_costvol_bwd_det" if deterministic else "nrgbd_costvol_bwd"
     with torch.cuda.device(src_nhwc.device):
         nbytes = ctypes.c_size_t(0)
-        _lib.check(_lib.load().nrgbd_costvol_bwd_workspace(V, Cp, D, h, w, ctypes.byref(nbytes)), "nrgbd_costvol_bwd_workspace")
+        _lib.check(getattr(_lib.load(), name + "_workspace")(V, Cp, D, h, w, ctypes.byref(nbytes)), name + "_workspace")
         work = torch.empty(nbytes.value, dtype=torch.uint8, device=src_nhwc.device) if nbytes.value else None
-        rc = _lib.load().nrgbd_costvol_bwd(_p(ref_nhwc), _p(src_nhwc), _p(_need(KR, "KR").reshape(V, 9)), _p(_need(Kt, "Kt", (V, 3))),
-                                           _p(_need(rays, "rays", (3, h * w))), _p(d_candi), float(cx), float(cy), float(sigma),
-                                           DIST[dist], int(bool(align_corners)), _p(g_cost), _p(g_ref), _p(g_src),
-                                           V, int(C), Cp, D, h, w, _p(work) if work is not None else None, nbytes.value,
-                                           _stream(src_nhwc))
-    _lib.check(rc, "nrgbd_costvol_bwd")
+        rc = getattr(_lib.load(), name)(_p(ref_nhwc), _p(src_nhwc), _p(_need(KR, "KR").reshape(V, 9)), _p(_need(Kt, "Kt", (V, 3))),
+                                        _p(_need(rays, "rays", (3, h * w))), _p(d_candi), float(cx), float(cy), float(sigma),
+                                        DIST[dist], int(bool(align_corners)), _p(g_cost), _p(g_ref), _p(g_src),
+                                        V, int(C), Cp, D, h, w, _p(work) if work is not None else None, nbytes.value,
+                                        _stream(src_nhwc))
+    _lib.check(rc, name)
     return g_ref, g_src
 
 

@@ -16,7 +16,7 @@ import torch.nn.functional as F
 
 from . import homography as warp_homo
 from . import ops
-from .autograd import nll_loss_d, pack_cache
+from .autograd import deterministic as _deterministic, nll_loss_d, pack_cache
 from .misc import depth_val_regression, valid_dpv
 
 
@@ -74,7 +74,7 @@ def _train_windows(A, dev, model_KV, t_win_r, d_candi, Ref_Dats, Src_Dats, poses
 
 def train(nGPU, model_KV, optimizer_KV, t_win_r, d_candi, Ref_Dats, Src_Dats, Src_CamPoses, BVs_predict,
           Cam_Intrinsics, refine_dup=False, weight_var=.001, loss_type='NLL', mGPU=False,
-          Cam_Intrinsics_spatial_up=None, return_confmap_up=False, grad_reducer=None, accum_steps=1):
+          Cam_Intrinsics_spatial_up=None, return_confmap_up=False, grad_reducer=None, accum_steps=1, deterministic=None):
     """Returns (r_dpv, BVs_predict_out, loss, dmap_kv_lowres, dmap_kv_highres) — the two depth maps are device
     tensors (the reference stacks them with the ground truth into numpy arrays for TensorBoard).
 
@@ -82,7 +82,10 @@ def train(nGPU, model_KV, optimizer_KV, t_win_r, d_candi, Ref_Dats, Src_Dats, Sr
     reference's batch dimension does — Ref_Dats / Src_Dats lists of length A, Src_CamPoses [A,V,4,4], BVs_predict None, a
     tensor [A,D,h,w] or a list of A (tensor | None) — and runs them as A SEQUENTIAL N = 1 windows (KVNET asserts N = 1 per
     forward), each with its own BV_predict: A forward/backward passes accumulate into the same gradient, ONE all-reduce,
-    division by A x world, ONE optimizer step.  Outputs are concatenated along the batch dimension; `loss` is the mean."""
+    division by A x world, ONE optimizer step.  Outputs are concatenated along the batch dimension; `loss` is the mean.
+
+    deterministic: None follows neuralrgbd_amd.autograd.is_deterministic(); True / False set that switch around this call's forward
+    and backward (True: the bit-reproducible cost-volume backward — two identical runs give identical weights)."""
     if loss_type != 'NLL' or refine_dup:
         raise NotImplementedError("only the NLL loss without depth up-sampling is on this path")
     A = int(accum_steps)
@@ -99,7 +102,7 @@ def train(nGPU, model_KV, optimizer_KV, t_win_r, d_candi, Ref_Dats, Src_Dats, Sr
     else:
         optimizer_KV.zero_grad()
 
-    with pack_cache():                # the A windows run on the same weights: their packed streams are built by the first one
+    with pack_cache(), _deterministic(deterministic):   # the A windows run on the same weights: their packed streams are built by the first one
         outs = _train_windows(A, dev, model_KV, t_win_r, d_candi, Ref_Dats, Src_Dats, poses_all, BVs_predict, Cam_Intrinsics)
 
     if grad_reducer is not None:
@@ -140,7 +143,11 @@ class TrainGraph:
     (checked; a RuntimeError names the parameter otherwise).
     """
 
-    def __init__(self, model, optimizer, t_win_r, d_candi, cam_intrinsics, warmup=1, grad_reducer=None, accum_steps=1):
+    def __init__(self, model, optimizer, t_win_r, d_candi, cam_intrinsics, warmup=1, grad_reducer=None, accum_steps=1,
+                 deterministic=None):
+        """deterministic: None follows neuralrgbd_amd.autograd.is_deterministic() at each eager iteration and at capture (a graph
+        keeps the kernels it was captured with); True / False set the switch around this object's forward and backward."""
+        self.deterministic = deterministic
         self.model, self.opt, self.t_win_r, self.d_candi, self.cam = model, optimizer, t_win_r, d_candi, cam_intrinsics
         self._graph = None
         self._st = None
@@ -168,6 +175,10 @@ class TrainGraph:
 
     def _fwd_bwd(self, st):
         """forward + 4 NLL terms + backward + PREDICT of one window (no optimizer step)."""
+        with _deterministic(self.deterministic):
+            return self._fwd_bwd_switched(st)
+
+    def _fwd_bwd_switched(self, st):
         model = self.model
         r_cur, r_kv, d_dpv, kv_dpv = model(ref_frame=st["ref"], src_frames=st["src"], src_cam_poses=st["poses"],
                                            BatchIdx=torch.zeros(1), cam_intrinsics=[self.cam], BV_predict=st["bv"],

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Training-step throughput (BASELINE config 4 shape: ScanNet 384x256 image, grid 96x64x64, N = 1 per GPU).
 
-    python tools/bench_train.py [--iters 6]
+    python tools/bench_train.py [--iters 6] [--graph] [--deterministic]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/bench_train.py
 
 One iteration = neuralrgbd_amd.train_step.train(): forward under autograd, 4 NLL terms, backward (fused cost-volume
@@ -22,8 +22,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=6)
     ap.add_argument("--graph", action="store_true", help="replay the captured hipGraph of the iteration (1 GPU)")
+    ap.add_argument("--deterministic", action="store_true", help="bit-reproducible mode (csrc/costvol_bwd_det.hip)")
     args = ap.parse_args()
     import neuralrgbd_amd
+    from neuralrgbd_amd import autograd
+    autograd.set_deterministic(args.deterministic)
     from neuralrgbd_amd import camera, distributed as nd, synth
     from neuralrgbd_amd.train_step import train
     rank, world = nd.init_from_env()
@@ -61,8 +64,8 @@ def main():
     steady = times[5:] if args.graph else times[2:]
     dt = nd.max_over_ranks(float(np.mean(steady)), device=dev)
     if rank == 0:
-        print("train step (grid 96x64x64, N=1/GPU, %d GPU): %.1f ms/iteration, %.2f windows/s aggregate, loss %.3f, "
-              "gradient message %.2f MB" % (world, 1e3 * dt, world / dt, float(loss),
+        print("train step (grid 96x64x64, N=1/GPU, %d GPU, %s): %.1f ms/iteration, %.2f windows/s aggregate, loss %.3f, "
+              "gradient message %.2f MB" % (world, "deterministic" if args.deterministic else "default mode", 1e3 * dt, world / dt, float(loss),
                                             4e-6 * (reducer.numel if reducer else sum(p.numel() for p in set(model.parameters())))))
 
 
