@@ -153,7 +153,8 @@ int nrgbd_costvol_fwd_gen(const float* ref_nhwc, const float* src_nhwc,
  *   workspace         device scratch of at least nrgbd_costvol_bwd_workspace() bytes, 16-byte aligned (per-slice
  *                     partial sums of the LDS scatter kernel); may be NULL when that size is 0 (grids whose
  *                     16*h*w bytes exceed the LDS budget use global atomics instead).
- * NRGBD_E_NULL / NRGBD_E_SHAPE when a needed workspace is missing / too small.
+ * NRGBD_E_NULL / NRGBD_E_SHAPE when a needed workspace is missing / too small.  NRGBD_E_SHAPE also for h * w > INT_MAX / 4
+ * (texels are indexed with int; the same limit as nrgbd_costvol_bwd_det, and from the workspace query too).
  */
 int nrgbd_costvol_bwd_workspace(int V, int Cp, int D, int h, int w, size_t* bytes);
 int nrgbd_costvol_bwd(const float* ref_nhwc, const float* src_nhwc,

@@ -14,97 +14,36 @@
 // 64x96x64, V = 4, C = 67 it spends 4.9 of its 5.2 ms waiting on those atomics, the LDS kernel takes the rest.
 // Sampling positions are recomputed exactly as in the forward kernels (no gradient flows to the poses:
 // they are inputs, as in the reference where they come from the dataset).
-#include "costvol.hpp"
+#include "costvol_bwd.hpp"
 
 namespace nrgbd {
 
-struct CostvolBwdArgs {
-    const float* ref; const float* src; const float* KR; const float* Kt; const float* rays;
-    const float* d_candi; const float* g_cost;
-    float* g_ref; float* g_src;
-    float cx, cy, sigma;
-    int dist, align, V, C, Cp, D, h, w, kchunks;
-    int abl;   // developer builds only (NRGBD_BWD_ABL): 1 = no atomics, 2 = no tap loads, 4 = conflict-free LDS addresses (results invalid)
-};
+// Developer builds only (NRGBD_BWD_ABL): 1 = no atomics, 2 = no tap loads, 4 = conflict-free LDS addresses (results invalid).
+#ifdef NRGBD_DEV
+#define NRGBD_BWD_ABL_BITS(abl) (abl)
+#else
+#define NRGBD_BWD_ABL_BITS(abl) 0
+#endif
 
 // grid (ceil(hw/64), kchunks, Cp/4), block 64: one lane = one pixel x one slice of consecutive depth candidates x
-// one 16-byte channel word.  Consecutive candidates of a pixel sample neighbouring positions along its epipolar
-// line — for the far planes the SAME 2x2 source cell for several candidates in a row — so the four tap gradients
-// are accumulated in registers while the cell stays the same and flushed with atomics only when it changes
-// (4-8x fewer atomics than one per (pixel, candidate, view, channel); the kernel is atomic-bound).
-__global__ __launch_bounds__(64) void costvol_bwd_kernel(const CostvolBwdArgs a) {
-#ifdef NRGBD_DEV
-    const int abl = a.abl;
-#else
-    constexpr int abl = 0;
-#endif
-    const size_t hw = (size_t)a.h * a.w;
-    const size_t p = (size_t)blockIdx.x * 64 + threadIdx.x;
+// one 16-byte channel word, over all views (costvol_bwd_sweep); a flushed tap gradient is one global atomic.
+__global__ __launch_bounds__(64) void costvol_bwd_kernel(const CostvolBwdArgs a, const int kchunks, const int abl_) {
+    const int abl = NRGBD_BWD_ABL_BITS(abl_);
+    const int hw = a.h * a.w;
+    const int p = blockIdx.x * 64 + threadIdx.x;
     if (p >= hw) return;
-    const int per = (a.D + a.kchunks - 1) / a.kchunks;
+    const int per = (a.D + kchunks - 1) / kchunks;
     const int k_begin = blockIdx.y * per, k_end = min(a.D, k_begin + per);
     const int i = blockIdx.z;                      // channel word
     const float rx = a.rays[p], ry = a.rays[hw + p], rz = a.rays[2 * hw + p];
-    const float wf = (float)a.w, hf = (float)a.h;
-    const float4 r = *reinterpret_cast<const float4*>(a.ref + p * a.Cp + 4 * i);
-    const int ncomp = min(4, a.C - 4 * i);         // valid components of this word
+    const float4 r = *reinterpret_cast<const float4*>(a.ref + (size_t)p * a.Cp + 4 * i);
     float gr[4] = {0.f, 0.f, 0.f, 0.f};
-
     for (int v = 0; v < a.V; ++v) {
-        const SweepTerm st = make_sweep_term(a.KR + 9 * v, a.Kt + 3 * v, rx, ry, rz);
-        const float* sv = a.src + (size_t)v * hw * a.Cp + 4 * i;
         float* gs = a.g_src + (size_t)v * hw * a.Cp + 4 * i;
-        // register accumulator of the current cell: 4 taps x 4 components
-        float acc[4][4];
-        float cx0 = -1e30f, cy0 = -1e30f;          // floor of the current cell (never matches initially)
-        size_t o[4] = {0, 0, 0, 0};
-        bool have = false;
-        auto flush = [&]() {
-            if (!have) return;
-#pragma unroll
-            for (int tpi = 0; tpi < 4; ++tpi)
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (acc[tpi][e] != 0.f && !(abl & 1)) atomicAdd(gs + o[tpi] + e, acc[tpi][e]);
-        };
-        for (int k = k_begin; k < k_end; ++k) {
-            const float gk = a.g_cost[(size_t)k * hw + p] / a.sigma;
-            float ix, iy;
-            sweep_sample_pos(st, a.d_candi[k], a.cx, a.cy, wf, hf, a.align != 0, ix, iy);
-            const Bilinear b = bilinear_zeros(ix, iy, a.w, a.h);
-            const float x0f = floorf(ix), y0f = floorf(iy);
-            if (!(x0f == cx0 && y0f == cy0)) {      // new cell (also taken for NaN positions)
-                flush();
-                cx0 = x0f; cy0 = y0f; have = true;
-                o[0] = ((size_t)b.y0 * a.w + b.x0) * a.Cp; o[1] = ((size_t)b.y0 * a.w + b.x1) * a.Cp;
-                o[2] = ((size_t)b.y1 * a.w + b.x0) * a.Cp; o[3] = ((size_t)b.y1 * a.w + b.x1) * a.Cp;
-#pragma unroll
-                for (int tpi = 0; tpi < 4; ++tpi)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[tpi][e] = 0.f;
-            }
-            if (gk == 0.f) continue;
-            float4 A = r, B = r, Cc = r, Dd = r;
-            if (!(abl & 2)) {
-                A = *reinterpret_cast<const float4*>(sv + o[0]); B = *reinterpret_cast<const float4*>(sv + o[1]);
-                Cc = *reinterpret_cast<const float4*>(sv + o[2]); Dd = *reinterpret_cast<const float4*>(sv + o[3]);
-            }
-            const float df[4] = {lerp4(A.x, B.x, Cc.x, Dd.x, b) - r.x, lerp4(A.y, B.y, Cc.y, Dd.y, b) - r.y,
-                                 lerp4(A.z, B.z, Cc.z, Dd.z, b) - r.z, lerp4(A.w, B.w, Cc.w, Dd.w, b) - r.w};
-            const float wt[4] = {b.nw, b.ne, b.sw, b.se};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (e >= ncomp) continue;
-                const float ds = (a.dist == NRGBD_DIST_L2) ? 2.f * df[e] : (df[e] > 0.f ? 1.f : (df[e] < 0.f ? -1.f : 0.f));
-                const float c = ds * gk;
-                gr[e] -= c;
-#pragma unroll
-                for (int tpi = 0; tpi < 4; ++tpi) acc[tpi][e] = __builtin_fmaf(wt[tpi], c, acc[tpi][e]);
-            }
-        }
-        flush();
+        costvol_bwd_sweep(a, abl, p, v, i, k_begin, k_end, rx, ry, rz, r, gr,
+                          [&](int tex, int e, float x) { atomicAdd(gs + (size_t)tex * a.Cp + e, x); });
     }
-    float* go = a.g_ref + p * a.Cp + 4 * i;
+    float* go = a.g_ref + (size_t)p * a.Cp + 4 * i;
 #pragma unroll
     for (int e = 0; e < 4; ++e)
         if (gr[e] != 0.f) atomicAdd(go + e, gr[e]);
@@ -116,85 +55,27 @@ constexpr size_t kBwdLdsMax = 144 * 1024;   // of the 160 KB of a CU
 // grid (kchunks, Cp/4, V), block 1024, LDS 16*h*w bytes: one workgroup = one source view x one 16-byte channel word
 // x one slice of consecutive depth candidates, over ALL pixels.  The gradient of that word of the view lives in LDS
 // as four component planes [4][h*w] (adjacent pixels sample adjacent texels -> adjacent banks); a lane walks the
-// candidates of a pixel, keeps the four tap gradients of the current 2x2 source cell in registers while the cell
-// stays the same (the far planes) and adds them into LDS when it changes.
+// candidates of a pixel (costvol_bwd_sweep), a flushed tap gradient is one LDS atomic.
 //   part_src [kchunks][V][Cp/4][h*w][4]   partial g_src of this slice (every element written)
 //   part_ref [kchunks][V][Cp/4][h*w][4]   partial g_ref of this slice and view
-__global__ __launch_bounds__(kBwdThreads) void costvol_bwd_lds_kernel(const CostvolBwdArgs a, float* __restrict__ part_src,
-                                                                      float* __restrict__ part_ref) {
-#ifdef NRGBD_DEV
-    const int abl = a.abl;
-#else
-    constexpr int abl = 0;
-#endif
+__global__ __launch_bounds__(kBwdThreads) void costvol_bwd_lds_kernel(const CostvolBwdArgs a, const int kchunks, const int abl_,
+                                                                      float* __restrict__ part_src, float* __restrict__ part_ref) {
+    const int abl = NRGBD_BWD_ABL_BITS(abl_);
     extern __shared__ float gl[];
     const int hw = a.h * a.w, words = a.Cp >> 2;
     const int kc = blockIdx.x, i = blockIdx.y, v = blockIdx.z, tid = threadIdx.x;
     for (int t = tid; t < 4 * hw; t += kBwdThreads) gl[t] = 0.f;
     __syncthreads();
-    const int per = (a.D + a.kchunks - 1) / a.kchunks;
+    const int per = (a.D + kchunks - 1) / kchunks;
     const int k_begin = kc * per, k_end = min(a.D, k_begin + per);
-    const int ncomp = min(4, a.C - 4 * i);
-    const float wf = (float)a.w, hf = (float)a.h;
-    const float* sv = a.src + (size_t)v * hw * a.Cp + 4 * i;
     const size_t slab = (((size_t)kc * a.V + v) * words + i) * hw;
-    const float inv_sigma_den = a.sigma;
 
     for (int p = tid; p < hw; p += kBwdThreads) {
         const float rx = a.rays[p], ry = a.rays[hw + p], rz = a.rays[2 * hw + p];
         const float4 r = *reinterpret_cast<const float4*>(a.ref + (size_t)p * a.Cp + 4 * i);
-        const SweepTerm st = make_sweep_term(a.KR + 9 * v, a.Kt + 3 * v, rx, ry, rz);
         float gr[4] = {0.f, 0.f, 0.f, 0.f};
-        float acc[4][4];
-        float cx0 = -1e30f, cy0 = -1e30f;
-        int o[4] = {0, 0, 0, 0};
-        bool have = false;
-        auto flush = [&]() {
-            if (!have) return;
-#pragma unroll
-            for (int tpi = 0; tpi < 4; ++tpi)
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (acc[tpi][e] != 0.f && !(abl & 1)) atomicAdd(gl + e * hw + ((abl & 4) ? min(p + tpi, hw - 1) : o[tpi]), acc[tpi][e]);
-        };
-        for (int k = k_begin; k < k_end; ++k) {
-            const float gk = a.g_cost[(size_t)k * hw + p] / inv_sigma_den;
-            float ix, iy;
-            sweep_sample_pos(st, a.d_candi[k], a.cx, a.cy, wf, hf, a.align != 0, ix, iy);
-            const Bilinear b = bilinear_zeros(ix, iy, a.w, a.h);
-            const float x0f = floorf(ix), y0f = floorf(iy);
-            if (!(x0f == cx0 && y0f == cy0)) {      // new cell (also taken for NaN positions)
-                flush();
-                cx0 = x0f; cy0 = y0f; have = true;
-                o[0] = b.y0 * a.w + b.x0; o[1] = b.y0 * a.w + b.x1;
-                o[2] = b.y1 * a.w + b.x0; o[3] = b.y1 * a.w + b.x1;
-#pragma unroll
-                for (int tpi = 0; tpi < 4; ++tpi)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[tpi][e] = 0.f;
-            }
-            if (gk == 0.f) continue;
-            float4 A = r, B = r, Cc = r, Dd = r;
-            if (!(abl & 2)) {
-                A = *reinterpret_cast<const float4*>(sv + (size_t)o[0] * a.Cp);
-                B = *reinterpret_cast<const float4*>(sv + (size_t)o[1] * a.Cp);
-                Cc = *reinterpret_cast<const float4*>(sv + (size_t)o[2] * a.Cp);
-                Dd = *reinterpret_cast<const float4*>(sv + (size_t)o[3] * a.Cp);
-            }
-            const float df[4] = {lerp4(A.x, B.x, Cc.x, Dd.x, b) - r.x, lerp4(A.y, B.y, Cc.y, Dd.y, b) - r.y,
-                                 lerp4(A.z, B.z, Cc.z, Dd.z, b) - r.z, lerp4(A.w, B.w, Cc.w, Dd.w, b) - r.w};
-            const float wt[4] = {b.nw, b.ne, b.sw, b.se};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (e >= ncomp) continue;
-                const float ds = (a.dist == NRGBD_DIST_L2) ? 2.f * df[e] : (df[e] > 0.f ? 1.f : (df[e] < 0.f ? -1.f : 0.f));
-                const float c = ds * gk;
-                gr[e] -= c;
-#pragma unroll
-                for (int tpi = 0; tpi < 4; ++tpi) acc[tpi][e] = __builtin_fmaf(wt[tpi], c, acc[tpi][e]);
-            }
-        }
-        flush();
+        costvol_bwd_sweep(a, abl, p, v, i, k_begin, k_end, rx, ry, rz, r, gr,
+                          [&](int tex, int e, float x) { atomicAdd(gl + e * hw + ((abl & 4) ? p : tex), x); });
         *reinterpret_cast<float4*>(part_ref + (slab + p) * 4) = make_float4(gr[0], gr[1], gr[2], gr[3]);
     }
     __syncthreads();
@@ -250,7 +131,7 @@ static int bwd_lds_kchunks(int V, int Cp, int D, int h, int w, int* out) {
 extern "C" int nrgbd_costvol_bwd_workspace(int V, int Cp, int D, int h, int w, size_t* bytes) {
     using namespace nrgbd;
     if (!bytes) return NRGBD_E_NULL;
-    if (V <= 0 || V > NRGBD_MAX_V || Cp <= 0 || (Cp & 3) || D <= 0 || D > NRGBD_MAX_D || h <= 0 || w <= 0) return NRGBD_E_SHAPE;
+    if (costvol_bwd_check_shape(V, Cp, Cp, D, h, w, NRGBD_DIST_L2) != NRGBD_OK) return NRGBD_E_SHAPE;
     int kc = 0;
     const int rc = bwd_lds_kchunks(V, Cp, D, h, w, &kc);
     if (rc != NRGBD_OK) return rc;
@@ -264,14 +145,15 @@ extern "C" int nrgbd_costvol_bwd(const float* ref_nhwc, const float* src_nhwc, c
                                  int V, int C, int Cp, int D, int h, int w, void* workspace, size_t workspace_bytes,
                                  void* stream) {
     using namespace nrgbd;
-    if (!ref_nhwc || !src_nhwc || !KR || !Kt || !rays || !d_candi || !g_cost || !g_ref || !g_src) return NRGBD_E_NULL;
-    if (V <= 0 || V > NRGBD_MAX_V || C <= 0 || D <= 0 || D > NRGBD_MAX_D || h <= 0 || w <= 0) return NRGBD_E_SHAPE;
-    if ((Cp & 3) || Cp < C || Cp - C > 3) return NRGBD_E_ALIGN;
-    if (dist != NRGBD_DIST_L2 && dist != NRGBD_DIST_L1) return NRGBD_E_ARG;
+    const CostvolBwdArgs a{ref_nhwc, src_nhwc, KR, Kt, rays, d_candi, g_cost, g_ref, g_src, cx, cy, sigma,
+                           dist, align_corners, V, C, Cp, D, h, w};
+    int rc = costvol_bwd_check(a);
+    if (rc != NRGBD_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const size_t hw = (size_t)h * w;
+    const int abl = dev_env_int("NRGBD_BWD_ABL");
     int lds_kc = 0;
-    const int rc = bwd_lds_kchunks(V, Cp, D, h, w, &lds_kc);
+    rc = bwd_lds_kchunks(V, Cp, D, h, w, &lds_kc);
     if (rc != NRGBD_OK) return rc;
     if (lds_kc > 0) {
         const size_t half = (size_t)lds_kc * V * (Cp >> 2) * hw * 4;   // floats per partial array
@@ -280,14 +162,12 @@ extern "C" int nrgbd_costvol_bwd(const float* ref_nhwc, const float* src_nhwc, c
         if ((uintptr_t)workspace & 15) return NRGBD_E_ALIGN;
         float* part_src = static_cast<float*>(workspace);
         float* part_ref = part_src + half;
-        CostvolBwdArgs a{ref_nhwc, src_nhwc, KR, Kt, rays, d_candi, g_cost, g_ref, g_src, cx, cy, sigma,
-                         dist, align_corners, V, C, Cp, D, h, w, lds_kc, dev_env_int("NRGBD_BWD_ABL")};
         const size_t lds = hw * 16;
         hipError_t e = hipSuccess;
         if (lds > 64 * 1024)   // the function's opt-in: always the maximum, never this call's size (a hipGraph replay runs under the current value)
             e = set_max_dynamic_lds(reinterpret_cast<const void*>(&costvol_bwd_lds_kernel), 160 * 1024);
         if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(costvol_bwd_lds_kernel, dim3(lds_kc, Cp >> 2, V), dim3(kBwdThreads), lds, s, a, part_src, part_ref);
+        hipLaunchKernelGGL(costvol_bwd_lds_kernel, dim3(lds_kc, Cp >> 2, V), dim3(kBwdThreads), lds, s, a, lds_kc, abl, part_src, part_ref);
         NRGBD_CHECK_LAUNCH();
         const size_t total = (size_t)(V + 1) * hw * (Cp >> 2);
         hipLaunchKernelGGL(costvol_bwd_reduce_kernel, dim3((unsigned)ceil_div((long)total, 256)), dim3(256), 0, s,
@@ -302,9 +182,7 @@ extern "C" int nrgbd_costvol_bwd(const float* ref_nhwc, const float* src_nhwc, c
     // slices of consecutive candidates: long enough for the register run-accumulation, parallelism comes from
     // the channel-word axis of the grid
     const int kchunks = D >= 32 ? 4 : (D >= 8 ? 2 : 1);
-    CostvolBwdArgs a{ref_nhwc, src_nhwc, KR, Kt, rays, d_candi, g_cost, g_ref, g_src, cx, cy, sigma,
-                     dist, align_corners, V, C, Cp, D, h, w, kchunks, dev_env_int("NRGBD_BWD_ABL")};
-    hipLaunchKernelGGL(costvol_bwd_kernel, dim3(ceil_div((long)hw, 64), kchunks, Cp >> 2), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(costvol_bwd_kernel, dim3(ceil_div((long)hw, 64), kchunks, Cp >> 2), dim3(64), 0, s, a, kchunks, abl);
     NRGBD_CHECK_LAUNCH();
     return NRGBD_OK;
 }

@@ -31,7 +31,8 @@
 // tests/costvol_bwd_exact.py bounds an element by gamma(C0 + n) A + ..., A = sum |t_i| >= M, gamma(m) ~ m 2^-24, where n - 1 of the
 // roundings in gamma are the additions of an fp32 summation in any order.  This path replaces those n - 1 roundings (up to
 // (n - 1) 2^-24 A) by n 2^-(S+1) M + 2^-24 |sum| <= (n 2^-33 + 2^-24) A: inside the same 1 x bound with room to spare, for any n.
-// (The terms themselves — weights, lerp4, difference, ds * g, the run fma — are formed exactly as in costvol_bwd.hip: the C0 part.)
+// (The terms themselves — weights, lerp4, difference, ds * g, the run fma — come from costvol_bwd_sweep of costvol_bwd.hpp, the one
+// function that costvol_bwd.hip's kernels call too: the C0 part.)
 //
 // Special values.  An element all of whose terms are zero (or that receives none) is exactly +0.  An element that receives a
 // non-finite term (Inf or NaN: non-finite features or g_cost) is NaN — also where the atomic kernels would give an infinity.
@@ -46,18 +47,13 @@
 //
 // Layout of the planes: [V][Cp][h w] (component planes, like the LDS kernel's), so the 64 lanes of a wave — 64 neighbouring pixels,
 // which sample neighbouring texels — issue each atomic on one or two contiguous runs instead of 64 addresses 4 Cp bytes apart.
-#include "costvol.hpp"
+#include "costvol_bwd.hpp"
 
 namespace nrgbd {
 
-struct CostvolBwdDetArgs {
-    const float* ref; const float* src; const float* KR; const float* Kt; const float* rays;
-    const float* d_candi; const float* g_cost;
-    float* g_ref; float* g_src;
+struct CostvolBwdDetArgs : CostvolBwdArgs {
     unsigned long long* sum;   // [V][Cp][hw] two's-complement int64 sums of the scaled terms
     unsigned int* mx;          // [V][Cp][hw] largest |term| as fp32 bits
-    float cx, cy, sigma;
-    int dist, align, V, C, Cp, D, h, w;
     int S;                     // scaled exponent of an element's largest term
 };
 
@@ -74,7 +70,8 @@ __device__ __forceinline__ double det_pow2(int n) {
     return __longlong_as_double((long long)(1023 + n) << 52);
 }
 
-// PASS 0: maxima of |term|.  PASS 1: scaled integer sums + g_ref.
+// PASS 0: maxima of |term|.  PASS 1: scaled integer sums + g_ref.  One lane = one pixel x one 16-byte channel word, all views, all
+// candidates (costvol_bwd_sweep); pass 0 never reads gr, so its sum is dead code there.
 template <int PASS>
 __global__ __launch_bounds__(kDetThreads) void costvol_bwd_det_sweep(const CostvolBwdDetArgs a) {
     const int hw = a.h * a.w;
@@ -82,78 +79,25 @@ __global__ __launch_bounds__(kDetThreads) void costvol_bwd_det_sweep(const Costv
     if (p >= hw) return;
     const int i = blockIdx.y;                      // channel word
     const float rx = a.rays[p], ry = a.rays[hw + p], rz = a.rays[2 * hw + p];
-    const float wf = (float)a.w, hf = (float)a.h;
     const float4 r = *reinterpret_cast<const float4*>(a.ref + (size_t)p * a.Cp + 4 * i);
-    const int ncomp = min(4, a.C - 4 * i);         // valid components of this word
     float gr[4] = {0.f, 0.f, 0.f, 0.f};
-
     for (int v = 0; v < a.V; ++v) {
-        const SweepTerm st = make_sweep_term(a.KR + 9 * v, a.Kt + 3 * v, rx, ry, rz);
-        const float* sv = a.src + (size_t)v * hw * a.Cp + 4 * i;
         const size_t plane = ((size_t)v * a.Cp + 4 * i) * hw;        // component e of this word: plane + e * hw + texel
-        // register accumulator of the current cell: 4 taps x 4 components
-        float acc[4][4];
-        float cx0 = -1e30f, cy0 = -1e30f;          // floor of the current cell (never matches initially)
-        int o[4] = {0, 0, 0, 0};
-        bool have = false;
-        auto flush = [&]() {
-            if (!have) return;
-#pragma unroll
-            for (int tpi = 0; tpi < 4; ++tpi)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float t = acc[tpi][e];
-                    if (t == 0.f) continue;        // an invalid tap (weight 0), a dead channel, a padding lane
-                    const size_t at = plane + (size_t)e * hw + o[tpi];
-                    if (PASS == 0) {
-                        const unsigned int bits = __float_as_uint(t) & 0x7fffffffu;
-                        // the plane only grows during this kernel: a value read here, however stale, is a lower bound of the final
-                        // maximum, so skipping the atomic when it already covers `bits` cannot change the result
-                        if (bits > __hip_atomic_load(a.mx + at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-                            atomicMax(a.mx + at, bits);
-                    } else {
-                        const unsigned int m = a.mx[at];
-                        if (m >= 0x7f800000u) continue;           // a non-finite term landed here: pass 3 writes NaN
-                        const long long q = __double2ll_rn((double)t * det_pow2(a.S + 127 - det_exp_field(m)));
-                        if (q != 0) atomicAdd(a.sum + at, (unsigned long long)q);
-                    }
-                }
-        };
-        for (int k = 0; k < a.D; ++k) {
-            const float gk = a.g_cost[(size_t)k * hw + p] / a.sigma;
-            float ix, iy;
-            sweep_sample_pos(st, a.d_candi[k], a.cx, a.cy, wf, hf, a.align != 0, ix, iy);
-            const Bilinear b = bilinear_zeros(ix, iy, a.w, a.h);
-            const float x0f = floorf(ix), y0f = floorf(iy);
-            if (!(x0f == cx0 && y0f == cy0)) {      // new cell (also taken for NaN positions)
-                flush();
-                cx0 = x0f; cy0 = y0f; have = true;
-                o[0] = b.y0 * a.w + b.x0; o[1] = b.y0 * a.w + b.x1;
-                o[2] = b.y1 * a.w + b.x0; o[3] = b.y1 * a.w + b.x1;
-#pragma unroll
-                for (int tpi = 0; tpi < 4; ++tpi)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[tpi][e] = 0.f;
+        costvol_bwd_sweep(a, 0, p, v, i, 0, a.D, rx, ry, rz, r, gr, [&](int tex, int e, float t) {
+            const size_t at = plane + (size_t)e * hw + tex;
+            if (PASS == 0) {
+                const unsigned int bits = __float_as_uint(t) & 0x7fffffffu;
+                // the plane only grows during this kernel: a value read here, however stale, is a lower bound of the final
+                // maximum, so skipping the atomic when it already covers `bits` cannot change the result
+                if (bits > __hip_atomic_load(a.mx + at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                    atomicMax(a.mx + at, bits);
+            } else {
+                const unsigned int m = a.mx[at];
+                if (m >= 0x7f800000u) return;              // a non-finite term landed here: pass 3 writes NaN
+                const long long q = __double2ll_rn((double)t * det_pow2(a.S + 127 - det_exp_field(m)));
+                if (q != 0) atomicAdd(a.sum + at, (unsigned long long)q);
             }
-            if (gk == 0.f) continue;
-            const float4 A = *reinterpret_cast<const float4*>(sv + (size_t)o[0] * a.Cp);
-            const float4 B = *reinterpret_cast<const float4*>(sv + (size_t)o[1] * a.Cp);
-            const float4 Cc = *reinterpret_cast<const float4*>(sv + (size_t)o[2] * a.Cp);
-            const float4 Dd = *reinterpret_cast<const float4*>(sv + (size_t)o[3] * a.Cp);
-            const float df[4] = {lerp4(A.x, B.x, Cc.x, Dd.x, b) - r.x, lerp4(A.y, B.y, Cc.y, Dd.y, b) - r.y,
-                                 lerp4(A.z, B.z, Cc.z, Dd.z, b) - r.z, lerp4(A.w, B.w, Cc.w, Dd.w, b) - r.w};
-            const float wt[4] = {b.nw, b.ne, b.sw, b.se};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (e >= ncomp) continue;
-                const float ds = (a.dist == NRGBD_DIST_L2) ? 2.f * df[e] : (df[e] > 0.f ? 1.f : (df[e] < 0.f ? -1.f : 0.f));
-                const float c = ds * gk;
-                if (PASS == 1) gr[e] -= c;
-#pragma unroll
-                for (int tpi = 0; tpi < 4; ++tpi) acc[tpi][e] = __builtin_fmaf(wt[tpi], c, acc[tpi][e]);
-            }
-        }
-        flush();
+        });
     }
     if (PASS == 1)
         *reinterpret_cast<float4*>(a.g_ref + (size_t)p * a.Cp + 4 * i) = make_float4(gr[0], gr[1], gr[2], gr[3]);
@@ -194,8 +138,7 @@ static int det_scale_exponent(int D, int h, int w) {
 extern "C" int nrgbd_costvol_bwd_det_workspace(int V, int Cp, int D, int h, int w, size_t* bytes) {
     using namespace nrgbd;
     if (!bytes) return NRGBD_E_NULL;
-    if (V <= 0 || V > NRGBD_MAX_V || Cp <= 0 || (Cp & 3) || D <= 0 || D > NRGBD_MAX_D || h <= 0 || w <= 0) return NRGBD_E_SHAPE;
-    if ((long long)h * w > 0x7fffffffLL / 4 || det_scale_exponent(D, h, w) < 0) return NRGBD_E_SHAPE;
+    if (costvol_bwd_check_shape(V, Cp, Cp, D, h, w, NRGBD_DIST_L2) != NRGBD_OK || det_scale_exponent(D, h, w) < 0) return NRGBD_E_SHAPE;
     *bytes = (size_t)V * Cp * h * w * (sizeof(unsigned long long) + sizeof(unsigned int));
     return NRGBD_OK;
 }
@@ -206,30 +149,29 @@ extern "C" int nrgbd_costvol_bwd_det(const float* ref_nhwc, const float* src_nhw
                                      int V, int C, int Cp, int D, int h, int w, void* workspace, size_t workspace_bytes,
                                      void* stream) {
     using namespace nrgbd;
-    if (!ref_nhwc || !src_nhwc || !KR || !Kt || !rays || !d_candi || !g_cost || !g_ref || !g_src || !workspace) return NRGBD_E_NULL;
-    if (V <= 0 || V > NRGBD_MAX_V || C <= 0 || D <= 0 || D > NRGBD_MAX_D || h <= 0 || w <= 0) return NRGBD_E_SHAPE;
-    if ((Cp & 3) || Cp < C || Cp - C > 3) return NRGBD_E_ALIGN;
-    if (dist != NRGBD_DIST_L2 && dist != NRGBD_DIST_L1) return NRGBD_E_ARG;
-    const int S = det_scale_exponent(D, h, w);
-    if ((long long)h * w > 0x7fffffffLL / 4 || S < 0) return NRGBD_E_SHAPE;
+    if (!workspace) return NRGBD_E_NULL;
+    CostvolBwdDetArgs a{{ref_nhwc, src_nhwc, KR, Kt, rays, d_candi, g_cost, g_ref, g_src, cx, cy, sigma,
+                         dist, align_corners, V, C, Cp, D, h, w}};
+    const int rc = costvol_bwd_check(a);
+    if (rc != NRGBD_OK) return rc;
+    a.S = det_scale_exponent(D, h, w);
+    if (a.S < 0) return NRGBD_E_SHAPE;
     const size_t hw = (size_t)h * w, n = (size_t)V * Cp * hw;
     const size_t need = n * (sizeof(unsigned long long) + sizeof(unsigned int));
     if (workspace_bytes < need) return NRGBD_E_SHAPE;
     if ((uintptr_t)workspace & 15) return NRGBD_E_ALIGN;
     hipStream_t s = (hipStream_t)stream;
-    unsigned long long* sum = static_cast<unsigned long long*>(workspace);
-    unsigned int* mx = reinterpret_cast<unsigned int*>(sum + n);
+    a.sum = static_cast<unsigned long long*>(workspace);
+    a.mx = reinterpret_cast<unsigned int*>(a.sum + n);
     hipError_t e = hipMemsetAsync(workspace, 0, need, s);
     if (e != hipSuccess) return (int)e;
-    const CostvolBwdDetArgs a{ref_nhwc, src_nhwc, KR, Kt, rays, d_candi, g_cost, g_ref, g_src, sum, mx, cx, cy, sigma,
-                              dist, align_corners, V, C, Cp, D, h, w, S};
     const dim3 grid(ceil_div((long)hw, kDetThreads), Cp >> 2);
     hipLaunchKernelGGL(costvol_bwd_det_sweep<0>, grid, dim3(kDetThreads), 0, s, a);
     NRGBD_CHECK_LAUNCH();
     hipLaunchKernelGGL(costvol_bwd_det_sweep<1>, grid, dim3(kDetThreads), 0, s, a);
     NRGBD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(costvol_bwd_det_convert, dim3((unsigned)ceil_div((long)n / 4, 256)), dim3(256), 0, s, sum, mx, g_src,
-                       V, Cp >> 2, (int)hw, S);
+    hipLaunchKernelGGL(costvol_bwd_det_convert, dim3((unsigned)ceil_div((long)n / 4, 256)), dim3(256), 0, s, a.sum, a.mx, g_src,
+                       V, Cp >> 2, (int)hw, a.S);
     NRGBD_CHECK_LAUNCH();
     return NRGBD_OK;
 }

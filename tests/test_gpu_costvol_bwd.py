@@ -9,10 +9,10 @@ import pytest
 import torch
 
 import costvol_bwd_exact as cx
+from costvol_bwd_gpu import DEV, LDS_SHAPES, _compare, _nchw, _run, _upload
 from neuralrgbd_amd import ops
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 
 
 def _kernel_path(V, Cp, D, h, w):
@@ -28,52 +28,6 @@ def _kernel_path(V, Cp, D, h, w):
     return "lds", n.value // per_slice
 
 
-def _upload(case):
-    V, C, h, w = case["src"].shape
-    Cp = ops.padded_channels(C)
-    tex = torch.zeros(V + 1, h, w, Cp)
-    tex[:V, ..., :C] = torch.from_numpy(case["src"]).permute(0, 2, 3, 1)
-    tex[V, ..., :C] = torch.from_numpy(case["ref"]).permute(1, 2, 0)
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)
-    return tex.to(DEV), dev(case["KR"]), dev(case["Kt"]), dev(case["rays"]), dev(case["d_candi"]), dev(case["g_cost"])
-
-
-def _run(case, dist, align):
-    """ops.costvol_bwd on the case -> (g_ref [Cp,h,w], g_src [V,Cp,h,w]) as numpy."""
-    V, C = case["src"].shape[:2]
-    tex, KR, Kt, rays, d, g = _upload(case)
-    g_ref, g_src = ops.costvol_bwd(tex[V], tex[:V], KR, Kt, rays, d, case["cx"], case["cy"], case["sigma"], C, g, dist=dist,
-                                   align_corners=align)
-    torch.cuda.synchronize()
-    return g_ref.permute(2, 0, 1).cpu().numpy(), g_src.permute(0, 3, 1, 2).cpu().numpy()
-
-
-def _where(name, at, ex, V):
-    if name == "g_ref":
-        c, y, x = at
-        return "g_ref channel %d pixel (%d, %d), %d terms" % (c, y, x, ex["n_ref"][y, x])
-    v, c, y, x = at
-    return "g_src view %d channel %d texel (%d, %d), %d terms (%d whatever g)" % (v, c, y, x, ex["n_src"][v, y, x], ex["reach_src"][v, y, x])
-
-
-def _compare(label, case, dist, align, got_ref, got_src, factor=1.0):
-    """Assert both gradients within factor x bound of the comparator; returns the comparator's result."""
-    V, C, h, w = case["src"].shape
-    ex = cx.exact_case(case, dist, align)
-    share = ex["ties"] / max(1, ex["elements"]) if dist == "L1" else 0.0
-    r_ref, at_ref, bad_ref = cx.worst_ratio(got_ref[:C], ex["g_ref"], factor * ex["bound_ref"])
-    r_src, at_src, bad_src = cx.worst_ratio(got_src[:, :C], ex["g_src"], factor * ex["bound_src"])
-    print("[parity] costvol_bwd %-44s %s align=%d: worst error / bound g_ref %.3f g_src %.3f, tie share %.1e, max |g_ref| %.1f |g_src| %.1f"
-          % (label, dist, align, r_ref, r_src, share, np.abs(ex["g_ref"]).max(), np.abs(ex["g_src"]).max()))
-    assert share <= cx.TIE_CAP
-    assert np.abs(ex["g_src"]).max() > 0 and np.abs(ex["g_ref"]).max() > 0
-    assert bad_ref == 0, "%d elements beyond the bound, worst %.2f x at %s" % (bad_ref, r_ref, _where("g_ref", at_ref, ex, V))
-    assert bad_src == 0, "%d elements beyond the bound, worst %.2f x at %s" % (bad_src, r_src, _where("g_src", at_src, ex, V))
-    # the padding lanes C ... Cp-1 carry no gradient
-    assert (got_ref[C:] == 0).all() and (got_src[:, C:] == 0).all()
-    return ex
-
-
 def _check(case, dist, align, kernel, label=None, slices=None):
     V, C, h, w = case["src"].shape
     D = len(case["d_candi"])
@@ -83,20 +37,13 @@ def _check(case, dist, align, kernel, label=None, slices=None):
         assert n == slices
     got_ref, got_src = _run(case, dist, align)
     name = "%s %dx%dx%d V%d C%d %s/%d" % (label or case["key"][5], h, w, D, V, C, path, n)
-    return _compare(name, case, dist, align, got_ref, got_src), got_ref, got_src
+    return _compare(name, case, dist, align, got_ref, got_src, "costvol_bwd"), got_ref, got_src
 
 
 # ---- kernel paths ------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("dist", ["L2", "L1"])
-@pytest.mark.parametrize("h,w,D,V,C,family", [
-    (64, 96, 64, 4, 67, "driver"),     # the training shape: slices = CUs / (V Cp / 4), long same-cell runs on the far planes
-    (64, 96, 16, 2, 67, "small"),
-    (33, 47, 1, 3, 5, "small"),        # fewer candidates than slices
-    (33, 47, 2, 3, 5, "small"),
-    (9, 11, 6, 2, 3, "small"), (33, 47, 6, 2, 3, "small"),      # every ncomp of the last channel word, hw no multiple of 1024
-    (33, 47, 6, 2, 4, "small"), (33, 47, 6, 2, 5, "large"), (33, 47, 6, 2, 64, "small"), (33, 47, 6, 2, 67, "large"),
-])
+@pytest.mark.parametrize("h,w,D,V,C,family", LDS_SHAPES)
 def test_lds_kernel_shapes(h, w, D, V, C, family, dist):
     _check(cx.make_case(h, w, D, V, C, family), dist, False, "lds")
 
@@ -199,8 +146,7 @@ def test_outputs_fully_overwritten_from_nan(kernel, h, w, D, V, dist, C):
     torch.cuda.synchronize()
     assert torch.isfinite(g_ref).all() and torch.isfinite(g_src).all()
     assert (g_ref[..., C:] == 0).all() and (g_src[..., C:] == 0).all()
-    _compare("NaN-filled buffers %dx%dx%d V%d C%d %s" % (h, w, D, V, C, kernel), case, dist, False,
-             g_ref.permute(2, 0, 1).cpu().numpy(), g_src.permute(0, 3, 1, 2).cpu().numpy())
+    _compare("NaN-filled buffers %dx%dx%d V%d C%d %s" % (h, w, D, V, C, kernel), case, dist, False, *_nchw(g_ref, g_src), "costvol_bwd")
 
 
 # ---- reproducibility, as far as it holds --------------------------------------------------------------------------------------
@@ -239,4 +185,4 @@ def test_autograd_wrapper_passes_dist_and_align_corners():
                            align_corners=False)
     assert torch.equal(cost.detach(), want) and not torch.equal(want, other)
     grad = tex.grad.permute(0, 3, 1, 2).cpu().numpy()
-    _compare("PlaneSweepCost", case, "L1", True, grad[V], grad[:V])
+    _compare("PlaneSweepCost", case, "L1", True, grad[V], grad[:V], "costvol_bwd")

@@ -15,40 +15,15 @@ import pytest
 import torch
 
 import costvol_bwd_exact as cx
+import costvol_bwd_gpu
+from costvol_bwd_gpu import DEV, LDS_SHAPES, _compare, _nchw, _upload
 from neuralrgbd_amd import ops
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 
 
-def _upload(case):
-    V, C, h, w = case["src"].shape
-    Cp = ops.padded_channels(C)
-    tex = torch.zeros(V + 1, h, w, Cp)
-    tex[:V, ..., :C] = torch.from_numpy(case["src"]).permute(0, 2, 3, 1)
-    tex[V, ..., :C] = torch.from_numpy(case["ref"]).permute(1, 2, 0)
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)
-    return tex.to(DEV), dev(case["KR"]), dev(case["Kt"]), dev(case["rays"]), dev(case["d_candi"]), dev(case["g_cost"])
-
-
-def _nchw(g_ref, g_src):
-    return g_ref.permute(2, 0, 1).cpu().numpy(), g_src.permute(0, 3, 1, 2).cpu().numpy()
-
-
-def _run(case, dist, align, deterministic=True, stream=None):
-    """ops.costvol_bwd on the case -> (g_ref [Cp,h,w], g_src [V,Cp,h,w]) as numpy."""
-    V, C = case["src"].shape[:2]
-    tex, KR, Kt, rays, d, g = _upload(case)
-    torch.cuda.synchronize()
-    if stream is None:
-        out = ops.costvol_bwd(tex[V], tex[:V], KR, Kt, rays, d, case["cx"], case["cy"], case["sigma"], C, g, dist=dist,
-                              align_corners=align, deterministic=deterministic)
-    else:
-        with torch.cuda.stream(stream):
-            out = ops.costvol_bwd(tex[V], tex[:V], KR, Kt, rays, d, case["cx"], case["cy"], case["sigma"], C, g, dist=dist,
-                                  align_corners=align, deterministic=deterministic)
-    torch.cuda.synchronize()
-    return _nchw(*out)
+def _run(case, dist, align, stream=None):
+    return costvol_bwd_gpu._run(case, dist, align, deterministic=True, stream=stream)
 
 
 def _run_raw_from_nan(case, dist, align):
@@ -73,49 +48,15 @@ def _run_raw_from_nan(case, dist, align):
     return _nchw(g_ref, g_src)
 
 
-def _where(name, at, ex):
-    if name == "g_ref":
-        c, y, x = at
-        return "g_ref channel %d pixel (%d, %d), %d terms" % (c, y, x, ex["n_ref"][y, x])
-    v, c, y, x = at
-    return "g_src view %d channel %d texel (%d, %d), %d terms (%d whatever g)" % (v, c, y, x, ex["n_src"][v, y, x], ex["reach_src"][v, y, x])
-
-
-def _compare(label, case, dist, align, got_ref, got_src):
-    """Assert both gradients within 1 x bound of the comparator; returns the comparator's result."""
-    V, C, h, w = case["src"].shape
-    ex = cx.exact_case(case, dist, align)
-    share = ex["ties"] / max(1, ex["elements"]) if dist == "L1" else 0.0
-    r_ref, at_ref, bad_ref = cx.worst_ratio(got_ref[:C], ex["g_ref"], ex["bound_ref"])
-    r_src, at_src, bad_src = cx.worst_ratio(got_src[:, :C], ex["g_src"], ex["bound_src"])
-    print("[parity] costvol_bwd_det %-40s %s align=%d: worst error / bound g_ref %.3f g_src %.3f, tie share %.1e, max |g_ref| %.1f |g_src| %.1f"
-          % (label, dist, align, r_ref, r_src, share, np.abs(ex["g_ref"]).max(), np.abs(ex["g_src"]).max()))
-    assert share <= cx.TIE_CAP
-    assert np.abs(ex["g_src"]).max() > 0 and np.abs(ex["g_ref"]).max() > 0
-    assert bad_ref == 0, "%d elements beyond the bound, worst %.2f x at %s" % (bad_ref, r_ref, _where("g_ref", at_ref, ex))
-    assert bad_src == 0, "%d elements beyond the bound, worst %.2f x at %s" % (bad_src, r_src, _where("g_src", at_src, ex))
-    # the padding lanes C ... Cp-1 carry no gradient
-    assert (got_ref[C:] == 0).all() and (got_src[:, C:] == 0).all()
-    return ex
-
-
 def _check(case, dist, align, label=None):
     V, C, h, w = case["src"].shape
     got_ref, got_src = _run(case, dist, align)
     name = "%s %dx%dx%d V%d C%d" % (label or case["key"][5], h, w, len(case["d_candi"]), V, C)
-    return _compare(name, case, dist, align, got_ref, got_src), got_ref, got_src
+    return _compare(name, case, dist, align, got_ref, got_src, "costvol_bwd_det"), got_ref, got_src
 
 
 # ---- parity at 1 x bound -------------------------------------------------------------------------------------------------------
 
-LDS_SHAPES = [
-    (64, 96, 64, 4, 67, "driver"),     # the training shape
-    (64, 96, 16, 2, 67, "small"),
-    (33, 47, 1, 3, 5, "small"),
-    (33, 47, 2, 3, 5, "small"),
-    (9, 11, 6, 2, 3, "small"), (33, 47, 6, 2, 3, "small"),      # every ncomp of the last channel word, hw no multiple of the block
-    (33, 47, 6, 2, 4, "small"), (33, 47, 6, 2, 5, "large"), (33, 47, 6, 2, 64, "small"), (33, 47, 6, 2, 67, "large"),
-]
 LARGE_SHAPES = [
     (96, 128, 4, 1, 6, "small"),
     (97, 131, 4, 4, 67, "small"),
@@ -234,13 +175,13 @@ def test_det_autograd_switch_selects_the_kernel_of_the_forward():
     cost, t = _plane_sweep_grad(case, tex, KR, Kt, rays, d, g, "L1", True)
     (cost * g).sum().backward()
     grad = t.grad.permute(0, 3, 1, 2).cpu().numpy()
-    _compare("PlaneSweepCost, switch off", case, "L1", True, grad[V], grad[:V])
+    _compare("PlaneSweepCost, switch off", case, "L1", True, grad[V], grad[:V], "costvol_bwd_det")
     # a forward recorded with the switch off keeps the atomic kernels even if the backward runs under the switch
     cost, t = _plane_sweep_grad(case, tex, KR, Kt, rays, d, g, "L1", True)
     with ag.deterministic():
         (cost * g).sum().backward()
     grad = t.grad.permute(0, 3, 1, 2).cpu().numpy()
-    _compare("PlaneSweepCost, forward off / backward on", case, "L1", True, grad[V], grad[:V])
+    _compare("PlaneSweepCost, forward off / backward on", case, "L1", True, grad[V], grad[:V], "costvol_bwd_det")
     # restored after an exception too
     with pytest.raises(RuntimeError):
         with ag.deterministic():
