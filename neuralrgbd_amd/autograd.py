@@ -141,53 +141,36 @@ class Conv3dCL(torch.autograd.Function):
     x [D,H,W,Cin] (Cin in {16, 64}), w [64,Cin,3,3,3] -> y [D,H,W,64].
     """
 
-    depth_f43 = True     # the 64 -> 64 layers (both directions) on wino_dw4.hip where D % 4 == 0; False: wino_dw.hip (A/B)
-
-    @staticmethod
-    def _depth_kind(x):
-        """4: wino_dw4.hip takes the grid, 2: wino_dw.hip does, 0: neither (wino_pc.hip / conv3d.hip)."""
-        D, H, W = x.shape[0], x.shape[1], x.shape[2]
-        if Conv3dCL.depth_f43 and ops.conv_wino_dw4_supported(D, H, W, 64, 64):
-            return 4
-        return 2 if ops.conv_wino_dw_supported(D, H, W, 64, 64) else 0
+    # Candidate kernels in order of preference (ops.conv3d_kernel holds the table and the reasons).  A/B: drop "dw4" from all three
+    kernels = ("dw4", "dw", "pc", "direct")           # the 64 -> 64 layers, both directions
+    kernels_first = ("dw4", "direct")                 # the 16 -> 64 first layer, forward
+    kernels_first_dgrad = ("dw4", "dw", "direct")     # ... its data gradient: a 64 -> 64 (16 real) layer on the output gradient
 
     @staticmethod
     def _conv(x, w, transposed=False, packed=None, key=None):
-        """y = conv(x, w) (transposed: with w's data-gradient weights): the Winograd-domain kernels (wino_dw4.hip / wino_dw.hip /
-        wino_pc.hip) for the 64 -> 64 layers, the direct kernel otherwise.  packed: the weight stream of this call if the caller
-        already has it; key: pack_cache key of the layer."""
-        tr = bool(transposed)
-        if w.shape[0] == 64 and w.shape[1] == 64:
-            kind = Conv3dCL._depth_kind(x)
-            if kind == 4:                                                                # F(4,3) along depth (wino_dw4.hip)
-                wp = packed if packed is not None else _cached(key, ("dw4", tr), lambda: ops.conv_wino_dw4_pack(w, transposed))
-                return ops.conv_wino_dw4(x, wp, 64, want_stats=False)[0]
-            if kind == 2:                                                                # F(2,3) along depth (wino_dw.hip)
-                wp = packed if packed is not None else _cached(key, ("dw", tr), lambda: ops.conv_wino_dw_pack(w, transposed))
-                return ops.conv_wino_dw(x, wp, 64, want_stats=False)[0]
-            wp = packed if packed is not None else _cached(key, ("pc3", tr), lambda: ops.conv_wino_pack(w, transposed))
-            return ops.conv_wino(x, wp, 64, 3, want_stats=False)[0]
-        if transposed:
-            cin = w.shape[1]
+        """y = conv(x, w) (transposed: with w's data-gradient weights): choose the kernel, fetch its weight stream, launch.
+        packed: (kind, stream) of this call if the caller already has it; key: pack_cache key of the layer."""
+        cin = w.shape[1]
+        kind = ops.conv3d_kernel(*x.shape, 64, Conv3dCL.kernels if cin == 64 else Conv3dCL.kernels_first_dgrad if transposed else Conv3dCL.kernels_first)
 
-            def wt():
-                t = w.transpose(0, 1).flip(2, 3, 4)                   # [Cin, 64, 3,3,3]: correlation with the flipped kernel
+        def stream():
+            wf = w.contiguous()
+            if transposed:                                            # as a forward layer of THIS call
+                wf = w.transpose(0, 1).flip(2, 3, 4)                  # [Cin, 64, 3,3,3]: correlation with the flipped kernel
                 if cin < 64:                                          # the kernels produce 64 outputs: pad, then slice
-                    t = torch.cat((t, t.new_zeros(64 - cin, 64, 3, 3, 3)), dim=0)
-                return t.contiguous()
-            kind = Conv3dCL._depth_kind(x)
-            if kind == 4:
-                gx = ops.conv_wino_dw4(x, _cached(key, ("dw4t", cin), lambda: ops.conv_wino_dw4_pack(wt())), 64, want_stats=False)[0]
-            elif kind == 2:
-                # data gradient of the first layer (16 -> 64): a 64 -> 64(16 real) layer in the Winograd domain, 0.31 instead of
-                # 0.64 ms on the direct kernel at the training grid
-                gx = ops.conv_wino_dw(x, _cached(key, ("dwt", cin), lambda: ops.conv_wino_dw_pack(wt())), 64, want_stats=False)[0]
-            else:
-                gx = ops.conv3d(x, _cached(key, ("d3t", cin), lambda: ops.conv3d_pack_weights(wt())), want_stats=False)[0]
-            return gx[..., :cin].contiguous() if cin < 64 else gx
-        if w.shape[0] == 64 and w.shape[1] == 16 and Conv3dCL._depth_kind(x) == 4:      # the first layer's forward: one channel block
-            return ops.conv_wino_dw4(x, _cached(key, ("dw4", False), lambda: ops.conv_wino_dw4_pack(w)), 64, want_stats=False)[0]
-        return ops.conv3d(x, _cached(key, ("d3", False), lambda: ops.conv3d_pack_weights(w.contiguous())), want_stats=False)[0]
+                    wf = torch.cat((wf, wf.new_zeros(64 - cin, 64, 3, 3, 3)), dim=0)
+                wf = wf.contiguous()
+            return {"dw4": ops.conv_wino_dw4_pack, "dw": ops.conv_wino_dw_pack, "pc": ops.conv_wino_pack, "direct": ops.conv3d_pack_weights}[kind](wf)
+        wp = packed[1] if packed is not None and packed[0] == kind else _cached(key, (kind, bool(transposed), cin), stream)
+        if kind == "dw4":                                             # F(4,3) along depth (wino_dw4.hip)
+            y = ops.conv_wino_dw4(x, wp, 64, want_stats=False)[0]
+        elif kind == "dw":                                            # F(2,3) along depth (wino_dw.hip)
+            y = ops.conv_wino_dw(x, wp, 64, want_stats=False)[0]
+        elif kind == "pc":
+            y = ops.conv_wino(x, wp, 64, 3, want_stats=False)[0]
+        else:
+            y = ops.conv3d(x, wp, want_stats=False)[0]
+        return y[..., :cin].contiguous() if transposed and cin < 64 else y
 
     @staticmethod
     def forward(ctx, x, w, key=None, grad_channel=None):
@@ -198,9 +181,11 @@ class Conv3dCL(torch.autograd.Function):
         fwd = bwd = None
         ctx.grad_channel = grad_channel
         if w.shape[0] == 64 and w.shape[1] == 64 and ctx.needs_input_grad[0]:
-            # both weight streams (forward + data gradient) in one launch: the weights changed since the last iteration anyway
-            kind = Conv3dCL._depth_kind(x)
-            fwd, bwd = _cached(key, ("both3", kind), lambda: ops.conv_wino_pack_both(w, dw=kind))
+            ctx.kind = ops.conv3d_kernel(*x.shape, 64, Conv3dCL.kernels)
+            if ctx.kind != "direct":
+                # both weight streams (forward + data gradient) in one launch: the weights changed since the last iteration anyway
+                both = _cached(key, ("both3", ctx.kind), lambda: ops.conv_wino_pack_both(w, dw={"dw4": 4, "dw": 2, "pc": 0}[ctx.kind]))
+                fwd, bwd = (ctx.kind, both[0]), both[1]
         y = Conv3dCL._conv(x, w, packed=fwd, key=key)
         ctx.save_for_backward(x, w, bwd)
         ctx.key = key
@@ -221,7 +206,7 @@ class Conv3dCL(torch.autograd.Function):
                 gx = gy.new_zeros(gy.shape[:3] + (w.shape[1],))
                 gx[..., c] = ops.conv3d_cout1(gy, w_tm)
             else:
-                gx = Conv3dCL._conv(gy, w, transposed=True, packed=bwd, key=ctx.key)
+                gx = Conv3dCL._conv(gy, w, transposed=True, packed=None if bwd is None else (ctx.kind, bwd), key=ctx.key)
         return gx, gw, None, None
 
 
@@ -281,11 +266,9 @@ def batch_norm_act_cl(x_cl, bn, relu, residual=None):
     MIOpen — ADVICE r5).  CPU tensors (host-side structure tests) go through torch.nn.functional."""
     import torch.nn.functional as F
     C = x_cl.shape[-1]
+    from .nets import _bn_batch_args, _bn_eval_affine
     use_batch = bn.training or not bn.track_running_stats
-    upd = bn.training and bn.track_running_stats
-    if upd:
-        bn.num_batches_tracked += 1
-    m = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+    m, rm, rv, _ = _bn_batch_args(bn, host_counter=True)      # csrc/bn_train.hip takes no counter: bumped on the host
     on_gpu = x_cl.is_cuda and x_cl.dtype == torch.float32
     if on_gpu and use_batch:
         if not (bn.affine and ops.bn_cl_supported(x_cl.numel() // C, C)):
@@ -294,13 +277,10 @@ def batch_norm_act_cl(x_cl, bn, relu, residual=None):
                              "covers C %% 4 == 0 with C / 4 dividing 256" % (C, bn.affine))
         if x_cl.numel() // C <= 1:      # nn.BatchNorm's own refusal (torch/nn/functional.py::_verify_batch_size)
             raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x_cl.shape),))
-        return BatchNormActCL.apply(x_cl, bn.weight, bn.bias, residual, bn.eps, relu, m,
-                                    bn.running_mean if upd else None, bn.running_var if upd else None)
+        return BatchNormActCL.apply(x_cl, bn.weight, bn.bias, residual, bn.eps, relu, m, rm, rv)
     if on_gpu:                          # eval(): the affine map of the running statistics
-        s_ = torch.rsqrt(bn.running_var + bn.eps)
-        if bn.affine:
-            s_ = s_ * bn.weight
-        y = x_cl * s_ + ((bn.bias if bn.affine else 0.0) - bn.running_mean * s_)
+        s_, t_ = _bn_eval_affine(bn, detach=False)
+        y = x_cl * s_ + t_
     else:
         y = F.batch_norm(x_cl.reshape(-1, C), bn.running_mean if bn.track_running_stats else None,
                          bn.running_var if bn.track_running_stats else None, bn.weight, bn.bias, use_batch, m, bn.eps).view_as(x_cl)

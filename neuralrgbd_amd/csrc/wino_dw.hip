@@ -48,14 +48,11 @@ constexpr int kDwNBuf = 2;                     // V buffers (wino_pc.hip: 3; the
 // AHEAD: iteration i publishes stage i into strip[i & 1] and transforms stage i - 1 from strip[(i - 1) & 1] (complete since the
 // stage barrier), so the only synchronisation is the barrier the stage has anyway (one more at the start).  Per stage and
 // producer wave: 6 instead of 10 loads, 18 instead of 30 packed activation / combine FMAs, 9 instead of 15 strip accesses.
-#ifndef NRGBD_DW_SHARED
-#define NRGBD_DW_SHARED 1   // 0: the private-strip producers (experimental A/B builds only)
-#endif
 constexpr int kDwShRows = kPcTH + 2;                       // halo rows of a tile
 constexpr int kDwShStrip = kDwShRows * kPcRawW * kCB;      // floats of one shared strip: [10 rows][20 pixels][16] = 12.8 KB
 constexpr int kDwShItems = kDwShRows * 18 * 4;             // (row, column, 16-byte word) items of a unit: 720
-constexpr int kDwNPF = NRGBD_DW_SHARED ? 3 : kPcNPF;       // items per producer lane and unit
-constexpr int kDwStrips = NRGBD_DW_SHARED ? 2 * kDwShStrip : 4 * kPcRawWave;   // floats of the strip region
+constexpr int kDwNPF = 3;                                  // items per producer lane and unit (720 over 256 lanes)
+constexpr int kDwStrips = 2 * kDwShStrip;                  // floats of the strip region
 
 struct DwTile { int z0, y0, x0, cg, row0; };   // row0: statistics row of slice z0 (slice z0 + 1: row0 + 1)
 
@@ -80,9 +77,6 @@ __device__ __forceinline__ DwTile dw_decode(int t, const WinoPcArgs& a) {
 // first read, and the 32 workgroups of an XCD stream 1.5 MB (3 MB with a residual operand) per stage through their 4 MB L2 beside
 // the 1 MB weight stream — every re-read missed (profiles/r3_pmc_wino.txt: the residual variant fetched ALL its reads).  Turning
 // round at the phase boundary puts the most recently read units first.
-#ifndef NRGBD_DW_IDENT
-#define NRGBD_DW_IDENT 1   // 0: experimental A/B builds only (tools/knet_ab.py)
-#endif
 #ifndef NRGBD_DW_SERP
 #define NRGBD_DW_SERP 1
 #endif
@@ -110,7 +104,7 @@ template <bool RES, bool MAT, bool RSID, bool IDENT = false, bool CLAMP = false>
 __global__ __launch_bounds__(512) void conv_wino_dw_kernel(const WinoPcArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* Vb = lds;                                   // [2][16 xi][32 tiles][16]
-    float* rawb = lds + kDwNBuf * kPcV;                // SHARED: [2][10 rows][20 pixels][16]; else [4 producer waves][4 rows][20 pixels][16]
+    float* rawb = lds + kDwNBuf * kPcV;                // the two shared strips: [2][10 rows][20 pixels][16]
     float* stashb = rawb + kDwStrips;                  // [4 consumer waves][2 slices][8][64][4]
     float* ssl = stashb + 4 * kDwStashWave;            // [Cin][2] (scale, shift) of x, then [Cin][2] of res
 
@@ -165,7 +159,7 @@ __global__ __launch_bounds__(512) void conv_wino_dw_kernel(const WinoPcArgs a) {
         f32x4 Bn[kPcNB], An[2][2];
 #pragma unroll
         for (int b = 0; b < kPcBD; ++b) Bn[b] = wt[b * 256];
-        if constexpr (NRGBD_DW_SHARED != 0) __syncthreads();   // the producers publish stage 0 (transformed one iteration later)
+        __syncthreads();                               // the producers publish stage 0 (transformed one iteration later)
         __syncthreads();                               // producers finish stage 0
         int buf = 0;
         An[0][0] = *reinterpret_cast<const f32x4*>(Vb + a0);
@@ -318,14 +312,13 @@ __global__ __launch_bounds__(512) void conv_wino_dw_kernel(const WinoPcArgs a) {
     } else {
         // =========================================== producer: tile row pw (8 Winograd tiles) ===========================
         const int pw = wv;
-        constexpr bool SH = NRGBD_DW_SHARED != 0;
-        constexpr int kItems = SH ? kDwShItems : kPcItems;
-        float* raw = SH ? rawb : rawb + pw * kPcRawWave;   // SH: the strip this iteration PUBLISHES into (set per iteration)
+        constexpr int kItems = kDwShItems;
+        float* raw = rawb;                                  // the strip this iteration PUBLISHES into (set per iteration)
         const float* rawT = raw;                            // ... and the one it TRANSFORMS from
         const int w4 = lane & 3;
-        // item u of this lane: word (item & 3) of halo pixel item >> 2, pixels in (row, de-interleaved column) order.
-        // SH: item = 192 pw + lane + 64 u over the whole 10-row halo; else lane + 64 u over the wave's own 4 rows
-        auto item_id = [&](int u) { return (SH ? 192 * pw : 0) + lane + 64 * u; };
+        // item u of this lane: word (item & 3) of halo pixel item >> 2, pixels in (row, de-interleaved column) order:
+        // item = 192 pw + lane + 64 u over the whole 10-row halo
+        auto item_id = [&](int u) { return 192 * pw + lane + 64 * u; };
         auto item_rr = [&](int u) { return (item_id(u) >> 2) / 18; };
         auto item_cp = [&](int u) { const int pi = item_id(u) >> 2; return pi - (pi / 18) * 18; };
         auto item_col = [&](int u) { const int cp = item_cp(u); return cp < 9 ? 2 * cp : 2 * cp - 17; };
@@ -338,7 +331,7 @@ __global__ __launch_bounds__(512) void conv_wino_dw_kernel(const WinoPcArgs a) {
         }
         const int tword = lane & 3, txl = ((lane >> 5) << 2) | ((lane >> 2) & 3), thalf = (lane >> 4) & 1;
         const int ttile = pw * 8 + txl;
-        const int rdc = txl * kCB + tword * 4 + (SH ? 2 * pw * kPcRawW * kCB : 0);   // SH: the tile row's halo rows start at strip row 2 pw
+        const int rdc = txl * kCB + tword * 4 + 2 * pw * kPcRawW * kCB;   // the tile row's halo rows start at strip row 2 pw
         const int rdR0 = (thalf ? 2 : 0) * kPcRawW * kCB + rdc, rdR1 = (thalf ? 1 : 2) * kPcRawW * kCB + rdc,
                   rdR2 = (thalf ? 3 : 1) * kPcRawW * kCB + rdc;
         const float sg = thalf ? -1.f : 1.f;
@@ -351,14 +344,13 @@ __global__ __launch_bounds__(512) void conv_wino_dw_kernel(const WinoPcArgs a) {
             b_own = 0;
 #pragma unroll
             for (int u = 0; u < kDwNPF; ++u) {
-                const int rr = item_rr(u), hy = SH ? rr : 2 * pw + rr, hx = item_col(u);
+                const int hy = item_rr(u), hx = item_col(u);
                 const int gy = tt.y0 + hy - 1, gx = tt.x0 + hx - 1;
                 const bool in = item_id(u) < kItems && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
                 b_off[u] = 4u * (in ? (unsigned)(((size_t)gy * a.W + gx) * a.Cin + w4 * 4) : (unsigned)(w4 * 4));
                 b_keep[u] = in ? 1.f : 0.f;
-                // the materialised input is written once per pixel: SH: every halo pixel has ONE loader, it owns the tile's own 8 x 16;
-                // else the wave whose strip rows 1, 2 are the pixel's tile row
-                const bool mine = SH ? (hy >= 1 && hy <= kPcTH) : (rr == 1 || rr == 2);
+                // the materialised input is written once per pixel: every halo pixel has ONE loader, it owns the tile's own 8 x 16
+                const bool mine = hy >= 1 && hy <= kPcTH;
                 if (in && mine && hx >= 1 && hx <= kPcTW) b_own |= 1u << u;
             }
         };
@@ -485,12 +477,7 @@ __global__ __launch_bounds__(512) void conv_wino_dw_kernel(const WinoPcArgs a) {
                     *reinterpret_cast<f32x4*>(raw + wr_off[u]) = v;
                 }
             };
-            if constexpr (RES && kDwNPF > 3) {
-                group(std::integral_constant<int, 0>{}, std::integral_constant<int, 3>{});
-                group(std::integral_constant<int, 3>{}, std::integral_constant<int, kDwNPF>{});
-            } else {
-                group(std::integral_constant<int, 0>{}, std::integral_constant<int, kDwNPF>{});
-            }
+            group(std::integral_constant<int, 0>{}, std::integral_constant<int, kDwNPF>{});
         };
 
         // plane transform B^T d B of this lane's (tile, word): rows (2 of the 4 xi_y), then columns; strip rawT -> V[qbuf]
@@ -516,7 +503,7 @@ __global__ __launch_bounds__(512) void conv_wino_dw_kernel(const WinoPcArgs a) {
             *reinterpret_cast<f32x4*>(Vq + pc_slot(xb + 2, ttile, tword)) = pk_fma_s(yb[1], m1, yb[2]);
             *reinterpret_cast<f32x4*>(Vq + pc_slot(xb + 3, ttile, tword)) = pk_fma_s(yb[3], m1, yb[1]);
         };
-        int gi = 0;                            // iterations so far (SH: strip parity; the transform lags one iteration)
+        int gi = 0;                            // iterations so far (strip parity; the transform lags one iteration)
 
         for (int it = 0; it < count; ++it) {
             has_next = it + 1 < count;
@@ -526,7 +513,7 @@ __global__ __launch_bounds__(512) void conv_wino_dw_kernel(const WinoPcArgs a) {
             for (int s = 0; s < NS; ++s) {
                 // the book of the next tile is needed by the refills of the tile's last stage
                 if (s == NS - 1 && has_next) { tn = dw_decode(first + (it + 1) * step, a); setup(tn, nxt_off, nxt_keep, nxt_own); }
-                if constexpr (SH) { raw = rawb + (gi & 1) * kDwShStrip; rawT = rawb + ((gi & 1) ^ 1) * kDwShStrip; }
+                raw = rawb + (gi & 1) * kDwShStrip; rawT = rawb + ((gi & 1) ^ 1) * kDwShStrip;
                 const int zA = tl.z0 + dw_zA(t), zB = tl.z0 + dw_zB(t);
                 const bool zinA = zA >= 0, zinB = zB < a.N;       // zA <= z0 + 1 < N and zB >= z0 >= 0 always hold
                 const bool wmat = MAT && t == 1 && tl.cg == 0;    // phase 1 publishes slices z0 (unit A) and z0 + 1 (unit B)
@@ -564,11 +551,10 @@ __global__ __launch_bounds__(512) void conv_wino_dw_kernel(const WinoPcArgs a) {
                     else publish(std::true_type{}, std::false_type{}, setB, zB, cbe, wmat, t == 1 ? 1.f : -1.f);
                 }
                 if (!(abl & (2 | 32))) issue(nx && has_next, tnx, cbne, true, setB);
-                if constexpr (!SH) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // private strip: the transform reads what this wave just wrote
-                // (3) plane transform B^T d B of this lane's (tile, word) — SH: of the stage published one iteration ago
-                if (!(abl & (2 | 4)) && (!SH || gi > 0)) transform();
+                // (3) plane transform B^T d B of this lane's (tile, word), of the stage published one iteration ago
+                if (!(abl & (2 | 4)) && gi > 0) transform();
                 __syncthreads();
-                if (!SH || gi > 0) qbuf ^= 1;
+                if (gi > 0) qbuf ^= 1;
                 ++gi;
                 if (++cb == ncb) { cb = 0; ++t; }
             }
@@ -577,11 +563,9 @@ __global__ __launch_bounds__(512) void conv_wino_dw_kernel(const WinoPcArgs a) {
             for (int u = 0; u < kDwNPF; ++u) { cur_off[u] = nxt_off[u]; cur_keep[u] = nxt_keep[u]; }
             cur_own = nxt_own;
         }
-        if constexpr (SH) {                    // the last published stage
-            rawT = rawb + ((gi & 1) ^ 1) * kDwShStrip;
-            transform();
-            __syncthreads();
-        }
+        rawT = rawb + ((gi & 1) ^ 1) * kDwShStrip;   // the last published stage
+        transform();
+        __syncthreads();
         __syncthreads();                       // the consumers' last stage
     }
 }
@@ -697,7 +681,7 @@ static int conv_wino_dw_launch(const float* x, const float* x_ss, int x_relu, co
     } else if (res && rsid) { if (materialized) NRGBD_WINO_DW_LAUNCH(true, true, true); else NRGBD_WINO_DW_LAUNCH(true, false, true); }
     else if (res) { if (materialized) NRGBD_WINO_DW_LAUNCH(true, true, false); else NRGBD_WINO_DW_LAUNCH(true, false, false); }
     else if (materialized) NRGBD_WINO_DW_LAUNCH(false, true, false);
-    else if (NRGBD_DW_IDENT && !x_ss && !x_relu) {   // the IDENT instantiation: nothing to apply to x
+    else if (!x_ss && !x_relu) {   // the IDENT instantiation: nothing to apply to x
         e = set_max_dynamic_lds(reinterpret_cast<const void*>(&conv_wino_dw_kernel<false, false, false, true>), lds_attr);
         if (e != hipSuccess) return (int)e;
         hipLaunchKernelGGL((conv_wino_dw_kernel<false, false, false, true>), dim3(nwg), dim3(512), lds, st, a);

@@ -77,58 +77,31 @@ class _Act(object):
         self.z, self.ss, self.relu, self.r, self.r_ss, self.r_relu = z, ss, relu, r, r_ss, r_relu
 
 
-def _packed_weights(owner, conv):
-    """B-operand stream of a conv for the matrix-core kernels, re-packed only when its weight changes."""
+# kind -> packer(ops, contiguous weight) -> stream.  ops.<name> is looked up when the packer runs, never bound here.
+_PACKERS = {
+    "taps": lambda ops, w: ops.conv_pack_weights(w),         # csrc/conv2d.hip: B-operand stream of the direct / 1x1 forms
+    "s2": lambda ops, w: ops.conv_s2_pack(w),                # a stride-2 3x3 conv in its space-to-depth form
+    # csrc/wino_pc.hip: U = G g G^T per depth tap; a 32-output 2-D layer takes the kernel's HALF form (upper 32 columns zero)
+    "pc": lambda ops, w: ops.conv_wino_pack32(w) if w.shape[0] == 32 and w.dim() == 4 else ops.conv_wino_pack(w),
+    "dw": lambda ops, w: ops.conv_wino_dw_pack(w),           # csrc/wino_dw.hip: Winograd along depth as well
+    "dw4": lambda ops, w: ops.conv_wino_dw4_pack(w),         # csrc/wino_dw4.hip: F(4,3) along depth
+    "direct": lambda ops, w: ops.conv3d_pack_weights(w),     # csrc/conv3d.hip
+    "cout1": lambda ops, w: w[0].reshape(w.shape[1], 27).t().contiguous(),   # the K-Net's 64 -> 1 layer: [27, Cin] tap-major
+}
+
+
+def _packed(owner, conv, kind, mult=1.0):
+    """Weight stream of `conv` for the kernel family `kind` (_PACKERS), of mult * w (mult = 2^k: the clamped-FMA forms of wino_dw.hip /
+    wino_dw4.hip, whose input arrives scaled by 2^-k); cached on `owner`, re-packed only when the weight changes."""
     from . import ops
     cache = owner.__dict__.setdefault("_wp_cache", {})
     w = conv.weight
-    key = (w.data_ptr(), w._version, str(w.device))
-    hit = cache.get(id(conv))
-    if hit is None or hit[0] != key:
-        hit = (key, ops.conv_pack_weights(w.detach().contiguous()))
-        cache[id(conv)] = hit
-    return hit[1]
-
-
-def _packed_wino(owner, conv):
-    """Winograd-domain weight stream U = G g G^T of a 3x3(x3) conv for csrc/wino_pc.hip, re-packed only when its weight changes."""
-    from . import ops
-    cache = owner.__dict__.setdefault("_wp_cache", {})
-    w = conv.weight
-    key = (w.data_ptr(), w._version, str(w.device), "wino")
-    hit = cache.get(("wino", id(conv)))
-    if hit is None or hit[0] != key:
-        hit = (key, ops.conv_wino_pack32(w.detach().contiguous()) if w.shape[0] == 32 and w.dim() == 4 else ops.conv_wino_pack(w.detach().contiguous()))
-        cache[("wino", id(conv))] = hit
-    return hit[1]
-
-
-def _packed_wino_dw(owner, conv, mult=1.0):
-    """Weight stream of csrc/wino_dw.hip (Winograd along depth as well): U_t = sum_kd G[t][kd] (G g_kd G^T), of mult * w
-    (mult = 2^k: the clamped-FMA form of the kernel, whose input arrives scaled by 2^-k)."""
-    from . import ops
-    cache = owner.__dict__.setdefault("_wp_cache", {})
-    w = conv.weight
-    key = (w.data_ptr(), w._version, str(w.device), "wino_dw", float(mult))
-    hit = cache.get(("wino_dw", id(conv)))
+    key = (w.data_ptr(), w._version, str(w.device), float(mult))
+    hit = cache.get((kind, id(conv)))
     if hit is None or hit[0] != key:
         wc = w.detach().contiguous()
-        hit = (key, ops.conv_wino_dw_pack(wc if mult == 1.0 else wc * float(mult)))
-        cache[("wino_dw", id(conv))] = hit
-    return hit[1]
-
-
-def _packed_wino_dw4(owner, conv, mult=1.0):
-    """Weight stream of csrc/wino_dw4.hip (F(4,3) along depth on top of the in-plane Winograd form), of mult * w."""
-    from . import ops
-    cache = owner.__dict__.setdefault("_wp_cache", {})
-    w = conv.weight
-    key = (w.data_ptr(), w._version, str(w.device), "wino_dw4", float(mult))
-    hit = cache.get(("wino_dw4", id(conv)))
-    if hit is None or hit[0] != key:
-        wc = w.detach().contiguous()
-        hit = (key, ops.conv_wino_dw4_pack(wc if mult == 1.0 else wc * float(mult)))
-        cache[("wino_dw4", id(conv))] = hit
+        hit = (key, _PACKERS[kind](ops, wc if mult == 1.0 else wc * float(mult)))
+        cache[(kind, id(conv))] = hit
     return hit[1]
 
 
@@ -145,19 +118,6 @@ def _relu_unit(owner, bn, count):
     if hit is None or hit[0] != key:
         hit = (key, ops.relu_unit(bn.weight, bn.bias, count))
         cache[("unit", id(bn))] = hit
-    return hit[1]
-
-
-def _packed_s2(owner, conv):
-    """Weight stream of a stride-2 3x3 conv in its space-to-depth form (ops.conv_s2_pack), re-packed only when the weight changes."""
-    from . import ops
-    cache = owner.__dict__.setdefault("_wp_cache", {})
-    w = conv.weight
-    key = (w.data_ptr(), w._version, str(w.device), "s2")
-    hit = cache.get(("s2", id(conv)))
-    if hit is None or hit[0] != key:
-        hit = (key, ops.conv_s2_pack(w.detach().contiguous()))
-        cache[("s2", id(conv))] = hit
     return hit[1]
 
 
@@ -221,25 +181,45 @@ def check_status(device):
                          "the convolution epilogues has no correct digit left); the frame's outputs are invalid" % n)
 
 
-def _bn_scale_shift(bn, stats, count, cm=False):
+def _bn_batch_args(bn, host_counter=False):
+    """(momentum, running_mean | None, running_var | None, batches_tracked | None) of a norm in batch-statistics mode (train mode, or
+    no running statistics) for the kernel that computes them, which also updates the running statistics it is handed.  The counter
+    is handed over too (the kernel increments it: an ATen launch less per layer) unless momentum is None — a cumulative average,
+    whose factor needs the counter's value on the host — or the kernel takes none (host_counter): then it is bumped here."""
+    upd = bn.training and bn.track_running_stats
+    nbt = None
+    if upd and (host_counter or bn.momentum is None):
+        bn.num_batches_tracked += 1
+    elif upd:
+        nbt = bn.num_batches_tracked
+    momentum = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+    return momentum, (bn.running_mean if upd else None), (bn.running_var if upd else None), nbt
+
+
+def _bn_eval_affine(bn, detach=True):
+    """(scale [C], shift [C]) of a norm on its running statistics (eval mode): y = x * scale + shift."""
+    sc = torch.rsqrt(bn.running_var + bn.eps)
+    if not bn.affine:
+        return sc, -bn.running_mean * sc
+    w, b = (bn.weight.detach(), bn.bias.detach()) if detach else (bn.weight, bn.bias)
+    sc = w * sc
+    return sc, b - bn.running_mean * sc
+
+
+_FINALISERS = {"rows": "bn_finalize", "cm": "bn_finalize_cm", "rows3d": "bn3d_finalize"}
+
+
+def _bn_scale_shift(bn, stats, count, layout="rows"):
     """(scale, shift) [C,2] of a BatchNorm: batch statistics from the conv epilogue's partials in train mode (the
     reference never leaves it) incl. the running-statistics side effect; running statistics in eval mode.
-    cm: the partials are column-major [2C, rows] (the Winograd kernel's), not [workgroups, 2C]."""
+    layout of the partials: "rows" [workgroups, 2C] (conv2d.hip), "cm" column-major [2C, rows] (the Winograd kernels),
+    "rows3d" [workgroups, 128] (conv3d.hip)."""
     from . import ops
-    if bn.training or not bn.track_running_stats:
-        upd = bn.training and bn.track_running_stats
-        nbt = None
-        if upd and bn.momentum is None:           # cumulative average: the factor needs the counter's value on the host
-            bn.num_batches_tracked += 1
-        elif upd:
-            nbt = bn.num_batches_tracked          # incremented by the finaliser itself (an ATen launch less per layer)
-        momentum = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
-        fin = ops.bn_finalize_cm if cm else ops.bn_finalize
-        return fin(stats, count, bn.weight.detach(), bn.bias.detach(), bn.eps, momentum,
-                   bn.running_mean if upd else None, bn.running_var if upd else None, status=status_word(stats.device),
-                   batches_tracked=nbt)
-    sc = bn.weight.detach() * torch.rsqrt(bn.running_var + bn.eps)
-    return torch.stack((sc, bn.bias.detach() - bn.running_mean * sc), dim=1).contiguous()
+    if _needs_stats(bn):
+        momentum, rm, rv, nbt = _bn_batch_args(bn)
+        return getattr(ops, _FINALISERS[layout])(stats, count, bn.weight.detach(), bn.bias.detach(), bn.eps, momentum, rm, rv,
+                                                 status=status_word(stats.device), batches_tracked=nbt)
+    return torch.stack(_bn_eval_affine(bn), dim=1).contiguous()
 
 
 def _bn_scale_shift_small(bns, zs):
@@ -249,28 +229,12 @@ def _bn_scale_shift_small(bns, zs):
     still; E[y^2] - mean^2 has no digit left there (the collapse guard of _bn_scale_shift would raise), the reference does not
     fail, and neither does this.  Eval mode: the running statistics, as _bn_scale_shift."""
     from . import ops
-    out = [None] * len(bns)
-    live = [k for k, bn in enumerate(bns) if _needs_stats(bn)]
-    for k, bn in enumerate(bns):
-        if k not in live:
-            out[k] = _bn_scale_shift(bn, None, 0)
+    out = [None if _needs_stats(bn) else _bn_scale_shift(bn, None, 0) for bn in bns]
+    live = [k for k, ss in enumerate(out) if ss is None]
     if live:
-        eps, mom, rms, rvs, nbts = [], [], [], [], []
-        for k in live:
-            bn = bns[k]
-            upd = bn.training and bn.track_running_stats
-            nbt = None
-            if upd and bn.momentum is None:       # cumulative average: the factor needs the counter's value on the host
-                bn.num_batches_tracked += 1
-            elif upd:
-                nbt = bn.num_batches_tracked      # incremented by the kernel itself
-            eps.append(bn.eps)
-            mom.append(bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked))
-            rms.append(bn.running_mean if upd else None)
-            rvs.append(bn.running_var if upd else None)
-            nbts.append(nbt)
+        mom, rms, rvs, nbts = zip(*[_bn_batch_args(bns[k]) for k in live])
         sss = ops.bn_small_stats([zs[k] for k in live], [bns[k].weight.detach() for k in live], [bns[k].bias.detach() for k in live],
-                             eps, mom, rms, rvs, nbts)
+                                 [bns[k].eps for k in live], list(mom), list(rms), list(rvs), list(nbts))
         for k, ss in zip(live, sss):
             out[k] = ss
     return out
@@ -414,11 +378,11 @@ class PSMFeatures(_PackedWeightsMixin, nn.Module):
         wino = (mfma and conv.in_channels % 32 == 0 and ((d in (1, 2) and conv.out_channels % 64 == 0) or (d == 1 and conv.out_channels == 32))
                 and ops.conv_wino_supported(a.z.shape[0], a.z.shape[1], a.z.shape[2], conv.in_channels, conv.out_channels, 1))
         if wino:
-            z, st, mat = ops.conv_wino(a.z, _packed_wino(self, conv), conv.out_channels, 1, d, x_ss=a.ss, x_relu=a.relu,
+            z, st, mat = ops.conv_wino(a.z, _packed(self, conv, "pc"), conv.out_channels, 1, d, x_ss=a.ss, x_relu=a.relu,
                                        res=a.r, res_ss=a.r_ss, res_relu=a.r_relu, materialize=materialize,
                                        want_stats=_needs_stats(bn))
         elif mfma:
-            z, st, mat = ops.conv2d(a.z, _packed_weights(self, conv), conv.out_channels, d, x_ss=a.ss, x_relu=a.relu,
+            z, st, mat = ops.conv2d(a.z, _packed(self, conv, "taps"), conv.out_channels, d, x_ss=a.ss, x_relu=a.relu,
                                     res=a.r, res_ss=a.r_ss, res_relu=a.r_relu, materialize=materialize,
                                     want_stats=_needs_stats(bn))
         else:
@@ -427,13 +391,13 @@ class PSMFeatures(_PackedWeightsMixin, nn.Module):
             s2 = (conv.kernel_size == (3, 3) and conv.stride == (2, 2) and conv.padding == (1, 1) and d == 1
                   and mat.shape[1] % 2 == 0 and mat.shape[2] % 2 == 0 and conv.out_channels in (32, 64))
             if s2:   # stride 2 = a 2x2-window convolution on the space-to-depth image of the input
-                z, st = ops.conv2d_taps(ops.space_to_depth2(mat), _packed_s2(self, conv), conv.out_channels, 4,
+                z, st = ops.conv2d_taps(ops.space_to_depth2(mat), _packed(self, conv, "s2"), conv.out_channels, 4,
                                         want_stats=_needs_stats(bn))
             else:
                 raise _no_kernel("feature CNN layer %d -> %d, kernel %s, stride %s, dilation %d on a %d x %d map" % (
                     conv.in_channels, conv.out_channels, tuple(conv.kernel_size), tuple(conv.stride), d, mat.shape[1], mat.shape[2]))
         count = z.shape[0] * z.shape[1] * z.shape[2]
-        return _Act(z, _bn_scale_shift(bn, st, count, cm=wino), relu), mat
+        return _Act(z, _bn_scale_shift(bn, st, count, "cm" if wino else "rows"), relu), mat
 
     def _pointwise_cl(self, conv, m, stride=1, want_stats=False):
         """1x1 convolution on a materialised channels-last tensor: the 1-tap form of csrc/conv2d.hip [+ statistics partials]."""
@@ -442,7 +406,7 @@ class PSMFeatures(_PackedWeightsMixin, nn.Module):
         if C % 16 != 0 or conv.out_channels not in (32, 64, 128) or H % stride or W % stride:
             raise _no_kernel("1x1 layer %d -> %d, stride %d on a %d x %d map" % (C, conv.out_channels, stride, H, W))
         # a strided shortcut (psm_submodule.py:127-131) reads every stride-th pixel inside the kernel: no gather pass
-        return ops.conv2d_taps(m.contiguous(), _packed_weights(self, conv), conv.out_channels, 1, want_stats=want_stats, stride=stride)
+        return ops.conv2d_taps(m.contiguous(), _packed(self, conv, "taps"), conv.out_channels, 1, want_stats=want_stats, stride=stride)
 
     def _pointwise_bn_cl(self, seq, m, stride=1):
         """1x1 Sequential(conv, bn) on a materialised channels-last tensor: the 1-tap form of csrc/conv2d.hip + statistics."""
@@ -478,7 +442,7 @@ class PSMFeatures(_PackedWeightsMixin, nn.Module):
             raise _no_kernel("image %d x %d: the plane-sweep grid is the image / 4 (models/basic.py:254-263), both sides must be multiples of 4"
                              % (x.shape[2], x.shape[3]))
         # 3 -> 32, stride 2: the image as a 12(+4)-channel space-to-depth tensor, then a 2x2-window convolution
-        z, st = ops.conv2d_taps(ops.space_to_depth2(x.contiguous(), nchw=True), _packed_s2(self, conv), conv.out_channels, 4,
+        z, st = ops.conv2d_taps(ops.space_to_depth2(x.contiguous(), nchw=True), _packed(self, conv, "s2"), conv.out_channels, 4,
                                 want_stats=_needs_stats(bn))
         a = _Act(z, _bn_scale_shift(bn, st, z.numel() // z.shape[-1]), True)
         for i in (2, 4):
@@ -530,7 +494,7 @@ class PSMFeatures(_PackedWeightsMixin, nn.Module):
         if head.out_channels not in (32, 64, 128):
             raise _no_kernel("feature_dim %d (1x1 head): 32, 64 or 128" % head.out_channels)
         # 1x1 head; BatchNorm + ReLU of lastconv[0] in its loader
-        feat, _ = ops.conv2d_taps(y.z, _packed_weights(self, head), head.out_channels, 1, x_ss=y.ss, x_relu=True, want_stats=False)
+        feat, _ = ops.conv2d_taps(y.z, _packed(self, head, "taps"), head.out_channels, 1, x_ss=y.ss, x_relu=True, want_stats=False)
         return half, feat
 
     def forward(self, x):
@@ -610,45 +574,11 @@ class KalmanGainNet(_PackedWeightsMixin, nn.Module):
         seq.append(self.classify[0])
         return [(m[0], m[1]) for m in seq] + [(self.classify[2], None)]
 
-    def _packed(self, conv):
-        """B-operand stream of a conv, re-packed only when its weight changes."""
-        from . import ops
-        cache = self.__dict__.setdefault("_wp_cache", {})
-        w = conv.weight
-        key = (w.data_ptr(), w._version, str(w.device))
-        hit = cache.get(id(conv))
-        if hit is None or hit[0] != key:
-            if conv.out_channels == 1:
-                packed = w.detach()[0].reshape(w.shape[1], 27).t().contiguous()  # [27, Cin] tap-major
-            else:
-                packed = ops.conv3d_pack_weights(w.detach().contiguous())
-            hit = (key, packed)
-            cache[id(conv)] = hit
-        return hit[1]
-
-    def _bn_scale_shift(self, bn, stats, count, cm=False):
-        """(scale, shift) of a BatchNorm3d: batch statistics in train mode (the reference never leaves it,
-        SURVEY §0.2) incl. the running-statistics side effect; running statistics in eval mode.
-        cm: column-major partials [128, tiles] of the Winograd kernel instead of [workgroups, 128]."""
-        from . import ops
-        use_batch = bn.training or not bn.track_running_stats
-        if use_batch:
-            upd = bn.training and bn.track_running_stats
-            nbt = None
-            if upd and bn.momentum is None:
-                bn.num_batches_tracked += 1
-            elif upd:
-                nbt = bn.num_batches_tracked      # incremented by the finaliser itself
-            momentum = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
-            fin = ops.bn_finalize_cm if cm else ops.bn3d_finalize
-            return fin(stats, count, bn.weight.detach(), bn.bias.detach(), bn.eps, momentum,
-                       bn.running_mean if upd else None, bn.running_var if upd else None, status=status_word(stats.device),
-                       batches_tracked=nbt)
-        sc = bn.weight.detach() * torch.rsqrt(bn.running_var + bn.eps)
-        return torch.stack((sc, bn.bias.detach() - bn.running_mean * sc), dim=1).contiguous()
-
-    _depth_f43_cin = (16, 64)   # input widths that take the F(4,3) form (the 16 -> 64 first layer: 0.62 -> 0.54 ms at config B)
-    _depth_f43 = True           # the 64 -> 64 layers on csrc/wino_dw4.hip where D % 4 == 0 (False: wino_dw.hip, the A/B and the training path's form)
+    # Candidate kernels of the 3x3x3 layers per input width, in order of preference (ops.conv3d_kernel holds the table).  The A/B switches
+    # are edits of these tuples: tools/knet_ab.py drops "dw4" (every layer on wino_dw.hip, the form of round 5), for all layers or for the
+    # 16 -> 64 first layer alone (0.62 -> 0.54 ms at config B with it)
+    kernels = {16: ("dw4", "dw", "pc", "direct"), 64: ("dw4", "dw", "pc", "direct")}
+    _GENERATIONS = {None: None, "wino_pc": ("pc", "direct"), "direct": ("direct",)}   # forward_channels_last(generation=): tests only
     _split_residual = True      # measured (tools/knet_ab.py, NO_SPLIT=1): K-Net 25.37 -> 24.67 ms at config B when introduced, 22.74 -> 22.40 after the shared strips; identical bits
 
     def forward_channels_last(self, vol, generation=None):
@@ -659,29 +589,30 @@ class KalmanGainNet(_PackedWeightsMixin, nn.Module):
             c0 = relu(bn(conv(relu(bn(conv(vol))))))
             c_i = bn(conv(relu(bn(conv(c_{i-1}))))) + c_{i-1}     i = 1..4
             gain = conv(relu(bn(conv(c4))))
-        The 3x3x3 layers run on wino_dw.hip (Winograd in all three dimensions: F(2,3) along depth on top of the in-plane
-        F(2x2,3x3), 8 multiplies per output voxel) where the grid is whole 8x16 tiles and D is even — every configuration of
-        the path —, on wino_pc.hip (12 multiplies) where only that fits, on conv3d.hip (direct, 27) otherwise.
+        The 3x3x3 layers run on the first of wino_dw4.hip (D % 4 == 0), wino_dw.hip (D even) — both where the grid is whole 8x16
+        tiles: every configuration of the path —, wino_pc.hip and conv3d.hip (direct) that takes the grid (ops.conv3d_kernel).
         generation: None = that choice; "wino_pc" / "direct" = start the choice at that kernel (tests compare the kernels on
         the whole stack; nothing in the package passes it)."""
         from . import ops
         if self.if_normalize or self.up_sample_ratio is not None:
             raise NotImplementedError("if_normalize / up_sample_ratio are never enabled by the reference scripts")
-        if generation not in (None, "wino_pc", "direct"):
+        if generation not in self._GENERATIONS:
             raise ValueError("generation: None | 'wino_pc' | 'direct'")
         D, H, W, C = vol.shape
         if C != self.in_channels:
             raise AssertionError("Input volume should have correct # of channels !")
         L = self._layers()
         count = D * H * W
-        need_stats = lambda bn: bn.training or not bn.track_running_stats
+
+        def choose(i, fused_res=False):
+            conv = L[i][0]
+            cands = self._GENERATIONS[generation] or self.kernels.get(conv.in_channels, ("direct",))
+            if fused_res:                       # wino_dw4.hip has no residual form
+                cands = tuple(k for k in cands if k != "dw4")
+            return ops.conv3d_kernel(D, H, W, conv.in_channels, conv.out_channels, cands)
 
         def run(i, x, x_ss, x_relu, res=None, materialize=False):
             conv, bn = L[i]
-            cm = False
-            # relu(bn(previous output)) as a clamped FMA (wino_dw.hip CLAMP): the previous layer's BatchNorm bounds its output
-            unit = _relu_unit(self, L[i - 1][1], count) if (i > 0 and x_ss is not None and x_relu and res is None and not materialize
-                                                              and generation is None) else 0.0
             if res is not None and self._split_residual:
                 # the residual layers as TWO launches: in = bn(x) + res materialised by one HBM-bound pass (nrgbd_nhwc_act), then the
                 # plain form of the convolution on it.  In the fused form the producers of wino_dw.hip load and add the second
@@ -692,42 +623,42 @@ class KalmanGainNet(_PackedWeightsMixin, nn.Module):
                 x = ops.nhwc_act(x, x_ss, x_relu, r, r_ss, r_relu)
                 y, ss, _ = run(i, x, None, False)
                 return y, ss, x
-            if (generation is None and self._depth_f43 and conv.in_channels in self._depth_f43_cin and conv.out_channels == 64 and res is None
-                    and ops.conv_wino_dw4_supported(D, H, W, conv.in_channels, 64)):
-                # the ten 64 -> 64 layers with F(4,3) along depth (csrc/wino_dw4.hip: 6 instead of 8 multiplies per output voxel).  Its two
-                # input forms are x as it is and relu(bn(x)); a layer that also has to KEEP its activated input (dres1.0) materialises it
-                # with one HBM-bound pass first, like the residual layers
-                if materialize:
-                    x = ops.nhwc_act(x, x_ss, x_relu)
-                    y, st = ops.conv_wino_dw4(x, _packed_wino_dw4(self, conv), 64, want_stats=need_stats(bn))
-                    return y, self._bn_scale_shift(bn, st, count, cm=True), x
-                y, st = ops.conv_wino_dw4(x, _packed_wino_dw4(self, conv, 1.0 / unit if unit else 1.0), 64, x_ss=x_ss, x_relu=x_relu,
-                                          want_stats=need_stats(bn), x_unit=unit)
-                mat, cm = None, True
-            elif (generation is None and conv.in_channels in (16, 64) and conv.out_channels == 64
-                    and ops.conv_wino_dw_supported(D, H, W, conv.in_channels, 64)):
-                y, st, mat = ops.conv_wino_dw(x, _packed_wino_dw(self, conv, 1.0 / unit if unit else 1.0), 64, x_ss=x_ss, x_relu=x_relu,
-                                              res=res, materialize=materialize, want_stats=need_stats(bn), x_unit=unit)
-                cm = True
-            elif generation != "direct" and (conv.in_channels == 64 or (conv.in_channels == 16 and res is None)) \
-                    and ops.conv_wino_supported(D, H, W, conv.in_channels, 64, 3):
-                # 64 -> 64 (12 stages per tile) and the first layer 16 -> 64 (3 stages: the odd-stage-count instantiation)
-                y, st, mat = ops.conv_wino(x, _packed_wino(self, conv), 64, 3, x_ss=x_ss, x_relu=x_relu, res=res,
-                                           materialize=materialize, want_stats=need_stats(bn))
-                cm = True
+            # (1) the kernel
+            kind = choose(i, res is not None)
+            # (2) wino_dw4.hip takes x as it is or relu(bn(x)): a layer that also has to KEEP its activated input (dres1.0) materialises
+            # it with one HBM-bound pass first, like the residual layers; the other kernels write it from their loaders
+            kept = None
+            if kind == "dw4" and materialize:
+                x = kept = ops.nhwc_act(x, x_ss, x_relu)
+                x_ss, x_relu, materialize = None, False, False
+            # (3) the launch.  relu(bn(previous output)) as a clamped FMA (the CLAMP forms of wino_dw.hip / wino_dw4.hip): the previous
+            # layer's BatchNorm bounds its output, the weight stream carries the inverse of the unit
+            unit = _relu_unit(self, L[i - 1][1], count) if (kind in ("dw4", "dw") and i > 0 and x_ss is not None and x_relu and res is None
+                                                              and not materialize) else 0.0
+            wp = _packed(self, conv, kind, 1.0 / unit if unit else 1.0)
+            if kind == "dw4":
+                y, st = ops.conv_wino_dw4(x, wp, 64, x_ss=x_ss, x_relu=x_relu, want_stats=_needs_stats(bn), x_unit=unit)
+            elif kind == "dw":
+                y, st, kept = ops.conv_wino_dw(x, wp, 64, x_ss=x_ss, x_relu=x_relu, res=res, materialize=materialize,
+                                               want_stats=_needs_stats(bn), x_unit=unit)
+            elif kind == "pc":      # 64 -> 64 (12 stages per tile) and the first layer 16 -> 64 (3 stages: the odd-stage-count instantiation)
+                y, st, kept = ops.conv_wino(x, wp, 64, 3, x_ss=x_ss, x_relu=x_relu, res=res, materialize=materialize,
+                                            want_stats=_needs_stats(bn))
             else:
-                y, st, mat = ops.conv3d(x, self._packed(conv), x_ss=x_ss, x_relu=x_relu, res=res,
-                                        materialize=materialize, want_stats=need_stats(bn))
-            return y, self._bn_scale_shift(bn, st, count, cm=cm), mat
+                y, st, kept = ops.conv3d(x, wp, x_ss=x_ss, x_relu=x_relu, res=res, materialize=materialize, want_stats=_needs_stats(bn))
+            # (4) the layer's BatchNorm from the epilogue's partials
+            return y, _bn_scale_shift(bn, st, count, "rows3d" if kind == "direct" else "cm"), kept
 
         z, ss, _ = run(0, vol, None, False)                       # dres0.0
         z, ss, _ = run(1, z, ss, True)                            # dres0.2   in = relu(bn(z))
         # dres1.0: in = c0 = relu(bn(z)), which is also the first residual.  Where the layer has a clamped-FMA form that costs what the
         # plain one costs (wino_dw4.hip, wino_dw.hip) c0 is not materialised: the layer reads the raw tensor with its (scale, shift), and
         # the first residual pass (dres2.0's input) applies the same FMA + max to it while it adds — the same roundings, one 1.6 GB pass
-        # (0.25 ms at config B) less
-        lazy_c0 = (generation is None and self._split_residual and L[2][0].in_channels == 64 and L[2][0].out_channels == 64
-                   and (ops.conv_wino_dw4_supported(D, H, W, 64, 64) if self._depth_f43 else ops.conv_wino_dw_supported(D, H, W, 64, 64)))
+        # (0.25 ms at config B) less.  Only where dres1.0 runs on its FIRST candidate: at even D with D % 4 != 0 (wino_dw.hip behind
+        # wino_dw4.hip) the layer still writes c0 from its loader — dropping that too is one edit here (choose(2) in ("dw4", "dw")), to be
+        # made together with a bit comparison against this form at such a depth
+        first = (self._GENERATIONS[generation] or self.kernels.get(64, ("direct",)))[0]
+        lazy_c0 = self._split_residual and first in ("dw4", "dw") and choose(2) == first
         if lazy_c0:
             skip = (z, ss, True)
             z, ss, _ = run(2, z, ss, True)
@@ -738,8 +669,7 @@ class KalmanGainNet(_PackedWeightsMixin, nn.Module):
             z, ss, skip = run(i, z, ss, False, res=skip, materialize=True)
             z, ss, _ = run(i + 1, z, ss, True)
         z, ss, _ = run(10, z, ss, False, res=skip)                # classify.0: in = c4
-        conv, _ = L[11]
-        return ops.conv3d_cout1(z, self._packed(conv), x_ss=ss, x_relu=True)  # classify.2
+        return ops.conv3d_cout1(z, _packed(self, L[11][0], "cout1"), x_ss=ss, x_relu=True)  # classify.2
 
     def forward_channels_last_autograd(self, vol, grad_channel=None):
         """Training path: same graph on channels-last activations with the convolutions (forward, data gradient and

@@ -494,27 +494,33 @@ def conv3d(x, w_packed, x_ss=None, x_relu=False, res=None, res_ss=None, res_relu
     return y, stats, mat
 
 
+def _wino_pack(w, transposed, name, points):
+    """Shared body of the three Winograd weight packers.  points: transform points along depth of the stream (4: wino_dw.hip,
+    6: wino_dw4.hip), None: one 2-D stream per depth tap (wino_pc.hip: kd = 3, or kd = 1 for a [Cout, Cin, 3, 3] weight).
+    transposed: False = the forward stream, True = the data-gradient stream (w is the FORWARD weight [Cin', Cout', ...]: channel axes
+    swapped, taps flipped), 2 = both in one launch: a buffer of twice the size, forward half first (ops.conv_wino_pack_both)."""
+    w = _need(w, "w")
+    if points is None and w.dim() == 4:
+        w = w[:, :, None]
+    if w.dim() != 5 or tuple(w.shape[3:]) != (3, 3) or w.shape[2] not in ((1, 3) if points is None else (3,)):
+        raise ValueError("%s expects [Cout, Cin, %s3, 3, 3], got %s" % (name, "(3,) " if points is None else "", tuple(w.shape)))
+    Cout, Cin = (w.shape[1], w.shape[0]) if transposed is True or transposed == 1 else w.shape[:2]
+    if Cout % 64 or Cin % 16 or (transposed == 2 and Cin % 64):
+        raise ValueError("%s: Cout %% 64 and Cin %% 16 required, got Cout=%d Cin=%d" % (name, Cout, Cin))
+    kd = [int(w.shape[2])] if points is None else []          # nrgbd_conv_wino_pack alone takes the tap count
+    wp = torch.empty(Cout * Cin * (points or kd[0]) * 16 * (2 if transposed == 2 else 1), dtype=torch.float32, device=w.device)
+    wc = w.detach().contiguous()
+    with torch.cuda.device(w.device):
+        rc = getattr(_lib.load(), "nrgbd_" + name)(_p(wc), _p(wp), Cin, Cout, *kd, int(transposed), _stream(w))
+    _lib.check(rc, "nrgbd_" + name)
+    return wp
+
+
 def conv_wino_pack(w, transposed=False):
     """w [Cout, Cin, 3, 3, 3] (kd = 3) or [Cout, Cin, 3, 3] (kd = 1) -> Winograd-domain B-operand stream of nrgbd_conv_wino_f32:
     U = G g G^T over (ky, kx) in float64, rounded once to fp32, laid out [cg][stage = cb*kd + depth tap][xi = 4*xi_y + xi_x]
-    [wave][lane = kq*16 + j][e] with ci = cb*16 + 4*kq + e and co = cg*64 + 16*wave + j.
-    transposed: w is the FORWARD weight [Cin', Cout', ...] of a layer and the stream is the one of its data gradient (channel
-    axes swapped, taps flipped) — the kernel then maps dL/dy [.., Cin' of this call = the layer's Cout] to dL/dx."""
-    w = _need(w, "w")
-    if w.dim() == 4:
-        w = w[:, :, None]
-    if w.dim() != 5 or tuple(w.shape[3:]) != (3, 3) or w.shape[2] not in (1, 3):
-        raise ValueError("conv_wino_pack expects [Cout, Cin, (3,) 3, 3], got %s" % (tuple(w.shape),))
-    Cout, Cin, KD = (w.shape[1], w.shape[0], w.shape[2]) if transposed is True or transposed == 1 else w.shape[:3]
-    if Cout % 64 or Cin % 16 or (transposed == 2 and Cin % 64):
-        raise ValueError("conv_wino_pack: Cout %% 64 and Cin %% 16 required, got Cout=%d Cin=%d" % (Cout, Cin))
-    # transposed = 2: both streams in one launch -> a buffer of twice the size, forward half first (training: ops.conv_wino_pack_both)
-    wp = torch.empty(Cout * Cin * KD * 16 * (2 if transposed == 2 else 1), dtype=torch.float32, device=w.device)
-    wc = w.detach().contiguous()
-    with torch.cuda.device(w.device):
-        rc = _lib.load().nrgbd_conv_wino_pack(_p(wc), _p(wp), Cin, Cout, KD, int(transposed), _stream(w))
-    _lib.check(rc, "nrgbd_conv_wino_pack")
-    return wp
+    [wave][lane = kq*16 + j][e] with ci = cb*16 + 4*kq + e and co = cg*64 + 16*wave + j.  transposed: see _wino_pack."""
+    return _wino_pack(w, transposed, "conv_wino_pack", None)
 
 
 def conv_wino_pack_both(w, dw=False):
@@ -586,19 +592,8 @@ def conv_wino(x, w_wino, Cout, kd, dilation=1, x_ss=None, x_relu=False, res=None
 
 def conv_wino_dw_pack(w, transposed=False):
     """w [Cout, Cin, 3, 3, 3] -> weight stream of nrgbd_conv_wino_dw_f32 (Winograd in depth too): U_t = sum_kd G[t][kd] (G g_kd G^T)
-    in float64, rounded once, laid out [cg][stage = t*(Cin/16) + cb][xi][wave][lane = kq*16 + j][e]."""
-    w = _need(w, "w")
-    if w.dim() != 5 or tuple(w.shape[2:]) != (3, 3, 3):
-        raise ValueError("conv_wino_dw_pack expects [Cout, Cin, 3, 3, 3], got %s" % (tuple(w.shape),))
-    Cout, Cin = (w.shape[1], w.shape[0]) if transposed is True or transposed == 1 else w.shape[:2]
-    if Cout % 64 or Cin % 16 or (transposed == 2 and Cin % 64):
-        raise ValueError("conv_wino_dw_pack: Cout %% 64 and Cin %% 16 required, got Cout=%d Cin=%d" % (Cout, Cin))
-    wp = torch.empty(Cout * Cin * 4 * 16 * (2 if transposed == 2 else 1), dtype=torch.float32, device=w.device)
-    wc = w.detach().contiguous()
-    with torch.cuda.device(w.device):
-        rc = _lib.load().nrgbd_conv_wino_dw_pack(_p(wc), _p(wp), Cin, Cout, int(transposed), _stream(w))
-    _lib.check(rc, "nrgbd_conv_wino_dw_pack")
-    return wp
+    in float64, rounded once, laid out [cg][stage = t*(Cin/16) + cb][xi][wave][lane = kq*16 + j][e].  transposed: see _wino_pack."""
+    return _wino_pack(w, transposed, "conv_wino_dw_pack", 4)
 
 
 def conv_wino_dw_pack_reference(w):
@@ -665,21 +660,40 @@ def conv_wino_dw4_supported(N, H, W, Cin, Cout):
     return N % 4 == 0 and N >= 4 and H % 8 == 0 and W % 16 == 0 and Cin % 16 == 0 and Cout % 64 == 0 and H * W * Cin < (1 << 30)
 
 
+def conv3d_kernel(D, H, W, Cin, Cout, candidates):
+    """Which kernel runs a channels-last 3x3x3 layer on a [D, H, W, Cin] input: the first of `candidates`, in order, that takes the
+    shape.  "dw4" = wino_dw4.hip (6 multiplies per output voxel; D % 4 == 0), "dw" = wino_dw.hip (8; D even) — both whole 8x16 tiles
+    —, "pc" = wino_pc.hip (12; any grid), each for 16 or 64 inputs and 64 outputs; "direct" = conv3d.hip (27) takes everything and
+    ends every search.  Pure host code: this is the one place the choice is written down.  Who passes what:
+
+      caller                                      Cin  candidates             why not the full list
+      K-Net inference (KalmanGainNet.kernels)     any  dw4, dw, pc, direct    -
+        ... generation="wino_pc" (tests)          any  pc, direct             compares the kernels on the whole stack
+        ... generation="direct" (tests)           any  direct
+        ... a layer with a fused residual         64   dw, pc, direct         wino_dw4.hip has no residual form (only with
+                                                                              _split_residual off: an A/B)
+      autograd 64 -> 64, both directions          64   dw4, dw, pc, direct    (Conv3dCL.kernels)
+      autograd 16 -> 64 forward                   16   dw4, direct            (Conv3dCL.kernels_first) its 16-input forms of wino_dw /
+                                                                              wino_pc were never timed against the direct kernel
+                                                                              at the training grids: inference takes them, training
+                                                                              does not
+      autograd 16 -> 64 data gradient             64   dw4, dw, direct        (Conv3dCL.kernels_first_dgrad) the layer zero-padded to
+                                                                              64 -> 64 on dL/dy; wino_pc.hip was never timed here
+    The A/B switches are edits of those tuples (tools/knet_ab.py drops "dw4")."""
+    takes = {"dw4": conv_wino_dw4_supported, "dw": conv_wino_dw_supported, "pc": lambda *shape: conv_wino_supported(*shape, 3)}
+    for kind in candidates:
+        if kind != "direct" and Cout == 64 and Cin in (16, 64) and takes[kind](D, H, W, Cin, Cout):
+            return kind
+        if kind == "direct":
+            break
+    return "direct"
+
+
 def conv_wino_dw4_pack(w, transposed=False):
     """w [Cout, Cin, 3, 3, 3] -> weight stream of nrgbd_conv_wino_dw4_f32 (F(2x2,3x3) in the plane x F(4,3) along depth, points
     0, +-1/2, +-3/2, inf): U_t = sum_kd Gd[t][kd] (G g_kd G^T) in float64, rounded once, phases in execution order t = 1,2,3,4,0,5.
-    transposed: True = the data-gradient stream (transposed + flipped weights), 2 = both streams (forward, then data gradient)."""
-    w = _need(w, "w")
-    if w.dim() != 5 or tuple(w.shape[2:]) != (3, 3, 3):
-        raise ValueError("conv_wino_dw4_pack expects [Cout, Cin, 3, 3, 3], got %s" % (tuple(w.shape),))
-    Cout, Cin = (w.shape[1], w.shape[0]) if transposed is True or transposed == 1 else w.shape[:2]
-    if Cout % 64 or Cin % 16 or (transposed == 2 and Cin % 64):
-        raise ValueError("conv_wino_dw4_pack: Cout %% 64 and Cin %% 16 required, got Cout=%d Cin=%d" % (Cout, Cin))
-    wp = torch.empty(Cout * Cin * 6 * 16 * (2 if transposed == 2 else 1), dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        rc = _lib.load().nrgbd_conv_wino_dw4_pack(_p(w.detach().contiguous()), _p(wp), Cin, Cout, int(transposed), _stream(w))
-    _lib.check(rc, "nrgbd_conv_wino_dw4_pack")
-    return wp
+    transposed: see _wino_pack."""
+    return _wino_pack(w, transposed, "conv_wino_dw4_pack", 6)
 
 
 def conv_wino_dw4(x, w_wino, Cout, x_ss=None, x_relu=False, want_stats=True, x_unit=0.0):

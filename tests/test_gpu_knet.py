@@ -324,6 +324,36 @@ def test_knet_stack_dw_vs_the_other_kernels():
     assert (a - c).abs().max().item() < 2e-4 * max(1.0, a.abs().max().item())
 
 
+@pytest.mark.parametrize("D,kernel", [(8, "dw4"), (6, "dw"), (5, "pc")])
+def test_knet_launches_the_chosen_kernels(D, kernel, monkeypatch):
+    """forward_channels_last at [D, 16, 32, 16] (two 8x16 tiles each way in the plane): the eleven 3x3x3 layers all run on the
+    kernel ops.conv3d_kernel names for the depth, and the stack makes four nhwc_act passes — the inputs of the four residual
+    layers (dres2.0, dres3.0, dres4.0, classify.0).  c0 costs none at any of the depths: wino_dw4.hip reads it lazily (the first
+    residual pass applies its BatchNorm + ReLU), wino_dw.hip and wino_pc.hip write it from their loaders."""
+    from neuralrgbd_amd import nets, ops
+    calls = {}
+
+    def counted(name):
+        fn = getattr(ops, name)
+
+        def wrapper(*a, **k):
+            calls[name] = calls.get(name, 0) + 1
+            return fn(*a, **k)
+        monkeypatch.setattr(ops, name, wrapper)
+    launcher = {"dw4": "conv_wino_dw4", "dw": "conv_wino_dw", "pc": "conv_wino", "direct": "conv3d"}
+    for name in list(launcher.values()) + ["nhwc_act", "conv3d_cout1"]:
+        counted(name)
+    torch.manual_seed(D)
+    net = nets.KalmanGainNet(16, feature_dim=64).to(DEV)
+    vol = torch.randn(D, 16, 32, 16, device=DEV)
+    with torch.no_grad():
+        gain = net.forward_channels_last(vol)
+    assert tuple(gain.shape) == (D, 16, 32) and bool(torch.isfinite(gain).all())
+    ran = {k: calls.get(name, 0) for k, name in launcher.items()}
+    assert ran == {k: (11 if k == kernel else 0) for k in launcher}, ran
+    assert calls.get("nhwc_act", 0) == 4 and calls.get("conv3d_cout1", 0) == 1, calls
+
+
 @pytest.mark.parametrize("shape", [(64, 64, 3, 3), (128, 64, 3, 3), (128, 320 - 64, 3, 3), (64, 64, 3, 3, 3)])
 def test_both_weight_streams_in_one_launch(shape):
     """transposed = 2 of the packing kernels (training): forward and data-gradient streams of a layer written by ONE launch are the

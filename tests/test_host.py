@@ -455,3 +455,32 @@ def test_pack_cache_scopes():
         assert ag._cached(1, ("a", 0), make("q")) == "y" and len(outer) == 3
     assert ag._PACK_CACHE is None
     assert calls == ["x", "x", "y", "k", "k", "t", "u", "w"]
+
+
+def test_conv3d_kernel_choice_table():
+    """ops.conv3d_kernel at named grids for the candidate tuple of every call site.  The expected kernels are literals, worked out
+    from the predicates of the code before the choice had one home (nets.KalmanGainNet.forward_channels_last, autograd.Conv3dCL):
+    wino_dw4.hip needs D % 4 == 0, wino_dw.hip D even, both whole 8x16 tiles; wino_pc.hip takes every grid here."""
+    from neuralrgbd_amd import autograd, nets, ops
+    grids = {"B": (64, 192, 256), "train": (64, 64, 96), "D6": (6, 16, 32), "D5": (5, 16, 32), "H13": (4, 13, 32)}
+    knet, cl = nets.KalmanGainNet, autograd.Conv3dCL
+    assert knet.kernels == {16: ("dw4", "dw", "pc", "direct"), 64: ("dw4", "dw", "pc", "direct")}
+    assert (cl.kernels, cl.kernels_first, cl.kernels_first_dgrad) == (("dw4", "dw", "pc", "direct"), ("dw4", "direct"), ("dw4", "dw", "direct"))
+    table = [   # (who, candidates, Cin values, expected per grid in the order B, train, D6, D5, H13)
+        ("K-Net inference", knet.kernels[64], (16, 64), ("dw4", "dw4", "dw", "pc", "pc")),
+        ("K-Net, generation='wino_pc'", knet._GENERATIONS["wino_pc"], (16, 64), ("pc",) * 5),
+        ("K-Net, generation='direct'", knet._GENERATIONS["direct"], (16, 64), ("direct",) * 5),
+        ("K-Net, fused residual / no dw4 (A/B)", ("dw", "pc", "direct"), (16, 64), ("dw", "dw", "dw", "pc", "pc")),
+        ("autograd 64 -> 64", cl.kernels, (64,), ("dw4", "dw4", "dw", "pc", "pc")),
+        ("autograd 16 -> 64 forward", cl.kernels_first, (16,), ("dw4", "dw4", "direct", "direct", "direct")),
+        ("autograd 16 -> 64 data gradient", cl.kernels_first_dgrad, (64,), ("dw4", "dw4", "dw", "direct", "direct")),
+    ]
+    for who, cands, cins, want in table:
+        for cin in cins:
+            got = tuple(ops.conv3d_kernel(*grids[g], cin, 64, cands) for g in ("B", "train", "D6", "D5", "H13"))
+            assert got == want, (who, cin, got, want)
+    # the direct kernel takes what no Winograd form has (other widths), and ends the search wherever it stands
+    assert ops.conv3d_kernel(64, 192, 256, 32, 64, knet.kernels[64]) == "direct"
+    assert ops.conv3d_kernel(64, 192, 256, 64, 64, ("direct", "dw4")) == "direct"
+    assert ops.conv3d_kernel(64, 192, 256, 64, 64, ()) == "direct"
+

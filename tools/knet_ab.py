@@ -1,6 +1,6 @@
 """The whole K-Net stack (nets.KalmanGainNet.forward_channels_last) at a K-Net grid with the product library or an experimental
-A/B build of it (python -c "from neuralrgbd_amd import build; build.build_variant('noident', ['-DNRGBD_DW_IDENT=0'])"; NRGBD_EXP_LIB=
-its path): run both in one gpurun call to compare on the same chip.  HIP events, steady state."""
+A/B build of it (python -c "from neuralrgbd_amd import build; build.build_variant('serp0', ['-DNRGBD_DW_SERP=0'])"; NRGBD_EXP_LIB=
+its path): run both in one session to compare on the same chip.  HIP events, steady state."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from neuralrgbd_amd import _lib
@@ -9,10 +9,11 @@ if os.environ.get("NRGBD_EXP_LIB"):
 from neuralrgbd_amd import nets
 if os.environ.get("NO_SPLIT"):          # A/B: the residual layers fused (wino_dw RES variants) instead of nhwc_act + the IDENT form
     nets.KalmanGainNet._split_residual = False
-if os.environ.get("NO_D4"):             # A/B: wino_dw.hip (F(2,3) along depth) for the 64 -> 64 layers instead of wino_dw4.hip
-    nets.KalmanGainNet._depth_f43 = False
-if os.environ.get("D4_L0"):             # A/B: the 16 -> 64 first layer on wino_dw4.hip too
-    nets.KalmanGainNet._depth_f43_cin = (16, 64)
+_no_d4 = lambda cands: tuple(k for k in cands if k != "dw4")
+if os.environ.get("NO_D4"):             # A/B: wino_dw.hip (F(2,3) along depth) for every layer instead of wino_dw4.hip
+    nets.KalmanGainNet.kernels = {cin: _no_d4(c) for cin, c in nets.KalmanGainNet.kernels.items()}
+if os.environ.get("NO_D4_L0"):          # A/B: the 16 -> 64 first layer alone on wino_dw.hip
+    nets.KalmanGainNet.kernels = dict(nets.KalmanGainNet.kernels, **{16: _no_d4(nets.KalmanGainNet.kernels[16])})
 if os.environ.get("NO_CLAMP"):            # A/B of the clamped-FMA ReLU form: the plain form everywhere
     nets._relu_unit = lambda owner, bn, count: 0.0
 torch.manual_seed(0)
