@@ -33,59 +33,26 @@
 // wino_pc's three — the third one's 32 KB hold the second stash.  A consumer therefore cannot read the first operand of the
 // next stage before the stage barrier; instead it ARRIVES at the barrier early, as soon as its last LDS operand of the stage is
 // in registers, and reads the next stage's first operand under its own last 8 MFMAs.)
+//
+// In wino_dw.hpp, shared with wino_dw4.hip: the strip / stash / table constants, DwTile + dw_decode<2>, the serpentine order dw_cb
+// (this file's knob: NRGBD_DW_SERP), the weight packer (dw_pack<4>) and the host helpers dw_workgroups / dw_check / dw_unit_ok.
+// Here: the kernel itself — and, still in two copies with wino_dw4.hip, the tile-list split, the table load, the consumers' MFMA
+// stage / plane inverse / statistics and the producers' item map / book / plane transform (wino_dw.hpp says why).
 #include <type_traits>
 
-#include "wino_pc.hpp"
+#include "wino_dw.hpp"
 
 namespace nrgbd {
 
-constexpr int kDwStashWave = 2 * 8 * 64 * 4;   // floats of one consumer wave's stash: [2 output slices][8 words][64 lanes][4]
-constexpr int kDwMaxCin = 512;                 // (scale, shift) tables of x and res live in LDS: 2 x 2 x Cin floats
-constexpr int kDwNBuf = 2;                     // V buffers (wino_pc.hip: 3; the third one's 32 KB hold the second stash here)
-// SHARED strips (round 4): wino_pc.hip's producer wave p loads the four halo rows 2p .. 2p+3 its tile row needs into a PRIVATE strip
-// — 16 rows for a 10-row halo, i.e. every interior row is loaded, activated and published twice.  Here the 10 x 18 halo of a unit is
-// split once over the 256 producer lanes (3 words per lane instead of 5) into a strip all four waves share, published one stage
-// AHEAD: iteration i publishes stage i into strip[i & 1] and transforms stage i - 1 from strip[(i - 1) & 1] (complete since the
-// stage barrier), so the only synchronisation is the barrier the stage has anyway (one more at the start).  Per stage and
-// producer wave: 6 instead of 10 loads, 18 instead of 30 packed activation / combine FMAs, 9 instead of 15 strip accesses.
-constexpr int kDwShRows = kPcTH + 2;                       // halo rows of a tile
-constexpr int kDwShStrip = kDwShRows * kPcRawW * kCB;      // floats of one shared strip: [10 rows][20 pixels][16] = 12.8 KB
-constexpr int kDwShItems = kDwShRows * 18 * 4;             // (row, column, 16-byte word) items of a unit: 720
-constexpr int kDwNPF = 3;                                  // items per producer lane and unit (720 over 256 lanes)
-constexpr int kDwStrips = 2 * kDwShStrip;                  // floats of the strip region
-
-struct DwTile { int z0, y0, x0, cg, row0; };   // row0: statistics row of slice z0 (slice z0 + 1: row0 + 1)
-
-__device__ __forceinline__ DwTile dw_decode(int t, const WinoPcArgs& a) {
-    DwTile r;
-    const int ncg = a.Cout >> 6;
-    const int tiles_x = (a.W + kPcTW - 1) / kPcTW;
-    const int row = t / ncg;
-    r.cg = t - row * ncg;
-    t = row;
-    const int npair = a.N >> 1;
-    const int zp = t % npair; t /= npair;       // depth fastest: list neighbours share three of their four input slices
-    const int tx = t % tiles_x, ty = t / tiles_x;
-    r.z0 = 2 * zp;
-    r.y0 = ty * kPcTH; r.x0 = tx * kPcTW;
-    r.row0 = (ty * tiles_x + tx) * a.N + r.z0;
-    return r;
-}
-
-// Channel block of the i-th stage of phase t: odd phases sweep the blocks backwards (ncb-1 .. 0).  Phases 1 and 2 read the same
-// two slices, phase 0 / 1 and 2 / 3 share one: with every phase sweeping forwards a unit's re-read came Cin/16 stages after its
-// first read, and the 32 workgroups of an XCD stream 1.5 MB (3 MB with a residual operand) per stage through their 4 MB L2 beside
-// the 1 MB weight stream — every re-read missed (profiles/r3_pmc_wino.txt: the residual variant fetched ALL its reads).  Turning
-// round at the phase boundary puts the most recently read units first.
 #ifndef NRGBD_DW_SERP
-#define NRGBD_DW_SERP 1
+#define NRGBD_DW_SERP 1   // 0: experimental A/B builds only (build.build_variant); see dw_cb
 #endif
-__device__ __forceinline__ int dw_cb(int t, int i, int ncb) { return (NRGBD_DW_SERP && (t & 1)) ? ncb - 1 - i : i; }
 
 // slices combined by stage phase t: V_t = d[zA] + sign * d[zB]
 __device__ __forceinline__ int dw_zA(int t) { return t == 0 ? -1 : (t == 2 ? 1 : 0); }   // relative to z0: -1, 0, 1, 0
 __device__ __forceinline__ int dw_zB(int t) { return t == 2 ? 0 : (t == 3 ? 2 : 1); }    //                  1, 1, 0, 2
 
+// RES: a second operand (res) is added after activation.  MAT: the activated input is also written out (a.mat).  MAT is a
 // RES: a second operand (res) is added after activation.  MAT: the activated input is also written out (a.mat).  MAT is a
 // template parameter because of what its stores do to the OTHER variants: with loads and stores of one wave both pending the
 // compiler cannot rely on in-order completion and turns every s_waitcnt on a prefetched register into vmcnt(0) — which also
@@ -154,7 +121,7 @@ __global__ __launch_bounds__(512) void conv_wino_dw_kernel(const WinoPcArgs a) {
         f32x4* stash0 = reinterpret_cast<f32x4*>(stashb + wv * kDwStashWave) + lane;     // slice z0:     word i at stash0[i * 64]
         f32x4* stash1 = stash0 + 8 * 64;                                                  // slice z0 + 1
 
-        DwTile tl = dw_decode(first, a);
+        DwTile tl = dw_decode<2>(first, a);
         const f32x4* wt = wbase + (size_t)tl.cg * wgroup;
         f32x4 Bn[kPcNB], An[2][2];
 #pragma unroll
@@ -170,7 +137,7 @@ __global__ __launch_bounds__(512) void conv_wino_dw_kernel(const WinoPcArgs a) {
 
         for (int it = 0; it < count; ++it) {
             const int tnext = first + (it + 1 < count ? it + 1 : it) * step;
-            const DwTile tn = dw_decode(tnext, a);
+            const DwTile tn = dw_decode<2>(tnext, a);
             const f32x4* wt_next = wbase + (size_t)tn.cg * wgroup;
             const int co = tl.cg * 64 + wv * 16 + jj;
             // one phase = the Cin/16 stages of depth-transform index T (accumulating M_T), then its fold; the four phases are
@@ -178,13 +145,13 @@ __global__ __launch_bounds__(512) void conv_wino_dw_kernel(const WinoPcArgs a) {
             auto phase = [&](auto t_tag) __attribute__((always_inline)) {
                 constexpr int T = decltype(t_tag)::value;
                 for (int cb = 0; cb < ncb; ++cb) {
-                    const int s = T * ncb + dw_cb(T, cb, ncb);          // cb: position in the phase's sweep
+                    const int s = T * ncb + dw_cb(NRGBD_DW_SERP, T, cb, ncb);          // cb: position in the phase's sweep
                     const float* Vc = Vb + buf * kPcV;
                     const int nbuf = buf ^ 1;
                     const float* Vn = Vb + nbuf * kPcV;
                     const f32x4* wcur = wt + (size_t)s * (16 * 256);
-                    const f32x4* wnx = cb + 1 < ncb ? wt + (size_t)(T * ncb + dw_cb(T, cb + 1, ncb)) * (16 * 256)
-                                       : (T < 3 ? wt + (size_t)((T + 1) * ncb + dw_cb(T + 1, 0, ncb)) * (16 * 256) : wt_next);
+                    const f32x4* wnx = cb + 1 < ncb ? wt + (size_t)(T * ncb + dw_cb(NRGBD_DW_SERP, T, cb + 1, ncb)) * (16 * 256)
+                                       : (T < 3 ? wt + (size_t)((T + 1) * ncb + dw_cb(NRGBD_DW_SERP, T + 1, 0, ncb)) * (16 * 256) : wt_next);
                     auto body = [&](auto first_tag) __attribute__((always_inline)) {
                         constexpr bool FIRST = decltype(first_tag)::value;
                         const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
@@ -355,7 +322,7 @@ __global__ __launch_bounds__(512) void conv_wino_dw_kernel(const WinoPcArgs a) {
             }
         };
         struct Regs { f32x4 pre[kDwNPF]; f32x4 prer[RES ? kDwNPF : 1]; f32x4 ss[2]; f32x4 rs[2]; };
-        DwTile tl = dw_decode(first, a), tn = tl;
+        DwTile tl = dw_decode<2>(first, a), tn = tl;
         // raw words of one unit = (slice zrel of stage s, channel block of stage s) -> registers
         auto issue = [&](bool nx, int t, int cb, bool unitB, Regs& r) __attribute__((always_inline)) {
             r.rs[0] = r.rs[1] = f32x4{1.f, 1.f, 0.f, 0.f};
@@ -512,14 +479,14 @@ __global__ __launch_bounds__(512) void conv_wino_dw_kernel(const WinoPcArgs a) {
             int cb = 0, t = 0;
             for (int s = 0; s < NS; ++s) {
                 // the book of the next tile is needed by the refills of the tile's last stage
-                if (s == NS - 1 && has_next) { tn = dw_decode(first + (it + 1) * step, a); setup(tn, nxt_off, nxt_keep, nxt_own); }
+                if (s == NS - 1 && has_next) { tn = dw_decode<2>(first + (it + 1) * step, a); setup(tn, nxt_off, nxt_keep, nxt_own); }
                 raw = rawb + (gi & 1) * kDwShStrip; rawT = rawb + ((gi & 1) ^ 1) * kDwShStrip;
                 const int zA = tl.z0 + dw_zA(t), zB = tl.z0 + dw_zB(t);
                 const bool zinA = zA >= 0, zinB = zB < a.N;       // zA <= z0 + 1 < N and zB >= z0 >= 0 always hold
                 const bool wmat = MAT && t == 1 && tl.cg == 0;    // phase 1 publishes slices z0 (unit A) and z0 + 1 (unit B)
                 const bool nx = s + 1 >= NS;
                 const int cbn = cb + 1 == ncb ? 0 : cb + 1, tnx = nx ? 0 : (cb + 1 == ncb ? t + 1 : t);   // (t, position) of stage s + 1
-                const int cbe = dw_cb(t, cb, ncb), cbne = dw_cb(tnx, cbn, ncb);                            // their channel blocks
+                const int cbe = dw_cb(NRGBD_DW_SERP, t, cb, ncb), cbne = dw_cb(NRGBD_DW_SERP, tnx, cbn, ncb);                            // their channel blocks
                 if constexpr (MAT) {
                     // With materialise stores in the queue the compiler cannot count it (loads and stores of one wave pending =
                     // "may complete out of order" = every wait becomes vmcnt(0)), and the wait for set B would also wait for the
@@ -570,75 +537,16 @@ __global__ __launch_bounds__(512) void conv_wino_dw_kernel(const WinoPcArgs a) {
     }
 }
 
-// w [Cout][Cin][3][3][3] -> U_t = sum_kd Gd[t][kd] (G g_kd G^T) (float64, rounded once) in the kernel's B-operand order
-// [cg][stage = t*ncb + cb][xi][wave][lane = kq*16 + j][e], co = cg*64 + 16*wave + j, ci = cb*16 + 4*kq + e
-__global__ __launch_bounds__(256) void conv_wino_dw_pack_kernel(const float* __restrict__ w, float* __restrict__ wp, int Cin, int Cout,
-                                                                int transposed) {
-    const long total = (long)Cout * Cin * 4 * 16;
-    if (transposed == 2) {     // both streams in one launch (grid.y = 2): forward at wp, data gradient behind it (see conv_wino_pack_kernel)
-        transposed = blockIdx.y;
-        if (transposed) { const int c = Cin; Cin = Cout; Cout = c; wp += total; }
-    }
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    long t = idx;
-    const int e = t & 3; t >>= 2;
-    const int j = t & 15; t >>= 4;
-    const int kq = t & 3; t >>= 2;
-    const int wave = t & 3; t >>= 2;
-    const int xi = t & 15; t >>= 4;
-    const int ncb = Cin / kCB;
-    const int stage = (int)(t % (4 * ncb));
-    const int cg = (int)(t / (4 * ncb));
-    const int td = stage / ncb, cb = stage - td * ncb;
-    const int co = cg * 64 + 16 * wave + j, ci = cb * kCB + 4 * kq + e;
-    const double G[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};
-    const int aa = xi >> 2, bb = xi & 3;
-    double u = 0.0;
-#pragma unroll
-    for (int kd = 0; kd < 3; ++kd) {
-        // transposed: the stored tensor is [Cin][Cout][3][3][3] (this kernel's ci is ITS output channel), taps flipped in every dimension
-        const float* g = transposed ? w + (((size_t)ci * Cout + co) * 3 + (2 - kd)) * 9 : w + (((size_t)co * Cin + ci) * 3 + kd) * 9;
-        double u2 = 0.0;
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) u2 += G[aa][ky] * (double)g[transposed ? (2 - ky) * 3 + (2 - kx) : ky * 3 + kx] * G[bb][kx];
-        u += G[td][kd] * u2;
-    }
-    wp[idx] = (float)u;
-}
-
 }  // namespace nrgbd
 
 extern "C" int nrgbd_conv_wino_dw_pack(const float* w, float* w_wino, int Cin, int Cout, int transposed, void* stream) {
-    using namespace nrgbd;
-    if (!w || !w_wino) return NRGBD_E_NULL;
-    if (Cin <= 0 || Cin % kCB || Cout <= 0 || Cout % 64) return NRGBD_E_SHAPE;
-    if (transposed < 0 || transposed > 2) return NRGBD_E_ARG;
-    if (transposed == 2 && Cin % 64) return NRGBD_E_SHAPE;
-    const long total = (long)Cout * Cin * 4 * 16;
-    hipLaunchKernelGGL(conv_wino_dw_pack_kernel, dim3((unsigned)((total + 255) / 256), transposed == 2 ? 2 : 1), dim3(256), 0, (hipStream_t)stream,
-                       w, w_wino, Cin, Cout, transposed);
-    NRGBD_CHECK_LAUNCH();
-    return NRGBD_OK;
-}
-
-static int dw_workgroups(int N, int H, int W, int Cout, int* out) {
-    const long nt = (long)(nrgbd_conv_wino_tiles(N, H, W, 1) / 2) * (Cout / 64);
-    int dev = 0, ncu = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return (int)e;
-    if (ncu <= 0) return NRGBD_E_ARG;
-    *out = nt < ncu ? (int)nt : ncu;
-    return NRGBD_OK;
+    return nrgbd::dw_pack<4>(w, w_wino, Cin, Cout, transposed, stream);
 }
 
 extern "C" int nrgbd_conv_wino_dw_workgroups(int N, int H, int W, int Cout) {
     if (N <= 0 || (N & 1) || H <= 0 || W <= 0 || Cout <= 0 || Cout % 64) return NRGBD_E_SHAPE;
     int n = 0;
-    const int rc = dw_workgroups(N, H, W, Cout, &n);
+    const int rc = nrgbd::dw_workgroups(2, N, H, W, Cout, &n);
     return rc == NRGBD_OK ? n : (rc < 0 ? rc : NRGBD_E_ARG);
 }
 
@@ -647,21 +555,16 @@ static int conv_wino_dw_launch(const float* x, const float* x_ss, int x_relu, co
                                int H, int W, int Cin, int Cout, void* stream, float x_unit = 0.f) {
     using namespace nrgbd;
     if (!x || !w_wino || !y) return NRGBD_E_NULL;
-    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cin % kCB || Cin > kDwMaxCin || Cout <= 0 || Cout % 64) return NRGBD_E_SHAPE;
-    if (N & 1) return NRGBD_E_SHAPE;                                  // pairs of output slices
-    if (H % kPcTH || W % kPcTW) return NRGBD_E_SHAPE;                 // whole 8x16 tiles only (every grid of the path; others: nrgbd_conv_wino_f32)
-    if ((long)H * W * Cin >= (1L << 30)) return NRGBD_E_SHAPE;       // 32-bit BYTE offsets inside a slice (the slice is a 64-bit base)
-    const int rows = nrgbd_conv_wino_tiles(N, H, W, 1);              // statistics rows: one per (8x16 tile, slice) as wino_pc
-    const long nt = (long)(rows / 2) * (Cout / 64);
+    int rows = 0, nwg = 0;           // statistics rows; persistent workgroups: one per CU
+    long nt = 0;
+    int rc = dw_check(2, N, H, W, Cin, Cout, &rows, &nt);
+    if (rc != NRGBD_OK) return rc;
     if (nt >= (1L << 31)) return NRGBD_E_SHAPE;
     WinoPcArgs a{x, x_ss, res, res_ss, materialized, w_wino, y, stats, x_relu, res_relu, N, H, W, Cin, Cout, (int)nt, rows,
                  nullptr, 0, 0, 0, 0, dev_env_int("NRGBD_WINO_ABL"), x_unit};
-    int dev = 0, ncu = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return (int)e;
-    if (ncu <= 0) return NRGBD_E_ARG;
-    const int nwg = nt < ncu ? (int)nt : ncu;   // persistent: one workgroup per CU
+    rc = dw_workgroups(2, N, H, W, Cout, &nwg);
+    if (rc != NRGBD_OK) return rc;
+    hipError_t e;
     const size_t lds = (size_t)(kDwNBuf * kPcV + kDwStrips + 4 * kDwStashWave + 4 * Cin) * sizeof(float);   // 64 + 25.6 (20) + 64 KB + tables
     // the function's opt-in is set to the form's maximum, not to this call's size (see nrgbd_conv_wino_f32: hipGraph replays read it)
     const int lds_attr = 160 * 1024;
@@ -702,7 +605,6 @@ extern "C" int nrgbd_conv_wino_dw_f32(const float* x, const float* x_ss, int x_r
 extern "C" int nrgbd_conv_wino_dw_unit_f32(const float* x, const float* x_ss, float x_unit, const float* w_wino, float* y, float* stats,
                                            int N, int H, int W, int Cin, int Cout, void* stream) {
     if (!x_ss) return NRGBD_E_NULL;
-    int ex = 0;
-    if (!(x_unit > 0.f) || x_unit > 1.f || frexpf(x_unit, &ex) != 0.5f) return NRGBD_E_ARG;   // a power of two in (0, 1]
+    if (!nrgbd::dw_unit_ok(x_unit)) return NRGBD_E_ARG;
     return conv_wino_dw_launch(x, x_ss, 1, nullptr, nullptr, 0, nullptr, w_wino, y, stats, N, H, W, Cin, Cout, stream, x_unit);
 }

@@ -32,17 +32,15 @@
 // Work per four output slices: 24 stages (wino_dw: 32); producer units 88 (64): 5.5 per output slice instead of 4, MFMAs 0.75x.
 #include <type_traits>
 
-#include "wino_pc.hpp"
+//
+// In wino_dw.hpp, shared with wino_dw.hip: the strip / stash / table constants, DwTile + dw_decode<4>, the serpentine order dw_cb
+// (this file's knob: NRGBD_D4_SERP), the weight packer (dw_pack<6>) and the host helpers dw_workgroups / dw_check / dw_unit_ok.
+// Here: the depth transform (d4_*), the kernel and its launcher; the skeleton pieces the kernel has in common with wino_dw.hip's
+// are still a copy (wino_dw.hpp says why).
+#include "wino_dw.hpp"
 
 namespace nrgbd {
 
-constexpr int kD4StashWave = 2 * 8 * 64 * 4;   // floats of one consumer wave's two LDS stashes: [2][8 words][64 lanes][4]
-constexpr int kD4MaxCin = 512;
-constexpr int kD4NBuf = 2;
-constexpr int kD4ShRows = kPcTH + 2;
-constexpr int kD4ShStrip = kD4ShRows * kPcRawW * kCB;      // floats of one shared strip: [10 rows][20 pixels][16] = 12.8 KB
-constexpr int kD4ShItems = kD4ShRows * 18 * 4;             // 720 (row, column, 16-byte word) items of a unit
-constexpr int kD4NPF = 3;                                  // items per producer lane and unit
 constexpr int kD4ScratchWave = 8 * 64 * 4;                 // floats of one consumer wave's global scratch (stash C)
 
 // depth-transform index of phase p (execution order) and the unit slots of index t: (input slice j = 0..5 relative to z0 - 1, coefficient)
@@ -61,29 +59,9 @@ __device__ __forceinline__ float d4_c(int t, int k) {
     return k == 1 ? s * 0.375f : (k == 2 ? -0.25f : -s * 1.5f);
 }
 
-struct D4Tile { int z0, y0, x0, cg, row0; };   // row0: statistics row of slice z0 (slice z0 + k: row0 + k)
-
-__device__ __forceinline__ D4Tile d4_decode(int t, const WinoPcArgs& a) {
-    D4Tile r;
-    const int ncg = a.Cout >> 6;
-    const int tiles_x = (a.W + kPcTW - 1) / kPcTW;
-    const int row = t / ncg;
-    r.cg = t - row * ncg;
-    t = row;
-    const int nquad = a.N >> 2;
-    const int zq = t % nquad; t /= nquad;       // depth fastest: list neighbours share two of their six input slices
-    const int tx = t % tiles_x, ty = t / tiles_x;
-    r.z0 = 4 * zq;
-    r.y0 = ty * kPcTH; r.x0 = tx * kPcTW;
-    r.row0 = (ty * tiles_x + tx) * a.N + r.z0;
-    return r;
-}
-
-// channel block of the i-th stage of phase position p: odd positions sweep the blocks backwards (see wino_dw.hip dw_cb)
 #ifndef NRGBD_D4_SERP
-#define NRGBD_D4_SERP 1   // 0: experimental A/B builds only (build.build_variant)
+#define NRGBD_D4_SERP 1   // 0: experimental A/B builds only (build.build_variant); see dw_cb
 #endif
-__device__ __forceinline__ int d4_cb(int p, int i, int ncb) { return (NRGBD_D4_SERP && (p & 1)) ? ncb - 1 - i : i; }
 
 struct WinoD4Args {
     WinoPcArgs b;       // x, x_ss, wp, y, stats, N, H, W, Cin, Cout, ntiles, rows, x_unit (res / mat / bias unused)
@@ -95,9 +73,9 @@ __global__ __launch_bounds__(512) void conv_wino_dw4_kernel(const WinoD4Args aa)
     const WinoPcArgs& a = aa.b;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* Vb = lds;                                   // [2][16 xi][32 tiles][16]
-    float* rawb = lds + kD4NBuf * kPcV;                // [2][10 rows][20 pixels][16] shared strips
-    float* stashb = rawb + 2 * kD4ShStrip;             // [4 consumer waves][2 stashes][8][64][4]
-    float* ssl = stashb + 4 * kD4StashWave;            // [Cin][2] (scale, shift) of x, pre-paired
+    float* rawb = lds + kDwNBuf * kPcV;                // [2][10 rows][20 pixels][16] shared strips
+    float* stashb = rawb + 2 * kDwShStrip;             // [4 consumer waves][2 stashes][8][64][4]
+    float* ssl = stashb + 4 * kDwStashWave;            // [Cin][2] (scale, shift) of x, pre-paired
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -132,7 +110,7 @@ __global__ __launch_bounds__(512) void conv_wino_dw4_kernel(const WinoD4Args aa)
         const f32x4* wbase = reinterpret_cast<const f32x4*>(a.wp) + wv * 64 + lane;
         const unsigned lane_yoff = (unsigned)jj + (unsigned)((2 * (kq >> 1)) * a.W + 8 * (kq & 1)) * (unsigned)a.Cout;
         const size_t wgroup = (size_t)NS * 16 * 256;
-        f32x4* stashA = reinterpret_cast<f32x4*>(stashb + wv * kD4StashWave) + lane;     // word i at stashA[i * 64]
+        f32x4* stashA = reinterpret_cast<f32x4*>(stashb + wv * kDwStashWave) + lane;     // word i at stashA[i * 64]
         f32x4* stashB = stashA + 8 * 64;
         // stash C: the wave's 8 KB of the global scratch through a buffer descriptor (uniform base in SGPRs + the lane's 32-bit byte offset:
         // no 64-bit per-lane pointer kept alive across the tile loop — the register file has none to spare)
@@ -140,7 +118,7 @@ __global__ __launch_bounds__(512) void conv_wino_dw4_kernel(const WinoD4Args aa)
                                                       ((size_t)blockIdx.x * 4 + wv) * kD4ScratchWave * sizeof(float));
         const int laneC = lane * 16;
 
-        D4Tile tl = d4_decode(first, a);
+        DwTile tl = dw_decode<4>(first, a);
         const f32x4* wt = wbase + (size_t)tl.cg * wgroup;
         f32x4 Bn[kPcNB], An[2][2];
 #pragma unroll
@@ -156,7 +134,7 @@ __global__ __launch_bounds__(512) void conv_wino_dw4_kernel(const WinoD4Args aa)
 
         for (int it = 0; it < count; ++it) {
             const int tnext = first + (it + 1 < count ? it + 1 : it) * step;
-            const D4Tile tn = d4_decode(tnext, a);
+            const DwTile tn = dw_decode<4>(tnext, a);
             const f32x4* wt_next = wbase + (size_t)tn.cg * wgroup;
             const int co = tl.cg * 64 + wv * 16 + jj;
             // one phase = the Cin/16 stages of position P (depth-transform index t = 1, 2, 3, 4, 0, 5), then its fold; the six phases are
@@ -165,13 +143,13 @@ __global__ __launch_bounds__(512) void conv_wino_dw4_kernel(const WinoD4Args aa)
             auto phase = [&](auto p_tag) __attribute__((always_inline)) {
                 constexpr int P = decltype(p_tag)::value;
                 for (int cb = 0; cb < ncb; ++cb) {
-                    const int s = P * ncb + d4_cb(P, cb, ncb);
+                    const int s = P * ncb + dw_cb(NRGBD_D4_SERP, P, cb, ncb);
                     const float* Vc = Vb + buf * kPcV;
                     const int nbuf = buf ^ 1;
                     const float* Vn = Vb + nbuf * kPcV;
                     const f32x4* wcur = wt + (size_t)s * (16 * 256);
-                    const f32x4* wnx = cb + 1 < ncb ? wt + (size_t)(P * ncb + d4_cb(P, cb + 1, ncb)) * (16 * 256)
-                                       : (P < 5 ? wt + (size_t)((P + 1) * ncb + d4_cb(P + 1, 0, ncb)) * (16 * 256) : wt_next);
+                    const f32x4* wnx = cb + 1 < ncb ? wt + (size_t)(P * ncb + dw_cb(NRGBD_D4_SERP, P, cb + 1, ncb)) * (16 * 256)
+                                       : (P < 5 ? wt + (size_t)((P + 1) * ncb + dw_cb(NRGBD_D4_SERP, P + 1, 0, ncb)) * (16 * 256) : wt_next);
                     auto body = [&](auto first_tag) __attribute__((always_inline)) {
                         constexpr bool FIRST = decltype(first_tag)::value;
                         const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
@@ -302,7 +280,7 @@ __global__ __launch_bounds__(512) void conv_wino_dw4_kernel(const WinoD4Args aa)
     } else {
         // =========================================== producer: tile row pw (8 Winograd tiles) ===========================
         const int pw = wv;
-        constexpr int kItems = kD4ShItems;
+        constexpr int kItems = kDwShItems;
         float* raw = rawb;                                  // the strip this iteration PUBLISHES into (set per iteration)
         const float* rawT = rawb;                           // ... and the one it TRANSFORMS from
         const int w4 = lane & 3;
@@ -310,9 +288,9 @@ __global__ __launch_bounds__(512) void conv_wino_dw4_kernel(const WinoD4Args aa)
         auto item_rr = [&](int u) { return (item_id(u) >> 2) / 18; };
         auto item_cp = [&](int u) { const int pi = item_id(u) >> 2; return pi - (pi / 18) * 18; };
         auto item_col = [&](int u) { const int cp = item_cp(u); return cp < 9 ? 2 * cp : 2 * cp - 17; };
-        int wr_off[kD4NPF];
+        int wr_off[kDwNPF];
 #pragma unroll
-        for (int u = 0; u < kD4NPF; ++u) {
+        for (int u = 0; u < kDwNPF; ++u) {
             const int item = item_id(u), e = (item - kItems) >> 2;   // lanes without an item write a zero into a pad pixel (columns 18, 19)
             wr_off[u] = item < kItems ? (item_rr(u) * kPcRawW + item_cp(u)) * kCB + w4 * 4
                                       : ((e >> 1) * kPcRawW + 18 + (e & 1)) * kCB + w4 * 4;
@@ -326,11 +304,11 @@ __global__ __launch_bounds__(512) void conv_wino_dw4_kernel(const WinoD4Args aa)
         float m1 = -1.f;
         asm volatile("" : "+v"(m1));
 
-        unsigned cur_off[kD4NPF], nxt_off[kD4NPF];   // BYTE offsets inside a slice
-        float cur_keep[kD4NPF], nxt_keep[kD4NPF];
-        auto setup = [&](const D4Tile& tt, unsigned (&b_off)[kD4NPF], float (&b_keep)[kD4NPF]) __attribute__((always_inline)) {
+        unsigned cur_off[kDwNPF], nxt_off[kDwNPF];   // BYTE offsets inside a slice
+        float cur_keep[kDwNPF], nxt_keep[kDwNPF];
+        auto setup = [&](const DwTile& tt, unsigned (&b_off)[kDwNPF], float (&b_keep)[kDwNPF]) __attribute__((always_inline)) {
 #pragma unroll
-            for (int u = 0; u < kD4NPF; ++u) {
+            for (int u = 0; u < kDwNPF; ++u) {
                 const int hy = item_rr(u), hx = item_col(u);
                 const int gy = tt.y0 + hy - 1, gx = tt.x0 + hx - 1;
                 const bool in = item_id(u) < kItems && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
@@ -338,8 +316,8 @@ __global__ __launch_bounds__(512) void conv_wino_dw4_kernel(const WinoD4Args aa)
                 b_keep[u] = in ? 1.f : 0.f;
             }
         };
-        struct Regs { f32x4 pre[kD4NPF]; };
-        D4Tile tl = d4_decode(first, a), tn = tl;
+        struct Regs { f32x4 pre[kDwNPF]; };
+        DwTile tl = dw_decode<4>(first, a), tn = tl;
         // raw words of one unit = (slice z0 - 1 + j, channel block cb) -> registers; nx: of the NEXT tile
         auto issue = [&](bool nx, int j, int cb, Regs& r) __attribute__((always_inline)) {
             const int tz = (nx ? tn.z0 : tl.z0) - 1 + j;
@@ -351,7 +329,7 @@ __global__ __launch_bounds__(512) void conv_wino_dw4_kernel(const WinoD4Args aa)
             const size_t base = ((size_t)z * plane + (size_t)(__builtin_amdgcn_readfirstlane(cb) * kCB)) * sizeof(float);
             const __amdgpu_buffer_rsrc_t xb = pc_rsrc(reinterpret_cast<const char*>(a.x) + base);
 #pragma unroll
-            for (int u = 0; u < kD4NPF; ++u) r.pre[u] = pc_bload(xb, nx ? nxt_off[u] : cur_off[u]);
+            for (int u = 0; u < kDwNPF; ++u) r.pre[u] = pc_bload(xb, nx ? nxt_off[u] : cur_off[u]);
         };
         setup(tl, cur_off, cur_keep);
         // one register set per unit slot of a stage, refilled with the same slot of the NEXT stage right after it was published: a whole
@@ -359,7 +337,7 @@ __global__ __launch_bounds__(512) void conv_wino_dw4_kernel(const WinoD4Args aa)
         Regs set0, set1, set2, set3;
         f32x4 ssw[2] = {{1.f, 1.f, 0.f, 0.f}, {1.f, 1.f, 0.f, 0.f}};     // (scale, shift) pairs of the stage's channel block (pre-paired table)
         {
-            const int t0 = d4_t(0), cb0 = d4_cb(0, 0, ncb);
+            const int t0 = d4_t(0), cb0 = dw_cb(NRGBD_D4_SERP, 0, 0, ncb);
             issue(false, d4_j(t0, 0), cb0, set0);
             issue(false, d4_j(t0, 1), cb0, set1);
             issue(false, d4_j(t0, 2), cb0, set2);
@@ -372,27 +350,27 @@ __global__ __launch_bounds__(512) void conv_wino_dw4_kernel(const WinoD4Args aa)
         auto activate = [&](Regs& r) __attribute__((always_inline)) {
             if constexpr (IDENT) return;
             const f32x2 sc01 = ssw[0].lo, sh01 = ssw[0].hi, sc23 = ssw[1].lo, sh23 = ssw[1].hi;
-            f32x2 lo[kD4NPF], hi[kD4NPF];
+            f32x2 lo[kDwNPF], hi[kDwNPF];
             if constexpr (CLAMP) {
 #pragma unroll
-                for (int i = 0; i < kD4NPF; ++i) {
+                for (int i = 0; i < kDwNPF; ++i) {
                     lo[i] = pk_fma_clamp01(r.pre[i].lo, sc01, sh01);
                     hi[i] = pk_fma_clamp01(r.pre[i].hi, sc23, sh23);
                 }
             } else {
 #pragma unroll
-                for (int i = 0; i < kD4NPF; ++i) {
+                for (int i = 0; i < kDwNPF; ++i) {
                     lo[i] = __builtin_elementwise_fma(r.pre[i].lo, sc01, sh01);
                     hi[i] = __builtin_elementwise_fma(r.pre[i].hi, sc23, sh23);
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 if (a.x_relu) {
 #pragma unroll
-                    for (int i = 0; i < kD4NPF; ++i) { lo[i].x = relu1(lo[i].x); lo[i].y = relu1(lo[i].y); hi[i].x = relu1(hi[i].x); hi[i].y = relu1(hi[i].y); }
+                    for (int i = 0; i < kDwNPF; ++i) { lo[i].x = relu1(lo[i].x); lo[i].y = relu1(lo[i].y); hi[i].x = relu1(hi[i].x); hi[i].y = relu1(hi[i].y); }
                 }
             }
 #pragma unroll
-            for (int i = 0; i < kD4NPF; ++i) r.pre[i] = __builtin_shufflevector(lo[i], hi[i], 0, 1, 2, 3);
+            for (int i = 0; i < kDwNPF; ++i) r.pre[i] = __builtin_shufflevector(lo[i], hi[i], 0, 1, 2, 3);
             __builtin_amdgcn_sched_barrier(0);
         };
 
@@ -427,13 +405,13 @@ __global__ __launch_bounds__(512) void conv_wino_dw4_kernel(const WinoD4Args aa)
             int cbi = 0, p = 0;
             for (int s = 0; s < NS; ++s) {
                 // the book of the next tile is needed by the refills of the tile's last stage
-                if (s == NS - 1 && has_next) { tn = d4_decode(first + (it + 1) * step, a); setup(tn, nxt_off, nxt_keep); }
-                raw = rawb + (gi & 1) * kD4ShStrip; rawT = rawb + ((gi & 1) ^ 1) * kD4ShStrip;
-                const int t = d4_t(p), cb = d4_cb(p, cbi, ncb), nsl = d4_nslot(t);
+                if (s == NS - 1 && has_next) { tn = dw_decode<4>(first + (it + 1) * step, a); setup(tn, nxt_off, nxt_keep); }
+                raw = rawb + (gi & 1) * kDwShStrip; rawT = rawb + ((gi & 1) ^ 1) * kDwShStrip;
+                const int t = d4_t(p), cb = dw_cb(NRGBD_D4_SERP, p, cbi, ncb), nsl = d4_nslot(t);
                 // stage s + 1: (position, channel block, depth index), possibly of the next tile
                 const bool nx = s + 1 >= NS;
                 const int cbn = cbi + 1 == ncb ? 0 : cbi + 1, pn = nx ? 0 : (cbi + 1 == ncb ? p + 1 : p);
-                const int tnx = d4_t(pn), cbne = d4_cb(pn, cbn, ncb);
+                const int tnx = d4_t(pn), cbne = dw_cb(NRGBD_D4_SERP, pn, cbn, ncb);
                 if constexpr (!IDENT) {
                     ssw[0] = *reinterpret_cast<const f32x4*>(ssl + 2 * (cb * kCB + w4 * 4));
                     ssw[1] = *reinterpret_cast<const f32x4*>(ssl + 2 * (cb * kCB + w4 * 4) + 4);
@@ -453,16 +431,16 @@ __global__ __launch_bounds__(512) void conv_wino_dw4_kernel(const WinoD4Args aa)
                     // unit by unit: wait for ITS words only, fold them into the running combination, request the same slot of stage s + 1
                     // right away (the refills stay spread over the stage: twelve loads in one burst cost ~600 issue cycles in a row, and one
                     // wait for all four sets exposes the slowest — measured +3 % against this order)
-                    f32x2 lo[kD4NPF], hi[kD4NPF];
+                    f32x2 lo[kDwNPF], hi[kDwNPF];
                     activate(set0);
                     {
                         // the first slot's coefficient is 1 (every row of Bd has one) unless its slice is outside the volume (then 0)
                         if (c[0] != 0.f) {
 #pragma unroll
-                            for (int i = 0; i < kD4NPF; ++i) { lo[i] = set0.pre[i].lo; hi[i] = set0.pre[i].hi; }
+                            for (int i = 0; i < kDwNPF; ++i) { lo[i] = set0.pre[i].lo; hi[i] = set0.pre[i].hi; }
                         } else {
 #pragma unroll
-                            for (int i = 0; i < kD4NPF; ++i) { lo[i] = f32x2{0.f, 0.f}; hi[i] = f32x2{0.f, 0.f}; }
+                            for (int i = 0; i < kDwNPF; ++i) { lo[i] = f32x2{0.f, 0.f}; hi[i] = f32x2{0.f, 0.f}; }
                         }
                     }
                     issue(nx && has_next, d4_j(tnx, 0), cbne, set0);
@@ -470,25 +448,25 @@ __global__ __launch_bounds__(512) void conv_wino_dw4_kernel(const WinoD4Args aa)
                     {
                         const f32x2 c1 = {c[1], c[1]};
 #pragma unroll
-                        for (int i = 0; i < kD4NPF; ++i) { lo[i] = __builtin_elementwise_fma(set1.pre[i].lo, c1, lo[i]); hi[i] = __builtin_elementwise_fma(set1.pre[i].hi, c1, hi[i]); }
+                        for (int i = 0; i < kDwNPF; ++i) { lo[i] = __builtin_elementwise_fma(set1.pre[i].lo, c1, lo[i]); hi[i] = __builtin_elementwise_fma(set1.pre[i].hi, c1, hi[i]); }
                     }
                     issue(nx && has_next, d4_j(tnx, 1), cbne, set1);
                     activate(set2);
                     {
                         const f32x2 c2 = {c[2], c[2]};
 #pragma unroll
-                        for (int i = 0; i < kD4NPF; ++i) { lo[i] = __builtin_elementwise_fma(set2.pre[i].lo, c2, lo[i]); hi[i] = __builtin_elementwise_fma(set2.pre[i].hi, c2, hi[i]); }
+                        for (int i = 0; i < kDwNPF; ++i) { lo[i] = __builtin_elementwise_fma(set2.pre[i].lo, c2, lo[i]); hi[i] = __builtin_elementwise_fma(set2.pre[i].hi, c2, hi[i]); }
                     }
                     issue(nx && has_next, d4_j(tnx, 2), cbne, set2);
                     if (nsl > 3) {
                         activate(set3);
                         const f32x2 c3 = {c[3], c[3]};
 #pragma unroll
-                        for (int i = 0; i < kD4NPF; ++i) { lo[i] = __builtin_elementwise_fma(set3.pre[i].lo, c3, lo[i]); hi[i] = __builtin_elementwise_fma(set3.pre[i].hi, c3, hi[i]); }
+                        for (int i = 0; i < kDwNPF; ++i) { lo[i] = __builtin_elementwise_fma(set3.pre[i].lo, c3, lo[i]); hi[i] = __builtin_elementwise_fma(set3.pre[i].hi, c3, hi[i]); }
                     }
                     if (nsn > 3) issue(nx && has_next, d4_j(tnx, 3), cbne, set3);
 #pragma unroll
-                    for (int i = 0; i < kD4NPF; ++i) {
+                    for (int i = 0; i < kDwNPF; ++i) {
                         if (!interior) {
                             const f32x2 kk = {cur_keep[i], cur_keep[i]};
                             lo[i] = lo[i] * kk; hi[i] = hi[i] * kk;
@@ -505,10 +483,10 @@ __global__ __launch_bounds__(512) void conv_wino_dw4_kernel(const WinoD4Args aa)
             }
             tl = tn;
 #pragma unroll
-            for (int u = 0; u < kD4NPF; ++u) { cur_off[u] = nxt_off[u]; cur_keep[u] = nxt_keep[u]; }
+            for (int u = 0; u < kDwNPF; ++u) { cur_off[u] = nxt_off[u]; cur_keep[u] = nxt_keep[u]; }
         }
         {                                      // the last published stage
-            rawT = rawb + ((gi & 1) ^ 1) * kD4ShStrip;
+            rawT = rawb + ((gi & 1) ^ 1) * kDwShStrip;
             transform();
             __syncthreads();
         }
@@ -516,79 +494,18 @@ __global__ __launch_bounds__(512) void conv_wino_dw4_kernel(const WinoD4Args aa)
     }
 }
 
-// w [Cout][Cin][3][3][3] -> U_t = sum_kd Gd[t][kd] (G g_kd G^T) (float64, rounded once) in the kernel's B-operand order, phases in
-// EXECUTION order: [cg][stage = p*ncb + cb][xi][wave][lane = kq*16 + j][e], t = d4_t(p), co = cg*64 + 16*wave + j, ci = cb*16 + 4*kq + e
-// transposed = 1: the data-gradient stream (w is stored [Cin][Cout][3][3][3] seen from this kernel: its ci is the stored tensor's output
-// channel; taps flipped in every dimension); 2: both streams in one launch (grid.y = 2), the data gradient's behind the forward one.
-__global__ __launch_bounds__(256) void conv_wino_dw4_pack_kernel(const float* __restrict__ w, float* __restrict__ wp, int Cin, int Cout,
-                                                                 int transposed) {
-    const long total = (long)Cout * Cin * 6 * 16;
-    if (transposed == 2) {
-        transposed = blockIdx.y;
-        if (transposed) { const int c = Cin; Cin = Cout; Cout = c; wp += total; }
-    }
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    long t = idx;
-    const int e = t & 3; t >>= 2;
-    const int j = t & 15; t >>= 4;
-    const int kq = t & 3; t >>= 2;
-    const int wave = t & 3; t >>= 2;
-    const int xi = t & 15; t >>= 4;
-    const int ncb = Cin / kCB;
-    const int stage = (int)(t % (6 * ncb));
-    const int cg = (int)(t / (6 * ncb));
-    const int p = stage / ncb, cb = stage - p * ncb;
-    const int td = p < 4 ? p + 1 : (p == 4 ? 0 : 5);
-    const int co = cg * 64 + 16 * wave + j, ci = cb * kCB + 4 * kq + e;
-    const double G[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};
-    const double Gd[6][3] = {{16.0 / 9.0, 0.0, 0.0}, {-1.0, -0.5, -0.25}, {-1.0, 0.5, -0.25}, {1.0 / 9.0, 1.0 / 6.0, 0.25}, {1.0 / 9.0, -1.0 / 6.0, 0.25}, {0.0, 0.0, 1.0}};
-    const int aa = xi >> 2, bb = xi & 3;
-    double u = 0.0;
-#pragma unroll
-    for (int kd = 0; kd < 3; ++kd) {
-        const float* g = transposed ? w + (((size_t)ci * Cout + co) * 3 + (2 - kd)) * 9 : w + (((size_t)co * Cin + ci) * 3 + kd) * 9;
-        double u2 = 0.0;
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) u2 += G[aa][ky] * (double)g[transposed ? (2 - ky) * 3 + (2 - kx) : ky * 3 + kx] * G[bb][kx];
-        u += Gd[td][kd] * u2;
-    }
-    wp[idx] = (float)u;
-}
-
 }  // namespace nrgbd
 
+// the weight stream's phases are in EXECUTION order: stage = p*ncb + cb, t = d4_t(p) (DwDepth<6>::t_of_phase)
 extern "C" int nrgbd_conv_wino_dw4_pack(const float* w, float* w_wino, int Cin, int Cout, int transposed, void* stream) {
-    using namespace nrgbd;
-    if (!w || !w_wino) return NRGBD_E_NULL;
-    if (Cin <= 0 || Cin % kCB || Cout <= 0 || Cout % 64) return NRGBD_E_SHAPE;
-    if (transposed < 0 || transposed > 2) return NRGBD_E_ARG;
-    if (transposed == 2 && Cin % 64) return NRGBD_E_SHAPE;
-    const long total = (long)Cout * Cin * 6 * 16;
-    hipLaunchKernelGGL(conv_wino_dw4_pack_kernel, dim3((unsigned)((total + 255) / 256), transposed == 2 ? 2 : 1), dim3(256), 0,
-                       (hipStream_t)stream, w, w_wino, Cin, Cout, transposed);
-    NRGBD_CHECK_LAUNCH();
-    return NRGBD_OK;
-}
-
-static int dw4_workgroups(int N, int H, int W, int Cout, int* out) {
-    const long nt = (long)(nrgbd_conv_wino_tiles(N, H, W, 1) / 4) * (Cout / 64);
-    int dev = 0, ncu = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return (int)e;
-    if (ncu <= 0) return NRGBD_E_ARG;
-    *out = nt < ncu ? (int)nt : ncu;
-    return NRGBD_OK;
+    return nrgbd::dw_pack<6>(w, w_wino, Cin, Cout, transposed, stream);
 }
 
 extern "C" int nrgbd_conv_wino_dw4_workspace(int N, int H, int W, int Cout, size_t* bytes) {
     if (!bytes) return NRGBD_E_NULL;
     if (N <= 0 || (N & 3) || H <= 0 || W <= 0 || Cout <= 0 || Cout % 64) return NRGBD_E_SHAPE;
     int n = 0;
-    const int rc = dw4_workgroups(N, H, W, Cout, &n);
+    const int rc = nrgbd::dw_workgroups(4, N, H, W, Cout, &n);
     if (rc != NRGBD_OK) return rc;
     *bytes = (size_t)n * 4 * nrgbd::kD4ScratchWave * sizeof(float);
     return NRGBD_OK;
@@ -599,30 +516,24 @@ extern "C" int nrgbd_conv_wino_dw4_f32(const float* x, const float* x_ss, int x_
                                        void* stream) {
     using namespace nrgbd;
     if (!x || !w_wino || !y || !workspace) return NRGBD_E_NULL;
-    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cin % kCB || Cin > kD4MaxCin || Cout <= 0 || Cout % 64) return NRGBD_E_SHAPE;
-    if (N & 3) return NRGBD_E_SHAPE;                                  // quadruples of output slices
-    if (H % kPcTH || W % kPcTW) return NRGBD_E_SHAPE;                 // whole 8x16 tiles only
-    if ((long)H * W * Cin >= (1L << 30)) return NRGBD_E_SHAPE;       // 32-bit BYTE offsets inside a slice
+    int rows = 0, nwg = 0;           // statistics rows; persistent workgroups
+    long nt = 0;
+    int rc = dw_check(4, N, H, W, Cin, Cout, &rows, &nt);
+    if (rc != NRGBD_OK) return rc;
     if (reinterpret_cast<uintptr_t>(workspace) & 15) return NRGBD_E_ALIGN;
     const bool clamp = x_unit != 0.f;
-    if (clamp) {
-        int ex = 0;
-        if (!x_ss || !x_relu || !(x_unit > 0.f) || x_unit > 1.f || frexpf(x_unit, &ex) != 0.5f) return NRGBD_E_ARG;   // a power of two in (0, 1]
-    }
-    const int rows = nrgbd_conv_wino_tiles(N, H, W, 1);              // statistics rows: one per (8x16 tile, slice)
-    const long nt = (long)(rows / 4) * (Cout / 64);
+    if (clamp && (!x_ss || !x_relu || !dw_unit_ok(x_unit))) return NRGBD_E_ARG;
     if (nt >= (1L << 31)) return NRGBD_E_SHAPE;
-    int nwg = 0;
-    const int rc = dw4_workgroups(N, H, W, Cout, &nwg);
+    rc = dw_workgroups(4, N, H, W, Cout, &nwg);
     if (rc != NRGBD_OK) return rc;
     if (workspace_bytes < (size_t)nwg * 4 * kD4ScratchWave * sizeof(float)) return NRGBD_E_NULL;
     WinoD4Args aa{};
     aa.b = WinoPcArgs{x, x_ss, nullptr, nullptr, nullptr, w_wino, y, stats, x_relu, 0, N, H, W, Cin, Cout, (int)nt, rows,
                       nullptr, 0, 0, 0, 0, 0, x_unit};
     aa.scratch = static_cast<float*>(workspace);
-    const size_t lds = (size_t)(kD4NBuf * kPcV + 2 * kD4ShStrip + 4 * kD4StashWave + 2 * Cin) * sizeof(float);
+    const size_t lds = (size_t)(kDwNBuf * kPcV + 2 * kDwShStrip + 4 * kDwStashWave + 2 * Cin) * sizeof(float);
     // the function's opt-in is set to the form's maximum, not to this call's size (see nrgbd_conv_wino_f32: hipGraph replays read it)
-    const int lds_attr = (int)((size_t)(kD4NBuf * kPcV + 2 * kD4ShStrip + 4 * kD4StashWave + 2 * kD4MaxCin) * sizeof(float));
+    const int lds_attr = (int)((size_t)(kDwNBuf * kPcV + 2 * kDwShStrip + 4 * kDwStashWave + 2 * kDwMaxCin) * sizeof(float));
     hipStream_t st = (hipStream_t)stream;
     hipError_t e;
 #define NRGBD_D4_LAUNCH(ID_, CL_)                                                                                          \

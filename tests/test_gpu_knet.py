@@ -476,7 +476,8 @@ def test_variance_collapse_is_loud_not_saturated():
         st.step(r, s_, p_)                                                # ... and the following step sees it
 
 
-@pytest.mark.parametrize("D,H,W,Cin", [(4, 16, 32, 64), (8, 24, 48, 64), (40, 40, 80, 64), (64, 8, 16, 64), (8, 16, 32, 16), (4, 16, 32, 128)])
+@pytest.mark.parametrize("D,H,W,Cin", [(4, 16, 32, 64), (8, 24, 48, 64), (40, 40, 80, 64), (64, 8, 16, 64), (8, 16, 32, 16), (4, 16, 32, 128),
+                                       (16, 40, 224, 64)])   # 280 tiles > 256 CUs: a workgroup walks a second tile (next-tile book, wt_next)
 def test_conv_wino_dw4_plain_vs_torch(D, H, W, Cin):
     """csrc/wino_dw4.hip: F(2x2,3x3) in the plane + F(4,3) along depth (6 x Cin/16 stages per FOUR output slices; points 0, +-1/2,
     +-3/2, inf) vs F.conv3d in float64: a single quadruple (both depth borders in one tile: the empty first and last input slices),
