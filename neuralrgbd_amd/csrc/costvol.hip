@@ -140,14 +140,7 @@ static int launch_gather(const CostvolArgs& a, hipStream_t stream) {
         hipLaunchKernelGGL((costvol_gather<TW, TH, KS, N>), dim3(tiles), dim3(256), lds, stream, a); \
         break;
     switch (cp4) {
-        NRGBD_GATHER_CASE(1)
-        NRGBD_GATHER_CASE(2)
-        NRGBD_GATHER_CASE(3)
-        NRGBD_GATHER_CASE(4)
-        NRGBD_GATHER_CASE(8)
-        NRGBD_GATHER_CASE(9)
-        NRGBD_GATHER_CASE(16)
-        NRGBD_GATHER_CASE(17)
+        NRGBD_CP4_CASES(NRGBD_GATHER_CASE)
         default:
             hipLaunchKernelGGL((costvol_gather<TW, TH, KS, 0>), dim3(tiles), dim3(256), lds, stream, a);
     }
@@ -185,18 +178,13 @@ extern "C" int nrgbd_costvol_fwd_gen(const float* ref_nhwc, const float* src_nhw
     // generation that does not support the shape is an error, never a silent substitution.
     if (generation == NRGBD_GEN_QUAD && !costvol_quad_supported(a)) return NRGBD_E_SHAPE;
     if (generation == NRGBD_GEN_LDS && !costvol_lds_supported(Cp >> 2)) return NRGBD_E_SHAPE;
-    if (generation == NRGBD_GEN_QUAD || (generation == NRGBD_GEN_AUTO && costvol_quad_supported(a))) {
-        bool did_softmax = false;
-        int rc = launch_costvol_quad(a, s, &did_softmax);
+    const bool quad = generation == NRGBD_GEN_QUAD || (generation == NRGBD_GEN_AUTO && costvol_quad_supported(a));
+    const bool lds = !quad && (generation == NRGBD_GEN_LDS || (generation == NRGBD_GEN_AUTO && costvol_lds_supported(Cp >> 2)));
+    if (quad || lds) {
+        bool did_softmax = false;                  // only the quad kernel can take the log-softmax in its own launch
+        const int rc = quad ? launch_costvol_quad(a, s, &did_softmax) : launch_costvol_lds(a, s);
         if (rc != NRGBD_OK) return rc;
-        if (out_logp && !did_softmax)
-            return launch_logsoftmax_d(out_cost ? out_cost : out_logp, nullptr, -1.f, out_logp, D, (size_t)h * w, s);
-        return NRGBD_OK;
-    }
-    if (generation == NRGBD_GEN_LDS || (generation == NRGBD_GEN_AUTO && costvol_lds_supported(Cp >> 2))) {
-        int rc = launch_costvol_lds(a, s);
-        if (rc != NRGBD_OK) return rc;
-        if (out_logp)  // log_softmax(-cost) over D (models/basic.py:299-300); in place when only logp is wanted
+        if (out_logp && !did_softmax)  // log_softmax(-cost) over D (models/basic.py:299-300); in place when only logp is wanted
             return launch_logsoftmax_d(out_cost ? out_cost : out_logp, nullptr, -1.f, out_logp, D, (size_t)h * w, s);
         return NRGBD_OK;
     }

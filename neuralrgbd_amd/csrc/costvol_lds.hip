@@ -46,14 +46,6 @@ struct LdsCfg {
     static constexpr int count(int cb) { return (CP4 - cb * kKB < kKB) ? CP4 - cb * kKB : kKB; }  // words computed
 };
 
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (N > 0) {
-        static_for<N - 1>(f);
-        f(std::integral_constant<int, N - 1>{});
-    }
-}
-
 // Direct-gather evaluation of one (pixel, candidate, view): sum_c dist(sample_c, ref_c) with 16-byte
 // loads straight from HBM/L2: the path of candidates whose tile footprint overflows the patch even alone.
 __device__ __noinline__ float gather_point(const float* __restrict__ sv, const float* __restrict__ refp,
@@ -64,10 +56,7 @@ __device__ __noinline__ float gather_point(const float* __restrict__ sv, const f
         float acc0 = 0.f;
         for (int i = 0; i < (Cp >> 2); ++i) {
             const float4 rr = rp0[i];
-            const float s[4] = {0.f - rr.x, 0.f - rr.y, 0.f - rr.z, 0.f - rr.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (4 * i + e < C) acc0 = (dist == NRGBD_DIST_L2) ? __builtin_fmaf(s[e], s[e], acc0) : acc0 + fabsf(s[e]);
+            acc0 = zero_sample_dist(rr.x, rr.y, rr.z, rr.w, C - 4 * i, dist, acc0);
         }
         return acc0;
     }
@@ -120,16 +109,6 @@ __device__ __forceinline__ int region_box(const CostvolArgs& a, const float* KRv
     o.ylo = max((int)floorf(mny) - 1, 0); o.yhi = min((int)floorf(mxy) + 2, a.h - 1);
     if (o.xlo > o.xhi || o.ylo > o.yhi) { o = Box{1, 0, 1, 0}; return 0; }
     return 1;
-}
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// |s| or s*s accumulated into `acc` (metric fixed at compile time: no branch inside the channel loop)
-template <int DIST>
-__device__ __forceinline__ float dist_acc(float s, float acc) {
-    if constexpr (DIST == NRGBD_DIST_L2) return __builtin_fmaf(s, s, acc);
-    else return acc + fabsf(s);
 }
 
 template <int CP4, int DIST>
@@ -298,17 +277,10 @@ __global__ __launch_bounds__(256, 2) void costvol_lds(const CostvolArgs a) {
                         // opaque copies: stop the compiler from keeping 8 candidates x (4 weights + 4
                         // addresses) alive across the channel blocks (that spills); recomputing is ~25 VALU
                         asm volatile("" : "+v"(ix), "+v"(iy));
-                        const float x0f = floorf(ix), y0f = floorf(iy);
-                        const float fx = ix - x0f, fy = iy - y0f, ex = 1.f - fx, ey = 1.f - fy;
-                        const float x1f = x0f + 1.f, y1f = y0f + 1.f;
-                        const bool vx0 = (x0f >= 0.f) && (x0f <= wf - 1.f), vx1 = (x1f >= 0.f) && (x1f <= wf - 1.f);
-                        const bool vy0 = (y0f >= 0.f) && (y0f <= hf - 1.f), vy1 = (y1f >= 0.f) && (y1f <= hf - 1.f);
-                        Bilinear b;
-                        b.nw = (vx0 && vy0) ? ey * ex : 0.f; b.ne = (vx1 && vy0) ? ey * fx : 0.f;
-                        b.sw = (vx0 && vy1) ? fy * ex : 0.f; b.se = (vx1 && vy1) ? fy * fx : 0.f;
+                        const TapW b = tap_weights(ix, iy, wf, hf);
                         // patch-relative texel indices; a tap that is out of view reads texel 0 with weight 0
-                        const int xo0 = vx0 ? (int)x0f - xlo : 0, xo1 = vx1 ? (int)x1f - xlo : 0;
-                        const int yo0 = vy0 ? __mul24((int)y0f - ylo, cols) : 0, yo1 = vy1 ? __mul24((int)y1f - ylo, cols) : 0;
+                        const int xo0 = b.vx0 ? (int)b.x0f - xlo : 0, xo1 = b.vx1 ? (int)(b.x0f + 1.f) - xlo : 0;
+                        const int yo0 = b.vy0 ? __mul24((int)b.y0f - ylo, cols) : 0, yo1 = b.vy1 ? __mul24((int)(b.y0f + 1.f) - ylo, cols) : 0;
                         const int last = area - 1;  // belt and braces: never address outside the patch
                         const f32x4* sm = reinterpret_cast<const f32x4*>(smem4);
                         const f32x4* tnw = sm + __mul24(min(max(yo0 + xo0, 0), last), S4);
@@ -373,14 +345,7 @@ __global__ __launch_bounds__(256, 2) void costvol_lds(const CostvolArgs a) {
 #pragma unroll
                         for (int i = 0; i < n4; ++i) {
                             const f32x4 rr = r[Cfg::first(cb) + i];
-                            const int ncomp = (Cfg::first(cb) + i == CP4 - 1) ? tail : 4;
-                            const float c4[4] = {rr.x, rr.y, rr.z, rr.w};
-#pragma unroll
-                            for (int e = 0; e < 4; ++e)
-                                if (e < ncomp) {
-                                    const float s = 0.f - c4[e];
-                                    part = dist_acc<DIST>(s, part);
-                                }
+                            part = zero_sample_dist(rr.x, rr.y, rr.z, rr.w, (Cfg::first(cb) + i == CP4 - 1) ? tail : 4, DIST, part);
                         }
                     }
                     acc[j] += part;
@@ -403,10 +368,12 @@ __global__ __launch_bounds__(256, 2) void costvol_lds(const CostvolArgs a) {
 }
 
 bool costvol_lds_supported(int cp4) {
+#define NRGBD_LDS_HAS(N) case N:
     switch (cp4) {
-        case 1: case 2: case 3: case 4: case 8: case 9: case 16: case 17: return true;
+        NRGBD_CP4_CASES(NRGBD_LDS_HAS) return true;
         default: return false;
     }
+#undef NRGBD_LDS_HAS
 }
 
 int launch_costvol_lds(const CostvolArgs& args, hipStream_t stream) {
@@ -426,14 +393,7 @@ int launch_costvol_lds(const CostvolArgs& args, hipStream_t stream) {
             hipLaunchKernelGGL((costvol_lds<N, NRGBD_DIST_L1>), grid, dim3(256), lds, stream, a); \
         break;
     switch (a.Cp >> 2) {
-        NRGBD_LDS_CASE(1)
-        NRGBD_LDS_CASE(2)
-        NRGBD_LDS_CASE(3)
-        NRGBD_LDS_CASE(4)
-        NRGBD_LDS_CASE(8)
-        NRGBD_LDS_CASE(9)
-        NRGBD_LDS_CASE(16)
-        NRGBD_LDS_CASE(17)
+        NRGBD_CP4_CASES(NRGBD_LDS_CASE)
         default: return NRGBD_E_SHAPE;
     }
 #undef NRGBD_LDS_CASE

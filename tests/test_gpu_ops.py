@@ -429,6 +429,49 @@ def test_costvol_quad_align_corners_and_determinism():
         assert np.abs(a - want).max() < 1e-5 * max(10.0, float(want.max()))
 
 
+@pytest.mark.parametrize("h,w,D", [
+    # The launcher (costvol_quad.hip) doubles nchunk while tiles * nchunk < 768 and ceil(D / (2 nchunk)) >= 8; tiles = 8x8-pixel tiles.
+    (128, 128, 8),   # 256 tiles, nchunk 1 (ceil(8 / 2) = 4 < 8): 32 tiles per XCD => bands, scramble on; fused log-softmax
+    (64, 64, 8),     # 64 tiles, nchunk 1: 8 tiles per XCD => bands without the scramble
+    (24, 40, 64),    # 15 tiles, nchunk 8 (ceil(64 / 16) = 4 stops it): 120 workgroups, 15 % 8 != 0, 120 % 8 == 0 => (tile, chunk) list
+    (17, 23, 5),     # 9 tiles, nchunk 1: 9 workgroups => plain order
+])
+def test_costvol_quad_writes_every_output_exactly_once(h, w, D):
+    """The comparisons above allocate their outputs with torch.empty: memory recycled from an earlier identical call can hide a
+    tile that a wrong blockIdx -> (tile, chunk) map never writes (and another it writes twice).  Here the C entry gets buffers
+    pre-filled with NaN, for cost + logp and for logp alone (the raw costs are parked in out_logp): no NaN may remain and the
+    bits equal ops.costvol's, on the smallest grid that reaches each branch of the map."""
+    from neuralrgbd_amd import _lib
+    ops = _ops()
+    V, C = 2, 67
+    cam = camera.scannet_intrinsics(w, h)
+    rng = np.random.RandomState(41)
+    feat_ref = rng.standard_normal((C, h, w)).astype(np.float32)
+    feat_src = rng.standard_normal((V, C, h, w)).astype(np.float32)
+    poses = synth.random_poses(rng, V, rot_sigma=0.02, trans_sigma=0.05)
+    KR, Kt = co.homography_terms(cam["intrinsic_M_cuda"].numpy(), poses[:, :3, :3], poses[:, :3, 3])
+    cx, cy = float(cam["intrinsic_M"][0, 2]), float(cam["intrinsic_M"][1, 2])
+    tex = ops.pack_nhwc(_dev(np.concatenate([feat_src, feat_ref[None]], 0)))
+    ref, src = tex[V].contiguous(), tex[:V].contiguous()
+    KRd, Ktd, rays, dc = _dev(KR).reshape(V, 9), _dev(Kt), _dev(cam["unit_ray_array_2D"].numpy()), _dev(np.linspace(0.1, 5, D))
+    want_cost, want_lp = ops.costvol(ref, src, KRd, Ktd, rays, dc, cx, cy, 10.0, C, want_cost=True, want_logp=True, generation="quad")
+    torch.cuda.synchronize()
+    p = lambda t: ctypes.c_void_p(0 if t is None else t.data_ptr())
+    for with_cost in (True, False):
+        cost = torch.full((D, h, w), float("nan"), device=DEV) if with_cost else None
+        lp = torch.full((D, h, w), float("nan"), device=DEV)
+        rc = _lib.load().nrgbd_costvol_fwd_gen(p(ref), p(src), p(KRd), p(Ktd), p(rays), p(dc), cx, cy, 10.0, ops.DIST["L2"], 0,
+                                               p(cost), p(lp), V, C, src.shape[-1], D, h, w, ops.GENERATION["quad"],
+                                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, "nrgbd_costvol_fwd_gen")
+        torch.cuda.synchronize()
+        assert not torch.isnan(lp).any()
+        assert torch.equal(lp, want_lp)
+        if with_cost:
+            assert not torch.isnan(cost).any()
+            assert torch.equal(cost, want_cost)
+
+
 def test_costvol_generation_errors():
     """An explicit generation that does not support the shape is refused (NRGBD_E_SHAPE), never substituted."""
     from neuralrgbd_amd import _lib
