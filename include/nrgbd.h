@@ -52,8 +52,9 @@ extern "C" {
  * no existing entry changed.  0.7: nrgbd_bn_small_stats (the SPP branches' BatchNorm statistics) is new; no existing entry changed.
  * 0.8: nrgbd_dpv_keyframe_maps (the LBA driver's depth / confidence maps in one launch) is new; no existing entry changed.
  * 0.9: nrgbd_costvol_bwd_det and nrgbd_costvol_bwd_det_workspace (the bit-reproducible cost-volume backward) are new; no existing
- * entry changed. */
-#define NRGBD_INTERFACE_VERSION "0.9"
+ * entry changed.  0.10: nrgbd_warp_volume_cl (the K-Net input volume for temporal windows of 3, 5 and 7 frames, padded to whole
+ * 16-channel blocks) is new, and nrgbd_conv3d_wgrad_f32 also takes Cin = 32; no existing entry changed. */
+#define NRGBD_INTERFACE_VERSION "0.10"
 const char* nrgbd_version(void);
 const char* nrgbd_strerror(int code);
 
@@ -228,6 +229,24 @@ int nrgbd_warp_volume(const float* src, long sv, long sc, long sy, long sx,
                       const float* bv_cur, const float* bv_pred,
                       float* out, int V, int Cs, int D, int h, int w, int channels_last,
                       void* stream);
+
+/*
+ * nrgbd_warp_volume_cl — the K-Net input volume of any temporal window, channels-last and zero-padded to Cp channels.
+ * Replaces: models/KVNET.py:147-166 (the warp of the 1/4-resolution source images to the reference view for every candidate and
+ * the torch.cat of :163-166) for t_win_r = 1, 2, 3 (V = 2, 4, 6 source views; the reference's --t_win).
+ *   arguments as nrgbd_warp_volume; ref, bv_cur and bv_pred are required
+ *   out [D][h][w][Cp]: channels 0 .. C-1 (C = V*Cs + Cs + 1) in the order of nrgbd_warp_volume — the sources in order, the
+ *        reference, bv_cur - bv_pred at channel C-1 —, channels C .. Cp-1 exactly 0.  Cp % 4 == 0, Cp >= C (NRGBD_E_SHAPE otherwise).
+ * The first K-Net layer runs at Cp = 16 ceil(C / 16) with zero weights in the padding (16 / 16 / 32 for V = 2 / 4 / 6).  At that Cp,
+ * with Cs = 3, V in {2, 4, 6}, channel strides of 1 and 16-byte aligned texels and output, one lane assembles a voxel from 16-byte
+ * loads and stores; any other call takes the general kernel.  The bits do not depend on which kernel ran.
+ */
+int nrgbd_warp_volume_cl(const float* src, long sv, long sc, long sy, long sx,
+                         const float* ref, long rc, long ry, long rx,
+                         const float* KR, const float* Kt, const float* rays,
+                         const float* d_candi, float cx, float cy, int align_corners,
+                         const float* bv_cur, const float* bv_pred,
+                         float* out, int V, int Cs, int Cp, int D, int h, int w, void* stream);
 
 /*
  * nrgbd_dpv_resample — PREDICT step: rigid 3-D resample of the DPV into the next frame.
@@ -415,7 +434,7 @@ int nrgbd_conv3d_cout1_wgrad_f32(const float* x, const float* gy, float* dw, voi
  * nrgbd_conv3d_wgrad_f32 — weight gradient of the 3x3x3 convolution (training):
  *   dW[co][ci][kd][kh][kw] = sum_voxels gy[v][co] * x[v + tap][ci]      (x zero outside the volume)
  * Replaces what autograd/MIOpen compute for nn.Conv3d.weight.grad in models/basic.py:71-94.
- *   x [D][H][W][Cin], gy [D][H][W][64] channels-last; dw [64][Cin][3][3][3] (torch layout, overwritten);
+ *   x [D][H][W][Cin] (Cin = 16, 32 or 64), gy [D][H][W][64] channels-last; dw [64][Cin][3][3][3] (torch layout, overwritten);
  *   partial: scratch of nrgbd_conv3d_wgrad_workgroups() * 27 * 64 * Cin floats.
  * The data gradient needs no new kernel: it is nrgbd_conv3d_3x3x3_f32 applied to gy with the weights
  * transposed (cin <-> cout) and flipped in all three tap axes.

@@ -39,6 +39,8 @@ SIGNATURES = {
     "nrgbd_bn_cl_bwd": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _L, _I, _P]),
     "nrgbd_warp_volume": (_I, [_P, _L, _L, _L, _L, _P, _L, _L, _L, _P, _P, _P, _P, _F, _F, _I,
                                _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "nrgbd_warp_volume_cl": (_I, [_P, _L, _L, _L, _L, _P, _L, _L, _L, _P, _P, _P, _P, _F, _F, _I,
+                                  _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "nrgbd_dpv_resample": (_I, [_P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _F, _F, _P, _I, _I, _I, _P]),
     "nrgbd_dpv_resample_to": (_I, [_P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _F, _F, _P, _I, _I, _I, _I, _P]),
     "nrgbd_dpv_keyframe_maps": (_I, [_P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _F, _F, _P, _P, _P, _P, _I, _I, _I, _I, _P]),

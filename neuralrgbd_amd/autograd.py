@@ -138,23 +138,29 @@ class Conv3dCL(torch.autograd.Function):
     the fp32 matrix cores: forward = csrc/wino_dw.hip / wino_pc.hip (64 -> 64 layers, Winograd domain) / csrc/conv3d.hip; data gradient = the
     same kernel on the output gradient with transposed + flipped weights; weight gradient = csrc/conv3d_wgrad.hip.
 
-    x [D,H,W,Cin] (Cin in {16, 64}), w [64,Cin,3,3,3] -> y [D,H,W,64].
+    x [D,H,W,Cin] (Cin in {16, 32, 64}), w [64,C,3,3,3] -> y [D,H,W,64].  C < Cin (the K-Net's first layer at a window of 3 or 7
+    frames: 10 -> 16, 22 -> 32): x carries zeros in channels C .. Cin-1, the weight streams are packed from w zero-padded to Cin, and
+    the weight gradient of the padded rows is dropped — the parameter and its .grad keep the shape [64,C,3,3,3].
     """
 
     # Candidate kernels in order of preference (ops.conv3d_kernel holds the table and the reasons).  A/B: drop "dw4" from all three
     kernels = ("dw4", "dw", "pc", "direct")           # the 64 -> 64 layers, both directions
     kernels_first = ("dw4", "direct")                 # the 16 -> 64 first layer, forward
     kernels_first_dgrad = ("dw4", "dw", "direct")     # ... its data gradient: a 64 -> 64 (16 real) layer on the output gradient
+    kernels_first32 = ("dw4", "dw", "pc")             # the first layer at 32 inputs (a 7-frame window), forward: conv3d.hip has no 32-input form
 
     @staticmethod
     def _conv(x, w, transposed=False, packed=None, key=None):
         """y = conv(x, w) (transposed: with w's data-gradient weights): choose the kernel, fetch its weight stream, launch.
         packed: (kind, stream) of this call if the caller already has it; key: pack_cache key of the layer."""
-        cin = w.shape[1]
-        kind = ops.conv3d_kernel(*x.shape, 64, Conv3dCL.kernels if cin == 64 else Conv3dCL.kernels_first_dgrad if transposed else Conv3dCL.kernels_first)
+        cin = w.shape[1] if transposed else x.shape[-1]               # forward: the width of x (w zero-padded to it)
+        kind = ops.conv3d_kernel(*x.shape, 64, Conv3dCL.kernels if cin == 64 else Conv3dCL.kernels_first_dgrad if transposed
+                                 else Conv3dCL.kernels_first32 if cin == 32 else Conv3dCL.kernels_first)
 
         def stream():
             wf = w.contiguous()
+            if not transposed and cin != w.shape[1]:
+                wf = torch.cat((wf, wf.new_zeros(64, cin - w.shape[1], 3, 3, 3)), dim=1)
             if transposed:                                            # as a forward layer of THIS call
                 wf = w.transpose(0, 1).flip(2, 3, 4)                  # [Cin, 64, 3,3,3]: correlation with the flipped kernel
                 if cin < 64:                                          # the kernels produce 64 outputs: pad, then slice
@@ -198,15 +204,19 @@ class Conv3dCL(torch.autograd.Function):
         gx = gw = None
         if ctx.needs_input_grad[1]:
             gw = ops.conv3d_wgrad(x.contiguous(), gy)
+            if gw.shape[1] != w.shape[1]:                             # x zero-padded: the padded rows are dropped, never stored
+                gw = gw[:, :w.shape[1]].contiguous()
         if ctx.needs_input_grad[0]:
             c = ctx.grad_channel
             if c is not None and w.shape[0] == 64:
                 # gx[v][c] = sum_co sum_tap gy[v - off(tap)][co] w[co][c][tap]: the 64 -> 1 kernel on gy with the taps mirrored
                 w_tm = _cached(ctx.key, ("c1t", c), lambda: w.detach()[:, c].reshape(64, 27).flip(1).t().contiguous())
-                gx = gy.new_zeros(gy.shape[:3] + (w.shape[1],))
+                gx = gy.new_zeros(gy.shape[:3] + (x.shape[-1],))
                 gx[..., c] = ops.conv3d_cout1(gy, w_tm)
             else:
                 gx = Conv3dCL._conv(gy, w, transposed=True, packed=None if bwd is None else (ctx.kind, bwd), key=ctx.key)
+                if gx.shape[-1] != x.shape[-1]:                       # x zero-padded: the padding carries no gradient
+                    gx = torch.cat((gx, gx.new_zeros(gx.shape[:3] + (x.shape[-1] - gx.shape[-1],))), dim=-1)
         return gx, gw, None, None
 
 

@@ -41,11 +41,11 @@ struct WgradArgs {
 
 constexpr int kWThreads = 256;
 
-template <int CSTAGE>     // input channels a workgroup stages: 32 (Cin = 64) or 16 (the first layer)
+template <int CSTAGE>     // input channels a workgroup stages: 32 (Cin = 64: four quadrants; Cin = 32: two) or 16 (Cin = 16)
 __global__ __launch_bounds__(kWThreads, 2) void conv3d_wgrad_kernel(const WgradArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];  // [kWHalo][kWSV]
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int nci = a.Cin >> 4;                       // ci blocks (1 or 4)
+    const int nci = a.Cin >> 4;                       // ci blocks (1, 2 or 4)
     constexpr int cstage = CSTAGE;
     constexpr int kWSV = CSTAGE + 8;                  // LDS voxel stride (floats)
     const int cib = wv & 1, cob = wv >> 1;            // this wave's ci block and co block inside the quadrant
@@ -274,14 +274,14 @@ extern "C" int nrgbd_conv3d_wgrad_f32(const float* x, const float* gy, float* pa
                                       int W, int Cin, void* stream) {
     using namespace nrgbd;
     if (!x || !gy || !partial || !dw) return NRGBD_E_NULL;
-    if (D <= 0 || H <= 0 || W <= 0 || (Cin != 16 && Cin != 64)) return NRGBD_E_SHAPE;
+    if (D <= 0 || H <= 0 || W <= 0 || (Cin != 16 && Cin != 32 && Cin != 64)) return NRGBD_E_SHAPE;
     WgradArgs a{x, gy, partial, D, H, W, Cin};
     const size_t lds = (size_t)kWHalo * ((Cin < 32 ? Cin : 32) + 8) * sizeof(float);  // 69,120 B (Cin = 64): two workgroups per CU
     hipError_t e;
-    if (Cin >= 64) {
+    if (Cin >= 32) {   // Cin = 32 (the first layer of a 7-frame window, 22 channels padded): the two co halves of ONE 32-channel stage
         e = set_max_dynamic_lds(reinterpret_cast<const void*>(&conv3d_wgrad_kernel<32>), (int)lds);
         if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(conv3d_wgrad_kernel<32>, dim3(kWRanges, 4), dim3(kWThreads), lds, (hipStream_t)stream, a);
+        hipLaunchKernelGGL(conv3d_wgrad_kernel<32>, dim3(kWRanges, Cin / 16), dim3(kWThreads), lds, (hipStream_t)stream, a);
     } else {
         e = set_max_dynamic_lds(reinterpret_cast<const void*>(&conv3d_wgrad_kernel<16>), (int)lds);
         if (e != hipSuccess) return (int)e;

@@ -7,7 +7,7 @@ checkpoints work unchanged.  What differs is the execution: the geometry between
 convolutions runs in hand-written gfx950 kernels (neuralrgbd_amd.ops):
 
     features --pack_nhwc--> texels --costvol (warp+cost+log-softmax, 1 launch)--> BV_cur
-    texels[RGB] --warp_volume (warp + K-Net input assembly, 1 launch)--> [1,16,D,h,w]
+    texels[RGB] --warp_volume (warp + K-Net input assembly, 1 launch)--> [1,16,D,h,w]   (t_win_r 1 / 2 / 3: 16 / 16 / 32 channels)
     K-Net gain + BV_predict --logsoftmax_d--> DPV
 
 so the [D,C,h,w] warped feature tensors, the repeat/transpose/cat temporaries and the per-call
@@ -215,26 +215,36 @@ class KVNET(nn.Module):
         # warp kernel's gathers touched its own cache line; at 16 B per texel four neighbouring taps share one
         rgb4 = measured["rgb4"] if (measured["rgb4"] is not None and texels.shape[-1] == F_dim + 4) else texels[..., F_dim:].contiguous()
         rgb_src, rgb_ref, Cp = rgb4[:V], rgb4[V], rgb4.shape[-1]
-        fused = (not torch.is_grad_enabled()) and self.kv_net.in_channels == 16 and self.KVNet_feature_dim == 64 \
+        # the K-Net input: C = 3 (V + 1) + 1 channels (10 / 16 / 22 for windows of 3 / 5 / 7 frames) in a voxel of whole 16-channel
+        # blocks (16 / 16 / 32), zeros in the padding — in the volume here, in the packed weights of dres0.0 where they are packed
+        C_in = self.kv_net.in_channels
+        C_pad = nets.padded_channels(C_in)
+        has_kernels = C_in in (10, 16, 22) and C_in == 3 * V + 4 and self.KVNet_feature_dim == 64
+        fused = (not torch.is_grad_enabled()) and has_kernels \
             and not self.kv_net.if_normalize and self.kv_net.up_sample_ratio is None
         warp_args = (rgb_src, (h * w * Cp, 1, w * Cp, Cp), rgb_ref, (1, w * Cp, Cp), KR, Kt, rays,
                      warp_homo._d_candi_dev(self.d_candi, dev), cx, cy, V, 3, h, w)
         if fused:   # inference: hand-written MFMA conv3d stack on the channels-last volume
             volume = ops.warp_volume(*warp_args, bv_cur=BV_cur[0], bv_pred=BV_predict[0],
-                                     align_corners=self.d_net.align_corners, channels_last=True)
+                                     align_corners=self.d_net.align_corners, channels_last=True, pad_channels=C_pad)
             gain = self.kv_net.forward_channels_last(volume)                # [D,h,w]
             DPV = ops.logsoftmax_d(gain, BV_predict[0]).unsqueeze(0)        # UPDATE
         else:       # autograd path (training): the warped RGB is constant, BV_cur - BV_predict carries the gradient
-            warped = ops.warp_volume(*warp_args, align_corners=self.d_net.align_corners)   # [15,D,h,w]
-            volume = torch.cat((warped, BV_cur - BV_predict), dim=0)                       # [16,D,h,w]
-            if self.kv_net.in_channels == 16 and self.KVNet_feature_dim == 64 and torch.is_grad_enabled():
+            warped = ops.warp_volume(*warp_args, align_corners=self.d_net.align_corners)   # [3V+3,D,h,w]
+            volume = torch.cat((warped, BV_cur - BV_predict), dim=0)                       # [C_in,D,h,w]
+            if has_kernels and torch.is_grad_enabled():
+                if C_pad != C_in:                                                          # zero channels up to whole 16-channel blocks
+                    volume = torch.cat((volume, volume.new_zeros((C_pad - C_in,) + tuple(volume.shape[1:]))), dim=0)
                 gain = self.kv_net.forward_channels_last_autograd(volume.permute(1, 2, 3, 0).contiguous(),
-                                                                  grad_channel=volume.shape[0] - 1).unsqueeze(0)   # only BV_cur - BV_predict
+                                                                  grad_channel=C_in - 1).unsqueeze(0)   # only BV_cur - BV_predict
             elif volume.is_cuda:
-                # a K-Net the kernels have no form for (KVNet_feature_dim != 64, a window other than 5 frames, depth up-sampling:
-                # no script of the reference selects one): an error, never a silent hand-over to MIOpen
-                raise nets._no_kernel("this K-Net (%d input channels, feature width %d, if_normalize %s, up_sample_ratio %s)" % (
-                    self.kv_net.in_channels, self.KVNet_feature_dim, self.kv_net.if_normalize, self.kv_net.up_sample_ratio))
+                # a K-Net the kernels have no form for (KVNet_feature_dim != 64, a window other than 3 / 5 / 7 frames, depth
+                # up-sampling: no script of the reference selects one): an error, never a silent hand-over to MIOpen
+                raise nets._no_kernel("this K-Net (%d input channels for %d source views, feature width %d, if_normalize %s, "
+                                      "up_sample_ratio %s): windows of 3, 5 and 7 frames (t_win_r 1, 2, 3: 10, 16, 22 channels) at "
+                                      "feature width 64, without if_normalize and depth up-sampling" % (
+                                          self.kv_net.in_channels, V, self.KVNet_feature_dim, self.kv_net.if_normalize,
+                                          self.kv_net.up_sample_ratio))
             else:
                 gain = torch.squeeze(self.kv_net(volume.unsqueeze(0)), dim=1)   # torch modules on the host (structure tests)
             if gain.is_cuda and gain.dtype == torch.float32:

@@ -90,16 +90,32 @@ _PACKERS = {
 }
 
 
-def _packed(owner, conv, kind, mult=1.0):
+def padded_channels(c):
+    """Width a 3x3x3 layer with c inputs runs at: whole 16-channel blocks (the K-Net's first layer: 10 / 16 / 22 channels for windows of
+    3 / 5 / 7 frames -> 16 / 16 / 32).  The input carries zeros and the packed weights zero rows in the padding."""
+    return -(-int(c) // 16) * 16
+
+
+def pad_input_channels(w, cin):
+    """w [Cout, C, ...] -> [Cout, cin, ...] with zero weights for input channels C .. cin-1 (w itself when cin == C)."""
+    if cin == w.shape[1]:
+        return w
+    return torch.cat((w, w.new_zeros((w.shape[0], cin - w.shape[1]) + tuple(w.shape[2:]))), dim=1)
+
+
+def _packed(owner, conv, kind, mult=1.0, cin=None):
     """Weight stream of `conv` for the kernel family `kind` (_PACKERS), of mult * w (mult = 2^k: the clamped-FMA forms of wino_dw.hip /
-    wino_dw4.hip, whose input arrives scaled by 2^-k); cached on `owner`, re-packed only when the weight changes."""
+    wino_dw4.hip, whose input arrives scaled by 2^-k); cached on `owner`, re-packed only when the weight changes.
+    cin: the input width the layer runs at (padded_channels; None = the module's own): the stream is packed from the weight
+    zero-padded to it, the parameter keeps its shape."""
     from . import ops
     cache = owner.__dict__.setdefault("_wp_cache", {})
     w = conv.weight
-    key = (w.data_ptr(), w._version, str(w.device), float(mult))
+    cin = int(w.shape[1] if cin is None else cin)
+    key = (w.data_ptr(), w._version, str(w.device), float(mult), cin)
     hit = cache.get((kind, id(conv)))
     if hit is None or hit[0] != key:
-        wc = w.detach().contiguous()
+        wc = pad_input_channels(w.detach(), cin).contiguous()
         hit = (key, _PACKERS[kind](ops, wc if mult == 1.0 else wc * float(mult)))
         cache[(kind, id(conv))] = hit
     return hit[1]
@@ -578,11 +594,13 @@ class KalmanGainNet(_PackedWeightsMixin, nn.Module):
     # are edits of these tuples: tools/knet_ab.py drops "dw4" (every layer on wino_dw.hip, the form of round 5), for all layers or for the
     # 16 -> 64 first layer alone (0.62 -> 0.54 ms at config B with it)
     kernels = {16: ("dw4", "dw", "pc", "direct"), 64: ("dw4", "dw", "pc", "direct")}
+    kernels32 = ("dw4", "dw", "pc")     # the first layer of a 7-frame window (22 channels in two 16-channel blocks): conv3d.hip has no 32-input form
     _GENERATIONS = {None: None, "wino_pc": ("pc", "direct"), "direct": ("direct",)}   # forward_channels_last(generation=): tests only
     _split_residual = True      # measured (tools/knet_ab.py, NO_SPLIT=1): K-Net 25.37 -> 24.67 ms at config B when introduced, 22.74 -> 22.40 after the shared strips; identical bits
 
     def forward_channels_last(self, vol, generation=None):
-        """Inference on the hand-written kernels: vol [D,H,W,Cin] (channels-last) -> gain [D,H,W].
+        """Inference on the hand-written kernels: vol [D,H,W,Cp] (channels-last; Cp = padded_channels(in_channels), zeros in
+        channels in_channels .. Cp-1) -> gain [D,H,W].
 
         One fused pass per layer: conv on the fp32 matrix cores, BatchNorm statistics in its epilogue, normalise + affine +
         ReLU + residual applied by the next layer's loader.  Same graph as forward() (basic.py:113-132):
@@ -599,17 +617,18 @@ class KalmanGainNet(_PackedWeightsMixin, nn.Module):
         if generation not in self._GENERATIONS:
             raise ValueError("generation: None | 'wino_pc' | 'direct'")
         D, H, W, C = vol.shape
-        if C != self.in_channels:
+        if C != padded_channels(self.in_channels):
             raise AssertionError("Input volume should have correct # of channels !")
         L = self._layers()
         count = D * H * W
+        cin = lambda i: C if i == 0 else L[i][0].in_channels      # the width layer i runs at: only the first is padded
 
         def choose(i, fused_res=False):
             conv = L[i][0]
-            cands = self._GENERATIONS[generation] or self.kernels.get(conv.in_channels, ("direct",))
+            cands = self._GENERATIONS[generation] or (self.kernels32 if cin(i) == 32 else self.kernels.get(cin(i), ("direct",)))
             if fused_res:                       # wino_dw4.hip has no residual form
                 cands = tuple(k for k in cands if k != "dw4")
-            return ops.conv3d_kernel(D, H, W, conv.in_channels, conv.out_channels, cands)
+            return ops.conv3d_kernel(D, H, W, cin(i), conv.out_channels, cands)
 
         def run(i, x, x_ss, x_relu, res=None, materialize=False):
             conv, bn = L[i]
@@ -635,7 +654,7 @@ class KalmanGainNet(_PackedWeightsMixin, nn.Module):
             # layer's BatchNorm bounds its output, the weight stream carries the inverse of the unit
             unit = _relu_unit(self, L[i - 1][1], count) if (kind in ("dw4", "dw") and i > 0 and x_ss is not None and x_relu and res is None
                                                               and not materialize) else 0.0
-            wp = _packed(self, conv, kind, 1.0 / unit if unit else 1.0)
+            wp = _packed(self, conv, kind, 1.0 / unit if unit else 1.0, cin(i))
             if kind == "dw4":
                 y, st = ops.conv_wino_dw4(x, wp, 64, x_ss=x_ss, x_relu=x_relu, want_stats=_needs_stats(bn), x_unit=unit)
             elif kind == "dw":
@@ -674,7 +693,8 @@ class KalmanGainNet(_PackedWeightsMixin, nn.Module):
     def forward_channels_last_autograd(self, vol, grad_channel=None):
         """Training path: same graph on channels-last activations with the convolutions (forward, data gradient and
         weight gradient) on the hand-written matrix-core kernels (autograd.Conv3dCL); BatchNorm3d / ReLU / adds are
-        ordinary torch autograd ops applied in place of the layout (no NCDHW round trips).  vol [D,H,W,Cin] -> [D,H,W].
+        ordinary torch autograd ops applied in place of the layout (no NCDHW round trips).  vol [D,H,W,Cin] -> [D,H,W]; Cin = the
+        module's in_channels or that padded with zero channels to padded_channels(in_channels).
         grad_channel: the ONE input channel whose gradient the caller needs (KVNET: the last, BV_cur - BV_predict; the others are
         warped images) — the other channels' gradient is then returned as zeros; None: all of them."""
         from .autograd import Conv3dCL, Conv3dCout1CL, batch_norm_act_cl

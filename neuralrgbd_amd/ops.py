@@ -160,9 +160,12 @@ def costvol_bwd(ref_nhwc, src_nhwc, KR, Kt, rays, d_candi, cx, cy, sigma, C, g_c
 
 
 def warp_volume(src, src_strides, ref, ref_strides, KR, Kt, rays, d_candi, cx, cy, V, Cs, h, w,
-                bv_cur=None, bv_pred=None, align_corners=False, channels_last=False):
+                bv_cur=None, bv_pred=None, align_corners=False, channels_last=False, pad_channels=None):
     """Plane-sweep warp with samples kept (+ K-Net input assembly) -> [V*Cs (+Cs) (+1), D, h, w]
     (or [D, h, w, channels] with channels_last=True, the layout conv3d consumes).
+    pad_channels = Cp (channels_last with ref and bv only): the voxel is Cp floats wide, zeros behind the assembly — the K-Net input
+    of any temporal window at whole 16-channel blocks.  V = 4 at Cp = 16 is nrgbd_warp_volume's own fast form; every other
+    window goes to nrgbd_warp_volume_cl.
 
     `src` / `ref` are any CUDA fp32 tensors; `src_strides` = (view, channel, y, x) and
     `ref_strides` = (channel, y, x) element strides from their data pointers.
@@ -183,6 +186,17 @@ def warp_volume(src, src_strides, ref, ref_strides, KR, Kt, rays, d_candi, cx, c
         bv_cur = _need(bv_cur, "bv_cur").reshape(D, h, w)
         bv_pred = _need(bv_pred, "bv_pred").reshape(D, h, w)
         n_ch += 1
+    if pad_channels is not None and int(pad_channels) != n_ch:
+        if not channels_last or ref is None or bv_cur is None or pad_channels < n_ch or pad_channels % 4:
+            raise ValueError("warp_volume: pad_channels = %r needs channels_last, ref and bv_cur, a multiple of 4 >= %d" % (pad_channels, n_ch))
+        out = torch.empty((D, h, w, int(pad_channels)), dtype=torch.float32, device=src.device)
+        with torch.cuda.device(src.device):
+            rc = _lib.load().nrgbd_warp_volume_cl(_p(src), *[int(s) for s in src_strides], _p(ref),
+                                                  *[int(s) for s in ref_strides], _p(KR), _p(Kt), _p(rays),
+                                                  _p(d_candi), float(cx), float(cy), int(bool(align_corners)),
+                                                  _p(bv_cur), _p(bv_pred), _p(out), V, Cs, int(pad_channels), D, h, w, _stream(src))
+        _lib.check(rc, "nrgbd_warp_volume_cl")
+        return out
     shape = (D, h, w, n_ch) if channels_last else (n_ch, D, h, w)
     out = torch.empty(shape, dtype=torch.float32, device=src.device)
     with torch.cuda.device(src.device):
@@ -663,8 +677,11 @@ def conv_wino_dw4_supported(N, H, W, Cin, Cout):
 def conv3d_kernel(D, H, W, Cin, Cout, candidates):
     """Which kernel runs a channels-last 3x3x3 layer on a [D, H, W, Cin] input: the first of `candidates`, in order, that takes the
     shape.  "dw4" = wino_dw4.hip (6 multiplies per output voxel; D % 4 == 0), "dw" = wino_dw.hip (8; D even) — both whole 8x16 tiles
-    —, "pc" = wino_pc.hip (12; any grid), each for 16 or 64 inputs and 64 outputs; "direct" = conv3d.hip (27) takes everything and
-    ends every search.  Pure host code: this is the one place the choice is written down.  Who passes what:
+    —, "pc" = wino_pc.hip (12; any grid), each for 16, 32 or 64 inputs and 64 outputs; "direct" = conv3d.hip (27) takes every grid at 16
+    or 64 inputs and ends every search.  Cin = 32 (the first layer of a 7-frame window: 22 channels zero-padded) has no direct form:
+    its tuples leave "direct" out, which is also what admits the width — a list that names "direct" is a list for 16 or 64 inputs and
+    answers "direct" for any other width, as it always did —, and a grid none of the three takes (2^30 bytes of input per depth
+    slice) is an NrgbdError.  Pure host code: this is the one place the choice is written down.  Who passes what:
 
       caller                                      Cin  candidates             why not the full list
       K-Net inference (KalmanGainNet.kernels)     any  dw4, dw, pc, direct    -
@@ -679,13 +696,19 @@ def conv3d_kernel(D, H, W, Cin, Cout, candidates):
                                                                               does not
       autograd 16 -> 64 data gradient             64   dw4, dw, direct        (Conv3dCL.kernels_first_dgrad) the layer zero-padded to
                                                                               64 -> 64 on dL/dy; wino_pc.hip was never timed here
+      first layer at 32 inputs, both paths        32   dw4, dw, pc            (KalmanGainNet.kernels32, Conv3dCL.kernels_first32)
+                                                                              conv3d.hip is instantiated for 16 and 64 inputs
     The A/B switches are edits of those tuples (tools/knet_ab.py drops "dw4")."""
     takes = {"dw4": conv_wino_dw4_supported, "dw": conv_wino_dw_supported, "pc": lambda *shape: conv_wino_supported(*shape, 3)}
+    widths = (16, 64) if "direct" in candidates or not candidates else (16, 32, 64)
     for kind in candidates:
-        if kind != "direct" and Cout == 64 and Cin in (16, 64) and takes[kind](D, H, W, Cin, Cout):
+        if kind != "direct" and Cout == 64 and Cin in widths and takes[kind](D, H, W, Cin, Cout):
             return kind
         if kind == "direct":
             break
+    if Cin == 32 and candidates and "direct" not in candidates:
+        raise _lib.NrgbdError("no hand-written kernel for a 3x3x3 layer with 32 inputs on a %d x %d x %d grid (candidates %s)"
+                              % (D, H, W, ", ".join(candidates)))
     return "direct"
 
 
@@ -720,7 +743,7 @@ def conv_wino_dw4(x, w_wino, Cout, x_ss=None, x_relu=False, want_stats=True, x_u
 
 
 def conv3d_wgrad(x, gy):
-    """Weight gradient of the channels-last 3x3x3 convolution: x [D,H,W,Cin], gy [D,H,W,64] -> dW [64,Cin,3,3,3]."""
+    """Weight gradient of the channels-last 3x3x3 convolution: x [D,H,W,Cin] (Cin 16, 32 or 64), gy [D,H,W,64] -> dW [64,Cin,3,3,3]."""
     x = _need(x, "x")
     D, H, W, Cin = x.shape
     gy = _need(gy, "gy", (D, H, W, 64))
