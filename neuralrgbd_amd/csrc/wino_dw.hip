@@ -36,8 +36,8 @@
 //
 // In wino_dw.hpp, shared with wino_dw4.hip: the strip / stash / table constants, DwTile + dw_decode<2>, the serpentine order dw_cb
 // (this file's knob: NRGBD_DW_SERP), the weight packer (dw_pack<4>) and the host helpers dw_workgroups / dw_check / dw_unit_ok.
-// Here: the kernel itself — and, still in two copies with wino_dw4.hip, the tile-list split, the table load, the consumers' MFMA
-// stage / plane inverse / statistics and the producers' item map / book / plane transform (wino_dw.hpp says why).
+// Here: the kernel itself — and, still in two copies with wino_dw4.hip, the consumers' MFMA stage / plane inverse / statistics and
+// the producers' item map / book / plane transform (wino_dw.hpp says why); the tile-list split and the table load are wino_pc.hpp's.
 #include <type_traits>
 
 #include "wino_dw.hpp"
@@ -88,26 +88,14 @@ __global__ __launch_bounds__(512) void conv_wino_dw_kernel(const WinoPcArgs a) {
 #endif
 
     int first, step, end;
-    {
-        const int G = (int)gridDim.x, b = (int)blockIdx.x;
-        if ((G & 7) == 0) {
-            const int xc = b & 7;
-            first = (int)(((long)a.ntiles * xc) >> 3) + (b >> 3);
-            end = (int)(((long)a.ntiles * (xc + 1)) >> 3);
-            step = G >> 3;
-        } else { first = b; end = a.ntiles; step = G; }
-    }
+    pc_tile_share(a.ntiles, first, step, end);
     if (first >= end) return;                  // a workgroup without tiles (uniform)
     const int count = (end - first + step - 1) / step;
     const unsigned plane = (unsigned)((size_t)a.H * a.W * a.Cin);
     // The per-channel (scale, shift) pairs go to LDS once (identity where the pointer is null).  Loading a stage's pairs from
     // global memory with its raw words — as wino_pc.hip does — puts them FIRST in the refill's queue, and the compiler moves them
     // into their home registers immediately: an s_waitcnt right behind the loads, i.e. one exposed L2 round trip per unit.
-    for (int i = tid; i < 2 * a.Cin; i += 512) {
-        const int j = pc_ss_slot(i);      // pairs as the packed FMAs take them: (s0, s1, t0, t1 | s2, s3, t2, t3) per 4 channels
-        ssl[j] = (a.x_ss ? a.x_ss[i] : ((i & 1) ? 0.f : 1.f)) * (CLAMP ? a.x_unit : 1.f);
-        ssl[2 * a.Cin + j] = (RES && a.res_ss) ? a.res_ss[i] : ((i & 1) ? 0.f : 1.f);
-    }
+    pc_load_ss_table<true>(ssl, a.Cin, a.x_ss, RES ? a.res_ss : nullptr, CLAMP ? a.x_unit : 1.f);
     __syncthreads();
 
     if (wave >= 4) {
@@ -171,7 +159,7 @@ __global__ __launch_bounds__(512) void conv_wino_dw_kernel(const WinoPcArgs a) {
                                 // the weight line of the point 7 ahead is requested HERE, in the second MFMA gap of the point, not at its top beside the two
                                 // LDS reads: a vector-memory instruction costs the wave ~50 issue cycles, and three memory instructions in one gap let the
                                 // matrix pipe run dry (tools/probes/mfma_stream_probe.hip: 78.5 -> 85.4 % busy)
-                                if (e == NRGBD_WPOS) Bn[(xi + kPcBD) % kPcNB] = xi + kPcBD < 16 ? wcur[(xi + kPcBD) * 256] : wnx[(xi + kPcBD - 16) * 256];
+                                if (e == kPcWPos) Bn[(xi + kPcBD) % kPcNB] = xi + kPcBD < 16 ? wcur[(xi + kPcBD) * 256] : wnx[(xi + kPcBD - 16) * 256];
                                 __builtin_amdgcn_sched_barrier(0);
                             }
                             if (xi == 14) {

@@ -3,8 +3,8 @@
 //   geometry   strip / stash / table constants, DwTile + dw_decode<slices per tile>, the serpentine channel-block order dw_cb
 //   weights    the packer conv_wino_dw_pack_kernel<POINTS> with the depth matrices DwDepth<POINTS>, and its entry dw_pack
 //   host       dw_workgroups (persistent workgroups), dw_check (the launchers' shared refusals), dw_unit_ok
-// NOT here, although both kernels carry them token for token: the XCD-aware split of the tile list, the (scale, shift) table load, the
-// consumers' MFMA stage,
+// From wino_pc.hpp, shared with wino_pc.hip as well: the XCD-aware split of the tile list (pc_tile_share) and the (scale, shift) table
+// load (pc_load_ss_table).  NOT here, although both kernels carry them token for token: the consumers' MFMA stage,
 // plane inverse transform and statistics, the producers' item map, book, activation and plane transform.  Both kernels run with the
 // register file full; moved into functions of this header (arrays by reference, every scheduling barrier in place) each of them
 // changed the kernels' register allocation or instruction order, and a changed stream needs a timing gate.

@@ -84,22 +84,11 @@ __global__ __launch_bounds__(512) void conv_wino_dw4_kernel(const WinoD4Args aa)
     const int NS = 6 * ncb;                            // stages per tile (four output slices)
 
     int first, step, end;
-    {
-        const int G = (int)gridDim.x, b = (int)blockIdx.x;
-        if ((G & 7) == 0) {
-            const int xc = b & 7;
-            first = (int)(((long)a.ntiles * xc) >> 3) + (b >> 3);
-            end = (int)(((long)a.ntiles * (xc + 1)) >> 3);
-            step = G >> 3;
-        } else { first = b; end = a.ntiles; step = G; }
-    }
+    pc_tile_share(a.ntiles, first, step, end);
     if (first >= end) return;                  // a workgroup without tiles (uniform)
     const int count = (end - first + step - 1) / step;
     const unsigned plane = (unsigned)((size_t)a.H * a.W * a.Cin);
-    for (int i = tid; i < 2 * a.Cin; i += 512) {
-        const int j = pc_ss_slot(i);
-        ssl[j] = (a.x_ss ? a.x_ss[i] : ((i & 1) ? 0.f : 1.f)) * (CLAMP ? a.x_unit : 1.f);
-    }
+    pc_load_ss_table<false>(ssl, a.Cin, a.x_ss, nullptr, CLAMP ? a.x_unit : 1.f);
     __syncthreads();
 
     if (wave >= 4) {
@@ -166,7 +155,7 @@ __global__ __launch_bounds__(512) void conv_wino_dw4_kernel(const WinoD4Args aa)
                                                                                   FIRST && e == 0 ? zero4 : acc[xi][0], 0, 0, 0);
                                 acc[xi][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(An[cur][1][e], Bn[xi % kPcNB][e],
                                                                                   FIRST && e == 0 ? zero4 : acc[xi][1], 0, 0, 0);
-                                if (e == NRGBD_WPOS) Bn[(xi + kPcBD) % kPcNB] = xi + kPcBD < 16 ? wcur[(xi + kPcBD) * 256] : wnx[(xi + kPcBD - 16) * 256];
+                                if (e == kPcWPos) Bn[(xi + kPcBD) % kPcNB] = xi + kPcBD < 16 ? wcur[(xi + kPcBD) * 256] : wnx[(xi + kPcBD - 16) * 256];
                                 __builtin_amdgcn_sched_barrier(0);
                             }
                             if (xi == 14) {            // EARLY stage barrier (wino_dw.hip)

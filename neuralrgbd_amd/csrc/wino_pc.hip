@@ -18,8 +18,7 @@
 //       tiles; the first A operand of the next stage is read before the stage barrier (three V buffers make that legal);
 //       the first k-step of a tile takes a zero C operand (the accumulators are never cleared).
 //   producer waves (waves 0..3: the older waves win the SIMD's VALU arbitration): the 10x18 halo of one 16-channel block is
-//       split over their 256 lanes (3 16-byte words each: every halo word has ONE loader — round 4; until then wave p loaded the
-//       four rows 2p..2p+3 of its tile row into a private strip, 16 rows for a 10-row halo): global -> registers (buffer loads,
+//       split over their 256 lanes (3 16-byte words each: every halo word has ONE loader): global -> registers (buffer loads,
 //       TWO stages ahead, two register sets, the stage's (scale, shift) with them) -> BatchNorm / ReLU / residual, packed and
 //       breadth-first -> the SHARED strip of the stage (two of them alternate); the transform B^T d B per (tile, 16-byte word,
 //       half) -> V[q % 3] of producer wave p = tile row p (8 Winograd tiles) runs one iteration LATER, on the strip the stage
@@ -33,6 +32,17 @@
 //   tiles, depth fastest, so the three slices a 3-D tile needs are shared in that XCD's L2), so a tile's epilogue and the
 //   next tile's first loads overlap with the producers' run-ahead instead of being exposed at every workgroup boundary.
 // LDS: 3 x 32 KB V + 2 x 12.8 KB strips = 122 KB (one workgroup per CU; 2 waves per SIMD, up to 256 VGPRs each).
+//
+// Measured, then removed (the switches and in-kernel timers this file carried until its split into named steps):
+//   * private strips (producer wave p loads halo rows 2p .. 2p+3 into its own 4-row strip, 5 words per lane and stage, transform
+//     in the same iteration behind an lgkmcnt(0)) against the shared strip (3 words per lane, transform one iteration later):
+//     trunk 64 -> 64 layer 91.6 -> 87.9 us, residual + materialise 103 -> 92.9, HALF 32 -> 32 148.5 -> 140.8, HALF res + mat
+//     178.1 -> 164.4 (profiles/r4_knet_producer_diet_ab.txt, 3b).  The shared strip is the only form now.
+//   * producers only / consumers only (ablation bits 1 and 2 of a developer build), trunk 64 -> 64 before the shared strips:
+//     full 106.1 us, consumers only 92.9, producers only 45.6 (same profile); per stage at the K-Net's config B, 10 ns ticks:
+//     consumers mfma 220, barrier 19, epilogue 14; producers publish 118, transform 67, barrier 48 (profiles/r2_pmc_wino.txt).
+//   * the HALF form's consumer clocks (wall_clock64 around the MFMA loop, the stage barrier and the epilogue, 32 -> 32 @
+//     5 x 384 x 512): MFMA loop 65 %, barrier 18 %, epilogue 17 %: there the producers set the pace.
 #include "wino_pc.hpp"
 
 namespace nrgbd {
@@ -47,45 +57,487 @@ namespace nrgbd {
 // alternate with another's; the weight stream is the 64-column one with the upper 32 columns zero (waves 0 / 1 read their two
 // lines of it); statistics rows are (tile, row block).  The producers are unchanged — they now set the pace (a stage's MFMAs
 // take 0.85 us): 2.25x fewer multiplies than conv2d.hip's direct form of these layers.
+// EPI = 1: the R-Net form (bias + LeakyReLU in the epilogue, no prologue, no statistics).  ODD: an odd stage count per tile.
+namespace {
+
+// ======================================================= consumer steps =====================================================
+// A consumer lane (kq, jj): output channel 16 cwv + jj of its column group; register r of row block m = tile 16 m + 4 kq + r.
+struct PcLane {
+    int kq, jj;
+    int msel, cwv;             // HALF: the one row block this wave owns / the wave's 16-column group
+    int a0, a1;                // LDS offsets of the lane's A operands of the two row blocks (+ xi * 512 floats + buffer)
+    unsigned ldy, lane_yoff;   // pixel stride of the output; the lane's part of an output's address (loop-invariant)
+};
+template <bool HALF> using PcAcc = f32x4[16][HALF ? 1 : 2];   // [xi][row block]: written by the first stage of every tile (C operand = 0): never cleared
+
+template <int DIL, int EPI, bool HALF>
+__device__ __forceinline__ PcLane pc_lane(const WinoPcArgs& a, int lane, int wv) {
+    PcLane c;
+    c.kq = lane >> 4; c.jj = lane & 15;
+    c.msel = HALF ? (wv >> 1) : 0;
+    c.cwv = HALF ? (wv & 1) : wv;
+    c.a0 = pc_slot(0, 16 * c.msel + c.jj, c.kq); c.a1 = pc_slot(0, 16 + c.jj, c.kq);
+    c.ldy = (EPI == 1 && a.ldy) ? (unsigned)a.ldy : (unsigned)a.Cout;
+    c.lane_yoff = (unsigned)c.jj + (unsigned)((DIL * 2 * (c.kq >> 1)) * a.W + 8 * (c.kq & 1) * DIL) * c.ldy;
+    return c;
+}
+
+// prime: the first weight lines of the ring (before the opening barriers) ...
+template <bool HALF>
+__device__ __forceinline__ void pc_prime_weights(f32x4 (&Bn)[kPcNB], const f32x4* wt) {
+    constexpr int BD = HALF ? 6 : kPcBD;   // weight lines in flight (HALF requests two per pair of points: an even distance)
+#pragma unroll
+    for (int b = 0; b < BD; ++b) Bn[b] = wt[b * 256];
+}
+// ... and the first four A operands (after them).  A operands run TWO transform points ahead (one point = 256 MFMA cycles < a
+// loaded LDS's latency); HALF: An[pair & 3][point of the pair], two PAIRS ahead
+template <bool HALF>
+__device__ __forceinline__ void pc_prime_a(f32x4 (&An)[4][2], const float* Vb, const PcLane& c) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {   // HALF: points 2i, 2i + 1 of the wave's row block; else point i of both row blocks
+        An[i][0] = *reinterpret_cast<const f32x4*>(Vb + c.a0 + (HALF ? 2 * i : i) * kPcTiles * kCB);
+        An[i][1] = *reinterpret_cast<const f32x4*>(Vb + (HALF ? c.a0 + (2 * i + 1) * kPcTiles * kCB : c.a1 + i * kPcTiles * kCB));
+    }
+}
+
+// one stage = 16 transform points x (2 A reads + 1 weight line + 8 MFMAs) from V buffer Vc (Vn: the next stage's, for its first
+// operands; wcur / wnx: the weight lines of this stage / the next).  FIRST (stage 0 of a tile): the first k-step takes a zero C
+// operand instead of the accumulator, which saves clearing 128 registers per tile.
+template <bool HALF, bool FIRST>
+__device__ __forceinline__ void pc_mfma_stage(PcAcc<HALF>& acc, f32x4 (&An)[4][2], f32x4 (&Bn)[kPcNB], const float* Vc, const float* Vn,
+                                              const f32x4* wcur, const f32x4* wnx, const PcLane& c) {
+    const int a0 = c.a0, a1 = c.a1;
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (HALF) {
+        // a step = the PAIR of transform points (2 xp, 2 xp + 1): 2 A reads (two pairs ahead), 8 MFMAs alternating
+        // between the two accumulators, the weight lines of points 2 xp + 6 and 2 xp + 7 requested in two MFMA gaps
+#pragma unroll
+        for (int xp = 0; xp < 8; ++xp) {
+            const int cur = xp & 3, nxt = (xp + 2) & 3;
+            const float* Vs = xp + 2 < 8 ? Vc : Vn;   // pairs 0, 1 of the next stage: its buffer was completed before the previous barrier
+            const int pn = (xp + 2) & 7;
+            An[nxt][0] = *reinterpret_cast<const f32x4*>(Vs + a0 + (2 * pn) * (kPcTiles * kCB));
+            An[nxt][1] = *reinterpret_cast<const f32x4*>(Vs + a0 + (2 * pn + 1) * (kPcTiles * kCB));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                acc[2 * xp][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(An[cur][0][e], Bn[(2 * xp) % kPcNB][e],
+                                                                      FIRST && e == 0 ? zero4 : acc[2 * xp][0], 0, 0, 0);
+                acc[2 * xp + 1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(An[cur][1][e], Bn[(2 * xp + 1) % kPcNB][e],
+                                                                          FIRST && e == 0 ? zero4 : acc[2 * xp + 1][0], 0, 0, 0);
+                if (e == 1) Bn[(2 * xp + 6) % kPcNB] = 2 * xp + 6 < 16 ? wcur[(2 * xp + 6) * 256] : wnx[(2 * xp + 6 - 16) * 256];
+                if (e == 3) Bn[(2 * xp + 7) % kPcNB] = 2 * xp + 7 < 16 ? wcur[(2 * xp + 7) * 256] : wnx[(2 * xp + 7 - 16) * 256];
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int xi = 0; xi < 16; ++xi) {
+            const int cur = xi & 3, nxt = (xi + 2) & 3;
+            if (xi + 2 < 16) {
+                An[nxt][0] = *reinterpret_cast<const f32x4*>(Vc + a0 + (xi + 2) * (kPcTiles * kCB));
+                An[nxt][1] = *reinterpret_cast<const f32x4*>(Vc + a1 + (xi + 2) * (kPcTiles * kCB));
+            } else {   // the first two operands of the next stage: its buffer was completed before the previous barrier
+                An[nxt][0] = *reinterpret_cast<const f32x4*>(Vn + a0 + (xi + 2 - 16) * (kPcTiles * kCB));
+                An[nxt][1] = *reinterpret_cast<const f32x4*>(Vn + a1 + (xi + 2 - 16) * (kPcTiles * kCB));
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                acc[xi][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(An[cur][0][e], Bn[xi % kPcNB][e], FIRST && e == 0 ? zero4 : acc[xi][0], 0, 0, 0);
+                acc[xi][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(An[cur][1][e], Bn[xi % kPcNB][e], FIRST && e == 0 ? zero4 : acc[xi][1], 0, 0, 0);
+                // the weight line of the point 7 ahead is requested HERE, in the second MFMA gap of the point (kPcWPos = 1), not at its
+                // top beside the two LDS reads: a vector-memory instruction costs the wave ~50 issue cycles, and three memory
+                // instructions in one gap let the matrix pipe run dry (tools/probes/mfma_stream_probe.hip: 78.5 -> 85.4 % busy)
+                if (e == kPcWPos) Bn[(xi + kPcBD) % kPcNB] = xi + kPcBD < 16 ? wcur[(xi + kPcBD) * 256] : wnx[(xi + kPcBD - 16) * 256];
+                __builtin_amdgcn_sched_barrier(0);   // pin the order: the row blocks alternate (no back-to-back dependent MFMAs), the operand streams keep their distances
+            }
+        }
+    }
+}
+
+// The epilogues: inverse transform Y = A^T M A in registers + output (+ bias, LeakyReLU when EPI = 1) + the lane's partial
+// statistics (s1, s2).  Row block m, register r = tile row 2m + (kq >> 1), tile column 4 (kq & 1) + r: the (m, r, a) part of
+// an output's address is uniform -> scalar base (ybase) + 32-bit lane offset stores, no per-store address arithmetic.
+// Interior tile: everything on register PAIRS (tiles r, r+1 of a row block): v_pk_add_f32 / v_pk_fma_f32 halve the epilogue's VALU
+// instructions; a - b is fma(b, -1, a) with an opaque -1 (same rounding; a literal would be folded into two scalar v_sub)
+template <int DIL, int EPI, bool HALF>
+__device__ __forceinline__ void pc_epilogue_interior(const PcAcc<HALF>& acc, const WinoPcArgs& a, const PcLane& c, float* ybase, bool cok,
+                                                     float bval, float& s1, float& s2) {
+    const unsigned ldy = c.ldy, lane_yoff = c.lane_yoff;
+    float neg1 = -1.f;
+    asm volatile("" : "+v"(neg1));
+    const f32x2 n1 = {neg1, neg1};
+    const f32x2 bias2 = {bval, bval};
+    f32x2 S1 = {0.f, 0.f}, S2 = {0.f, 0.f};
+#pragma unroll
+    for (int mi = 0; mi < (HALF ? 1 : 2); ++mi) {
+        const int m = HALF ? c.msel : mi;   // row block: address arithmetic uses m, the register index is mi
+#pragma unroll
+        for (int rp = 0; rp < 2; ++rp) {
+            f32x2 tr[2][4];   // t[a][xi_x] = sum_xi_y A^T[a][xi_y] M[xi_y][xi_x]
+#pragma unroll
+            for (int xx = 0; xx < 4; ++xx) {
+                const f32x2 m0 = rp ? acc[0 + xx][mi].hi : acc[0 + xx][mi].lo, m1 = rp ? acc[4 + xx][mi].hi : acc[4 + xx][mi].lo;
+                const f32x2 m2 = rp ? acc[8 + xx][mi].hi : acc[8 + xx][mi].lo, m3 = rp ? acc[12 + xx][mi].hi : acc[12 + xx][mi].lo;
+                tr[0][xx] = (m0 + m1) + m2;
+                tr[1][xx] = __builtin_elementwise_fma(m3, n1, __builtin_elementwise_fma(m2, n1, m1));   // (m1 - m2) - m3
+            }
+#pragma unroll
+            for (int aa = 0; aa < 2; ++aa) {
+                f32x2 o0 = (tr[aa][0] + tr[aa][1]) + tr[aa][2];
+                f32x2 o1 = __builtin_elementwise_fma(tr[aa][3], n1, __builtin_elementwise_fma(tr[aa][2], n1, tr[aa][1]));
+                if constexpr (EPI == 1) {   // m_submodule.py:18-27: bias, LeakyReLU(0.01) = max(z, 0.01 z)
+                    o0 = o0 + bias2; o1 = o1 + bias2;
+                    if (a.out_lrelu) {
+                        const f32x2 sl = {0.01f, 0.01f};
+                        o0 = __builtin_elementwise_max(o0, o0 * sl); o1 = __builtin_elementwise_max(o1, o1 * sl);
+                    }
+                }
+                float* oa = ybase + ((size_t)(DIL * (4 * m + aa)) * a.W + (size_t)(2 * (2 * rp) * DIL)) * ldy;       // tile r = 2 rp
+                float* ob = ybase + ((size_t)(DIL * (4 * m + aa)) * a.W + (size_t)(2 * (2 * rp + 1) * DIL)) * ldy;   // tile r + 1
+                if (cok) {
+                    oa[lane_yoff] = o0.x; oa[lane_yoff + DIL * ldy] = o1.x;
+                    ob[lane_yoff] = o0.y; ob[lane_yoff + DIL * ldy] = o1.y;
+                }
+                S1 = (S1 + o0) + o1;
+                S2 = __builtin_elementwise_fma(o1, o1, __builtin_elementwise_fma(o0, o0, S2));
+            }
+        }
+    }
+    s1 = S1.x + S1.y; s2 = S2.x + S2.y;
+}
+
+// a tile that crosses the image's lower or right edge: scalar, every output bounds-checked
+template <int DIL, int EPI, bool HALF>
+__device__ __forceinline__ void pc_epilogue_edge(const PcAcc<HALF>& acc, const WinoPcArgs& a, const PcTile& tl, const PcLane& c, float* ybase,
+                                                 bool cok, float bval, float& s1, float& s2) {
+    const unsigned ldy = c.ldy, lane_yoff = c.lane_yoff;
+#pragma unroll
+    for (int mi = 0; mi < (HALF ? 1 : 2); ++mi) {
+        const int m = HALF ? c.msel : mi;   // row block: address arithmetic uses m, the register index is mi
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float tr[2][4];
+#pragma unroll
+            for (int xx = 0; xx < 4; ++xx) {
+                const float m0 = acc[0 + xx][mi][r], m1 = acc[4 + xx][mi][r], m2 = acc[8 + xx][mi][r], m3 = acc[12 + xx][mi][r];
+                tr[0][xx] = (m0 + m1) + m2;
+                tr[1][xx] = (m1 - m2) - m3;
+            }
+#pragma unroll
+            for (int aa = 0; aa < 2; ++aa) {
+                float o0 = (tr[aa][0] + tr[aa][1]) + tr[aa][2];
+                float o1 = (tr[aa][1] - tr[aa][2]) - tr[aa][3];
+                if constexpr (EPI == 1) {
+                    o0 += bval; o1 += bval;
+                    if (a.out_lrelu) { o0 = fmaxf(o0, 0.01f * o0); o1 = fmaxf(o1, 0.01f * o1); }
+                }
+                float* o = ybase + ((size_t)(DIL * (4 * m + aa)) * a.W + (size_t)(2 * r * DIL)) * ldy;   // uniform
+                const int tile = 16 * m + 4 * c.kq + r;
+                const int gy = tl.y0 + tl.py + DIL * (2 * (tile >> 3) + aa), gx = tl.x0 + tl.px + DIL * (2 * (tile & 7));
+                if (gy < a.H && cok) {
+                    if (gx < a.W) { o[lane_yoff] = o0; s1 += o0; s2 = __builtin_fmaf(o0, o0, s2); }
+                    if (gx + DIL < a.W) { o[lane_yoff + DIL * ldy] = o1; s1 += o1; s2 = __builtin_fmaf(o1, o1, s2); }
+                }
+            }
+        }
+    }
+}
+
+// the wave owns its 16 channels: reduce over the 4 lanes (kq) that share a channel; column-major partials [2 Cout][rows]:
+// nrgbd_bn_finalize_cm reads a channel's partials as one run
+template <bool HALF>
+__device__ __forceinline__ void pc_store_stats(const WinoPcArgs& a, const PcTile& tl, const PcLane& c, int co, float s1, float s2) {
+    s1 += __shfl_xor(s1, 16, 64); s2 += __shfl_xor(s2, 16, 64);
+    s1 += __shfl_xor(s1, 32, 64); s2 += __shfl_xor(s2, 32, 64);
+    if (c.kq == 0) {
+        const int srow = HALF ? 2 * tl.row + c.msel : tl.row;   // HALF: two waves share a channel -> a row per (tile, row block)
+        a.stats[(size_t)co * a.rows + srow] = s1;
+        a.stats[(size_t)(a.Cout + co) * a.rows + srow] = s2;
+    }
+}
+
+// a finished tile: output + statistics
+template <int DIL, int EPI, bool HALF>
+__device__ __forceinline__ void pc_epilogue(const PcAcc<HALF>& acc, const WinoPcArgs& a, const PcTile& tl, const PcLane& c) {
+    const int co = tl.cg * 64 + c.cwv * 16 + c.jj;
+    float* ybase = a.y + (((size_t)tl.n * a.H + tl.y0 + tl.py) * a.W + tl.x0 + tl.px) * c.ldy + (EPI == 1 ? a.ycoff : 0) + tl.cg * 64 + c.cwv * 16;
+    const bool cok = EPI != 1 || a.cout_valid == 0 || co < a.cout_valid;   // EPI = 1: a padded output column is not stored
+    const bool inside = tl.y0 + tl.py + DIL * (kPcTH - 1) < a.H && tl.x0 + tl.px + DIL * (kPcTW - 1) < a.W;
+    float s1 = 0.f, s2 = 0.f;
+    float bval = 0.f;
+    if constexpr (EPI == 1) bval = a.bias ? a.bias[co] : 0.f;
+    if (inside) pc_epilogue_interior<DIL, EPI, HALF>(acc, a, c, ybase, cok, bval, s1, s2);
+    else pc_epilogue_edge<DIL, EPI, HALF>(acc, a, tl, c, ybase, cok, bval, s1, s2);
+    if (a.stats) pc_store_stats<HALF>(a, tl, c, co, s1, s2);
+}
+
+// ======================================================= producer steps =====================================================
+// A producer lane's items.  Load / publish item u = 192 pw + lane + 64 u over the whole 10-row halo (every halo word has ONE
+// loader) -> strip pixel pi = item >> 2 in (row, de-interleaved column) order, 16-byte word w4; row and column are recomputed
+// where needed: a few integer operations instead of 15 live registers.  Transform item: (tile of the row, 16-byte word, half
+// of the xi rows); 16 consecutive lanes = 4 tiles x 4 words: conflict-free strip reads (the four tiles' columns are consecutive
+// strip pixels) and V writes.
+struct PcItems {
+    int id0, w4;               // item u = id0 + 64 u; the item's 16-byte word
+    int wr_off[kPcNPF];        // strip offset an item is published at
+    int rdR0, rdR1, rdR2;      // strip offsets of the transform's three rows, in the order it takes them
+    float sg, m1;              // sign of the third row; an opaque -1
+    int vslot;                 // float offset in a V buffer of the lane's first transform point xi = 8 thalf; point xi + k: + 512 k
+    __device__ __forceinline__ int item_id(int u) const { return id0 + 64 * u; }
+    __device__ __forceinline__ int row(int u) const { return (item_id(u) >> 2) / 18; }
+    __device__ __forceinline__ int cp(int u) const { const int pi = item_id(u) >> 2; return pi - (pi / 18) * 18; }
+    __device__ __forceinline__ int col(int u) const { const int c = cp(u); return c < 9 ? 2 * c : 2 * c - 17; }   // even columns first, then odd
+};
+
+__device__ __forceinline__ PcItems pc_items(int pw, int lane) {
+    PcItems p;
+    p.id0 = 192 * pw + lane;
+    p.w4 = lane & 3;
+    // the 48 items beyond the halo's 720 (768 = 3 x 256) go to pad pixels of the strip (columns 18, 19 of the 20-pixel row
+    // pitch, written as zero) so that the publish loop has no per-lane branch
+#pragma unroll
+    for (int u = 0; u < kPcNPF; ++u) {
+        const int item = p.item_id(u), e = (item - kPcShItems) >> 2;
+        p.wr_off[u] = item < kPcShItems ? (p.row(u) * kPcRawW + p.cp(u)) * kCB + p.w4 * 4
+                                        : ((e >> 1) * kPcRawW + 18 + (e & 1)) * kCB + p.w4 * 4;
+    }
+    const int tword = lane & 3, thalf = (lane >> 4) & 1, txl = ((lane >> 5) << 2) | ((lane >> 2) & 3);
+    p.vslot = pc_slot(8 * thalf, pw * 8 + txl, tword);
+    // Row transform without per-lane selects: the lane reads its three strip rows in a lane-dependent ORDER (R0, R1, R2) and
+    // computes ya = R0 - R1, yb = R1 + sg * R2:
+    //   half 0 (xi_y 0, 1): R = strip rows (0, 2, 1), sg = +1 ->  d0 - d2,  d2 + d1
+    //   half 1 (xi_y 2, 3): R = strip rows (2, 1, 3), sg = -1 ->  d2 - d1,  d1 - d3
+    // (strip columns of tile txl: cc = 0 at column pixel txl, cc = 1: +9 pixels, cc = 2: +1, cc = 3: +10)
+    const int rdc = txl * kCB + tword * 4 + 2 * pw * kPcRawW * kCB;   // the tile row's halo rows start at strip row 2 pw
+    p.rdR0 = (thalf ? 2 : 0) * kPcRawW * kCB + rdc; p.rdR1 = (thalf ? 1 : 2) * kPcRawW * kCB + rdc;
+    p.rdR2 = (thalf ? 3 : 1) * kPcRawW * kCB + rdc;
+    p.sg = thalf ? -1.f : 1.f;
+    p.m1 = -1.f;                            // opaque to the optimiser: fma(a, -1, c) would otherwise be folded into four scalar
+    asm volatile("" : "+v"(p.m1));          // v_sub_f32; as a register operand it stays one v_pk_fma_f32 per pair (same rounding)
+    return p;
+}
+
+// Per-tile book of a lane's items: in-plane BYTE offset (a harmless in-tensor offset when outside), 1 inside the image / 0
+// outside (zero padding), owner bits (materialise target).  Two books: the raw words run TWO stages ahead of their use, so the
+// last two stages of a tile already load the next tile's words.
+struct PcBook { unsigned off[kPcNPF]; float keep[kPcNPF]; unsigned own; };
+
+template <int KD, int DIL>
+__device__ __forceinline__ void pc_book(const WinoPcArgs& a, const PcItems& p, const PcTile& t, PcBook& b) {
+    b.own = 0;
+#pragma unroll
+    for (int u = 0; u < kPcNPF; ++u) {
+        const int hy = p.row(u), hx = p.col(u);
+        const int gy = t.y0 + t.py + DIL * (hy - 1), gx = t.x0 + t.px + DIL * (hx - 1);
+        const bool in = p.item_id(u) < kPcShItems && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
+        const unsigned n2 = KD == 3 ? 0u : (unsigned)t.n;
+        b.off[u] = 4u * (in ? (unsigned)((((size_t)n2 * a.H + gy) * a.W + gx) * a.Cin + p.w4 * 4) : (unsigned)(p.w4 * 4));
+        b.keep[u] = in ? 1.f : 0.f;
+        const bool mine = hy >= 1 && hy <= kPcTH;   // the one loader of a pixel of the tile's own 8 x 16
+        if (in && mine && hx >= 1 && hx <= kPcTW) b.own |= 1u << u;
+    }
+}
+
+// One register set per stage parity: raw words (+ residual words) and the (scale, shift) of the stage's 4 channels.
+// A set is refilled for stage s+2 right after stage s has published it, so a load has two stage periods to land:
+// with a single set the chain load -> publish -> next load made the producers' period = memory latency + publish
+// (measured 2.8 us against the consumers' 2.0 us of MFMAs), i.e. the matrix pipe waited for the producers.
+template <bool RES> struct PcRegs { f32x4 pre[kPcNPF]; f32x4 prer[RES ? kPcNPF : 1]; f32x4 ss[2]; f32x4 rs[2]; };
+
+// a producer wave's state across stages and tiles
+struct PcProd {
+    PcItems p;
+    PcTile tl, tn;             // current tile; the next one once the refills reach into it
+    PcBook cur, nxt;
+    float* Vb; float* rawb; const float* ssl;
+    unsigned plane;            // floats of one slice
+    int qbuf, gi;              // V buffer the next transform writes; stages published so far (strip parity)
+    bool has_next, interior;   // another tile follows; the current tile's whole halo lies inside the image
+};
+
+// raw words of stage s -> registers; nx: the stage belongs to the NEXT tile (book nxt, tile tn).  The book is selected per
+// value, not per pointer: a pointer select would force both books into scratch memory.
+template <int KD, bool RES, int EPI>
+__device__ __forceinline__ void pc_issue(const WinoPcArgs& a, const PcProd& P, bool nx, int s, PcRegs<RES>& r) {
+    const int cb = s / KD, kd = s - cb * KD, w4 = P.p.w4;
+    r.ss[0] = r.ss[1] = r.rs[0] = r.rs[1] = f32x4{1.f, 1.f, 0.f, 0.f};
+    if constexpr (EPI == 0) {
+        r.ss[0] = *reinterpret_cast<const f32x4*>(P.ssl + 2 * (cb * kCB + w4 * 4));
+        r.ss[1] = *reinterpret_cast<const f32x4*>(P.ssl + 2 * (cb * kCB + w4 * 4) + 4);
+        if constexpr (RES) {
+            r.rs[0] = *reinterpret_cast<const f32x4*>(P.ssl + 2 * a.Cin + 2 * (cb * kCB + w4 * 4));
+            r.rs[1] = *reinterpret_cast<const f32x4*>(P.ssl + 2 * a.Cin + 2 * (cb * kCB + w4 * 4) + 4);
+        }
+    }
+    const int tz = nx ? P.tn.n : P.tl.n;
+    const int z = KD == 3 ? min(max(tz + kd - 1, 0), a.N - 1) : 0;   // clamped: an outside slice is zeroed when published
+    // uniform 64-bit base + per-lane 32-bit byte offset: the global_load saddr form, no per-lane 64-bit address math
+    const size_t base = ((size_t)z * P.plane + (size_t)(cb * kCB)) * sizeof(float);
+    const __amdgpu_buffer_rsrc_t xb = pc_rsrc(reinterpret_cast<const char*>(a.x) + base);
+    const __amdgpu_buffer_rsrc_t rb = pc_rsrc(reinterpret_cast<const char*>(RES ? a.res : a.x) + base);
+#pragma unroll
+    for (int u = 0; u < kPcNPF; ++u) {
+        const unsigned o = nx ? P.nxt.off[u] : P.cur.off[u];
+        r.pre[u] = pc_bload(xb, o);
+        if constexpr (RES) r.prer[u] = pc_bload(rb, o);
+    }
+}
+
+// (1) normalise / activate the prefetched words of set r and publish them to the strip `raw` (+ materialise).
+// Straight-line, packed, no per-lane branches or selects: as a chain of exec-masked blocks this phase took 0.74 us alone and
+// 2.0 us beside the consumers' MFMA stream — longer than the MFMAs it has to stay ahead of.  Breadth-first over the items — all
+// FMAs, then all ReLUs, then all masks, then the stores — and pinned in that order: beside the consumer's MFMA stream a VALU
+// instruction that has to wait for its predecessor's result loses the issue port to the next MFMA (32 cycles), an
+// independent one issues back to back.  INTERIOR: every item of every lane inside the image: no padding mask (the strip's
+// pad pixels are never read by the transform).
+template <int KD, bool RES, int EPI, bool MAT, bool INTERIOR>
+__device__ __forceinline__ void pc_activate_publish(const WinoPcArgs& a, const PcProd& P, const PcRegs<RES>& r, float* raw, int cb, int kd, int z) {
+    // (scale, shift) pairs of channels (0,1) and (2,3); identity = (1, 0); the LDS table is stored pre-paired (pc_ss_slot)
+    const f32x2 sc01 = r.ss[0].lo, sh01 = r.ss[0].hi, sc23 = r.ss[1].lo, sh23 = r.ss[1].hi;
+    const f32x2 rc01 = r.rs[0].lo, rh01 = r.rs[0].hi, rc23 = r.rs[1].lo, rh23 = r.rs[1].hi;
+    const bool wmat = MAT && (KD != 3 || kd == 1) && P.tl.cg == 0;
+    constexpr int NU = kPcNPF;
+    f32x2 lo[NU], hi[NU];
+    if constexpr (EPI == 1) {   // the R-Net form has no prologue: no identity FMAs (x * 1 + 0 is not folded: -0)
+#pragma unroll
+        for (int i = 0; i < NU; ++i) { lo[i] = r.pre[i].lo; hi[i] = r.pre[i].hi; }
+    } else {
+#pragma unroll
+        for (int i = 0; i < NU; ++i) {
+            lo[i] = __builtin_elementwise_fma(r.pre[i].lo, sc01, sh01);
+            hi[i] = __builtin_elementwise_fma(r.pre[i].hi, sc23, sh23);
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (EPI == 0 && a.x_relu) {
+#pragma unroll
+        for (int i = 0; i < NU; ++i) { lo[i].x = relu1(lo[i].x); lo[i].y = relu1(lo[i].y); hi[i].x = relu1(hi[i].x); hi[i].y = relu1(hi[i].y); }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (RES) {
+        f32x2 ql[NU], qh[NU];
+#pragma unroll
+        for (int i = 0; i < NU; ++i) {
+            ql[i] = __builtin_elementwise_fma(r.prer[i].lo, rc01, rh01);
+            qh[i] = __builtin_elementwise_fma(r.prer[i].hi, rc23, rh23);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (a.res_relu) {
+#pragma unroll
+            for (int i = 0; i < NU; ++i) { ql[i].x = relu1(ql[i].x); ql[i].y = relu1(ql[i].y); qh[i].x = relu1(qh[i].x); qh[i].y = relu1(qh[i].y); }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < NU; ++i) { lo[i] = lo[i] + ql[i]; hi[i] = hi[i] + qh[i]; }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    // zero padding applies to the ACTIVATED tensor: out-of-image lanes (their loads read a harmless in-tensor word) are multiplied by 0
+    if constexpr (!INTERIOR) {
+#pragma unroll
+        for (int i = 0; i < NU; ++i) {
+            const f32x2 kk = {P.cur.keep[i], P.cur.keep[i]};
+            lo[i] = lo[i] * kk; hi[i] = hi[i] * kk;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+        const f32x4 v = __builtin_shufflevector(lo[u], hi[u], 0, 1, 2, 3);
+        // the activated input is written once: by the wave that owns the pixel, at the centre tap
+        if (MAT && wmat) {
+            if ((P.cur.own >> u) & 1u)
+                *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(a.mat) + ((size_t)(KD == 3 ? z : 0) * P.plane + (size_t)(cb * kCB)) * sizeof(float) + P.cur.off[u]) = v;
+        }
+        *reinterpret_cast<f32x4*>(raw + P.p.wr_off[u]) = v;
+    }
+}
+
+// (3) input transform B^T d B of this lane's (tile, word): rows (2 of the 4 xi_y), then columns; strip rawT -> V buffer Vq
+__device__ __forceinline__ void pc_transform(const PcItems& p, const float* rawT, float* Vq) {
+    const float m1 = p.m1;
+    f32x4 ya[4], yb[4];
+#pragma unroll
+    for (int cc = 0; cc < 4; ++cc) {
+        const int co = ((cc & 1) * 9 + (cc >> 1)) * kCB;
+        const f32x4 R0 = *reinterpret_cast<const f32x4*>(rawT + p.rdR0 + co);
+        const f32x4 R1 = *reinterpret_cast<const f32x4*>(rawT + p.rdR1 + co);
+        const f32x4 R2 = *reinterpret_cast<const f32x4*>(rawT + p.rdR2 + co);
+        ya[cc] = pk_fma_s(R1, m1, R0);     // R0 - R1
+        yb[cc] = pk_fma_s(R2, p.sg, R1);   // R1 +- R2
+    }
+    float* V = Vq + p.vslot;                     // points 8 thalf + 0 .. 3 from ya, + 4 .. 7 from yb
+    constexpr int kXi = kPcTiles * kCB;          // floats per transform point
+    *reinterpret_cast<f32x4*>(V + 0 * kXi) = pk_fma_s(ya[2], m1, ya[0]);   // y0 - y2
+    *reinterpret_cast<f32x4*>(V + 1 * kXi) = pk_add(ya[1], ya[2]);
+    *reinterpret_cast<f32x4*>(V + 2 * kXi) = pk_fma_s(ya[1], m1, ya[2]);   // y2 - y1
+    *reinterpret_cast<f32x4*>(V + 3 * kXi) = pk_fma_s(ya[3], m1, ya[1]);   // y1 - y3
+    *reinterpret_cast<f32x4*>(V + 4 * kXi) = pk_fma_s(yb[2], m1, yb[0]);
+    *reinterpret_cast<f32x4*>(V + 5 * kXi) = pk_add(yb[1], yb[2]);
+    *reinterpret_cast<f32x4*>(V + 6 * kXi) = pk_fma_s(yb[1], m1, yb[2]);
+    *reinterpret_cast<f32x4*>(V + 7 * kXi) = pk_fma_s(yb[3], m1, yb[1]);
+}
+
+// one stage, up to its barrier: (1) publish set r (stage s of the current tile) into strip gi & 1, (2) refill the set for stage
+// s+2 (of this tile, or stage s+2-NS of the next one), (3) transform the strip published one stage ago into V[qbuf]
+template <int KD, bool RES, int EPI, bool MAT>
+__device__ __forceinline__ void pc_stage(const WinoPcArgs& a, const PcProd& P, int NS, int s, PcRegs<RES>& r) {
+    const int cb = s / KD, kd = s - cb * KD;
+    const int z = KD == 3 ? P.tl.n + kd - 1 : P.tl.n;
+    const bool zin = KD != 3 || (z >= 0 && z < a.N);
+    float* raw = P.rawb + (P.gi & 1) * kPcShStrip;
+    const float* rawT = P.rawb + ((P.gi & 1) ^ 1) * kPcShStrip;
+    if (!zin) {   // a depth tap outside the volume: the whole slice is zero padding
+#pragma unroll
+        for (int u = 0; u < kPcNPF; ++u) *reinterpret_cast<f32x4*>(raw + P.p.wr_off[u]) = f32x4{0.f, 0.f, 0.f, 0.f};
+    } else {
+        asm volatile("" : "+v"(r.ss[0]), "+v"(r.ss[1]));   // the pairs are re-paired HERE, not behind their loads
+        if constexpr (RES) asm volatile("" : "+v"(r.rs[0]), "+v"(r.rs[1]));
+        if (P.interior) pc_activate_publish<KD, RES, EPI, MAT, true>(a, P, r, raw, cb, kd, z);
+        else pc_activate_publish<KD, RES, EPI, MAT, false>(a, P, r, raw, cb, kd, z);
+    }
+    // UNCONDITIONAL (the last two stages of the last tile re-read this tile's first two: harmless, never used)
+    const bool nx = s + 2 >= NS;
+    pc_issue<KD, RES, EPI>(a, P, nx && P.has_next, nx ? s + 2 - NS : s + 2, r);
+    if (P.gi > 0) pc_transform(P.p, rawT, P.Vb + P.qbuf * kPcV);
+}
+// ... and behind its barrier: the transform lags the publish by one stage, so the first stage does not advance the V buffer
+__device__ __forceinline__ void pc_stage_end(PcProd& P) {
+    if (P.gi > 0) P.qbuf = P.qbuf == kPcNBuf - 1 ? 0 : P.qbuf + 1;
+    ++P.gi;
+}
+
+}  // namespace
+
+// ---- The barrier protocol.  G = tiles of this workgroup x NS stages, counted across tiles (P.gi); every wave executes G + 3
+// barriers (+ 1 behind the (scale, shift) table load when EPI = 0).  A workgroup without tiles returns before the first one: the
+// test is uniform and follows nothing but the tile-list split.
+//   Producers, iteration g = 0 .. G-1: publish stage g into strip g & 1 from a register set loaded TWO stages earlier, refill
+//   that set for stage g + 2, transform stage g - 1 into V[(g - 1) % 3], barrier.  The transform runs one iteration after the
+//   publish because the barrier between them is what completes the shared strip (four waves write it, each reads all of it).
+//   Closing: the transform of the last published stage G - 1 and its barrier, then two more: the consumers' last two stages.
+//   Consumers: three opening barriers (stage 0 published | stage 0 transformed | stage 1 transformed), then per stage g its
+//   MFMAs on V[g % 3] and one barrier.  Meanwhile the producers transform stage g + 2 into V[(g + 2) % 3] — they run two
+//   stages ahead — and the consumers read the first operands of stage g + 1 from V[(g + 1) % 3], completed before the
+//   previous barrier: three V buffers make both legal.
+//   One barrier per stage; the consumers never wait for data, the producers wait for the consumers.
 template <int KD, int DIL, bool RES, bool ODD = false, int EPI = 0, bool MAT = false, bool HALF = false>
 __global__ __launch_bounds__(512) void conv_wino_pc_kernel(const WinoPcArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* Vb = lds;                           // [3][16 xi][32 tiles][16]
-    float* rawb = lds + kPcNBuf * kPcV;        // SHARED: [2][10 rows][20 pixels][16]; else [4 producer waves][4 rows][20 pixels][16]
+    float* rawb = lds + kPcNBuf * kPcV;        // [2 strips][10 rows][20 pixels][16]
     float* ssl = rawb + kPcStrips;             // [Cin][2] (scale, shift) of x, then [Cin][2] of res (identity where null)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wv = wave & 3;                   // index within the role
     const int NS = (a.Cin / kCB) * KD;         // stages per tile
-#ifdef NRGBD_DEV
-    const int abl = a.abl;
-    const long t_entry = wall_clock64();
-#else
-    constexpr int abl = 0;
-#endif
 
-    // ---- this workgroup's share of the tile list: XCD x = blockIdx % 8 owns the x-th contiguous eighth, its workgroups
-    //      (slots) walk it interleaved, so the workgroups of one XCD are always on neighbouring tiles
     int first, step, end;
-    {
-        const int G = (int)gridDim.x, b = (int)blockIdx.x;
-        if ((G & 7) == 0) {
-            const int xc = b & 7;
-            first = (int)(((long)a.ntiles * xc) >> 3) + (b >> 3);
-            end = (int)(((long)a.ntiles * (xc + 1)) >> 3);
-            step = G >> 3;
-        } else { first = b; end = a.ntiles; step = G; }
-    }
+    pc_tile_share(a.ntiles, first, step, end);
     if (first >= end) return;                  // uniform: no wave of this workgroup ever reaches a barrier
     const int count = (end - first + step - 1) / step;
-    const unsigned plane = (unsigned)((size_t)a.H * a.W * a.Cin);
     if constexpr (EPI == 0) {
-        for (int i = threadIdx.x; i < 2 * a.Cin; i += 512) {
-            const int j = pc_ss_slot(i);  // pairs as the packed FMAs take them: (s0, s1, t0, t1 | s2, s3, t2, t3) per 4 channels
-            ssl[j] = a.x_ss ? a.x_ss[i] : ((i & 1) ? 0.f : 1.f);
-            ssl[2 * a.Cin + j] = (RES && a.res_ss) ? a.res_ss[i] : ((i & 1) ? 0.f : 1.f);
-        }
+        pc_load_ss_table<true>(ssl, a.Cin, a.x_ss, RES ? a.res_ss : nullptr, 1.f);
         __syncthreads();
     }
 
@@ -93,43 +545,19 @@ __global__ __launch_bounds__(512) void conv_wino_pc_kernel(const WinoPcArgs a) {
     // get through beside the consumer's continuous MFMA stream (measured: 3.58 -> 3.38 ms per layer from this alone)
     if (wave >= 4) {
         // =========================================== consumer: 16 output channels x 16 xi x 32 tiles ====================
-        const int kq = lane >> 4, jj = lane & 15;
-        constexpr int NM = HALF ? 1 : 2;       // row blocks (16 Winograd tiles each) of this wave
-        const int msel = HALF ? (wv >> 1) : 0; // HALF: the one row block this wave owns
-        const int cwv = HALF ? (wv & 1) : wv;  // the wave's 16-column group
-        f32x4 acc[16][NM];                     // written by the first stage of every tile (C operand = 0): never cleared
-        const int a0 = pc_slot(0, 16 * msel + jj, kq), a1 = pc_slot(0, 16 + jj, kq);   // + xi * 512 floats + buffer
-        const f32x4* wbase = reinterpret_cast<const f32x4*>(a.wp) + cwv * 64 + lane;
-        const unsigned ldy = (EPI == 1 && a.ldy) ? (unsigned)a.ldy : (unsigned)a.Cout;   // pixel stride of the output
-        const unsigned lane_yoff = (unsigned)jj + (unsigned)((DIL * 2 * (kq >> 1)) * a.W + 8 * (kq & 1) * DIL) * ldy;
+        const PcLane c = pc_lane<DIL, EPI, HALF>(a, lane, wv);
+        PcAcc<HALF> acc;
+        const f32x4* wbase = reinterpret_cast<const f32x4*>(a.wp) + c.cwv * 64 + lane;
         const size_t wgroup = (size_t)NS * 16 * 256;                        // f32x4 per 64-column output group
-
         PcTile tl = pc_decode<KD, DIL>(first, a);
         const f32x4* wt = wbase + (size_t)tl.cg * wgroup;
-        constexpr int BD = HALF ? 6 : kPcBD;   // weight lines in flight (HALF requests two per pair of points: an even distance)
-        f32x4 Bn[kPcNB], An[4][2];             // A operands run TWO transform points ahead (one point = 256 MFMA cycles < a loaded LDS's latency)
-                                               // HALF: An[pair & 3][point of the pair], two PAIRS ahead
-#pragma unroll
-        for (int b = 0; b < BD; ++b) Bn[b] = wt[b * 256];
-        if constexpr (NRGBD_PC_SHARED != 0) __syncthreads();   // the producers publish stage 0 (transformed one iteration later)
+        f32x4 Bn[kPcNB], An[4][2];             // weight ring (7 lines ahead, continues across stages and tiles); A operands
+        pc_prime_weights<HALF>(Bn, wt);
+        __syncthreads();                       // the producers publish stage 0 (transformed one iteration later)
         __syncthreads();                       // producers finish stage 0
         __syncthreads();                       // ... and stage 1
-        if constexpr (HALF) {
-            An[0][0] = *reinterpret_cast<const f32x4*>(Vb + a0);
-            An[0][1] = *reinterpret_cast<const f32x4*>(Vb + a0 + kPcTiles * kCB);
-            An[1][0] = *reinterpret_cast<const f32x4*>(Vb + a0 + 2 * kPcTiles * kCB);
-            An[1][1] = *reinterpret_cast<const f32x4*>(Vb + a0 + 3 * kPcTiles * kCB);
-        } else {
-            An[0][0] = *reinterpret_cast<const f32x4*>(Vb + a0);
-            An[0][1] = *reinterpret_cast<const f32x4*>(Vb + a1);
-            An[1][0] = *reinterpret_cast<const f32x4*>(Vb + a0 + kPcTiles * kCB);
-            An[1][1] = *reinterpret_cast<const f32x4*>(Vb + a1 + kPcTiles * kCB);
-        }
+        pc_prime_a<HALF>(An, Vb, c);
         int buf = 0;
-#ifdef NRGBD_DEV
-        long t_mfma = 0, t_bar = 0, t_epi = 0;
-        const long t_loop = wall_clock64();
-#endif
         for (int it = 0; it < count; ++it) {
             const int tnext = first + (it + 1 < count ? it + 1 : it) * step;
             const PcTile tn = pc_decode<KD, DIL>(tnext, a);
@@ -140,493 +568,56 @@ __global__ __launch_bounds__(512) void conv_wino_pc_kernel(const WinoPcArgs a) {
                 const float* Vn = Vb + nbuf * kPcV;
                 const f32x4* wcur = wt + (size_t)s * (16 * 256);
                 const f32x4* wnx = s + 1 < NS ? wcur + 16 * 256 : wt_next;
-#ifdef NRGBD_DEV
-                const long c0 = wall_clock64();
-#endif
-                // one stage = 16 transform points x (2 A reads + 1 weight line + 8 MFMAs).  FIRST (stage 0 of a tile): the first
-                // k-step takes a zero C operand instead of the accumulator, which saves clearing 128 registers per tile.
-                auto body = [&](auto first_tag) __attribute__((always_inline)) {
-                    constexpr bool FIRST = decltype(first_tag)::value;
-                    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-                    if constexpr (HALF) {
-                        // a step = the PAIR of transform points (2 xp, 2 xp + 1): 2 A reads (two pairs ahead), 8 MFMAs alternating
-                        // between the two accumulators, the weight lines of points 2 xp + 6 and 2 xp + 7 requested in two MFMA gaps
-#pragma unroll
-                        for (int xp = 0; xp < 8; ++xp) {
-                            const int cur = xp & 3, nxt = (xp + 2) & 3;
-                            const float* Vs = xp + 2 < 8 ? Vc : Vn;   // pairs 0, 1 of the next stage: its buffer was completed two barriers ago
-                            const int pn = (xp + 2) & 7;
-                            An[nxt][0] = *reinterpret_cast<const f32x4*>(Vs + a0 + (2 * pn) * (kPcTiles * kCB));
-                            An[nxt][1] = *reinterpret_cast<const f32x4*>(Vs + a0 + (2 * pn + 1) * (kPcTiles * kCB));
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                acc[2 * xp][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(An[cur][0][e], Bn[(2 * xp) % kPcNB][e],
-                                                                                      FIRST && e == 0 ? zero4 : acc[2 * xp][0], 0, 0, 0);
-                                acc[2 * xp + 1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(An[cur][1][e], Bn[(2 * xp + 1) % kPcNB][e],
-                                                                                          FIRST && e == 0 ? zero4 : acc[2 * xp + 1][0], 0, 0, 0);
-                                if (e == 1) Bn[(2 * xp + 6) % kPcNB] = 2 * xp + 6 < 16 ? wcur[(2 * xp + 6) * 256] : wnx[(2 * xp + 6 - 16) * 256];
-                                if (e == 3) Bn[(2 * xp + 7) % kPcNB] = 2 * xp + 7 < 16 ? wcur[(2 * xp + 7) * 256] : wnx[(2 * xp + 7 - 16) * 256];
-                                __builtin_amdgcn_sched_barrier(0);
-                            }
-                        }
-                    } else {
-#pragma unroll
-                    for (int xi = 0; xi < 16; ++xi) {
-                        const int cur = xi & 3, nxt = (xi + 2) & 3;
-                        if (xi + 2 < 16) {
-                            An[nxt][0] = *reinterpret_cast<const f32x4*>(Vc + a0 + (xi + 2) * (kPcTiles * kCB));
-                            An[nxt][1] = *reinterpret_cast<const f32x4*>(Vc + a1 + (xi + 2) * (kPcTiles * kCB));
-                        } else {   // the first two operands of the next stage: its buffer was completed two barriers ago
-                            An[nxt][0] = *reinterpret_cast<const f32x4*>(Vn + a0 + (xi + 2 - 16) * (kPcTiles * kCB));
-                            An[nxt][1] = *reinterpret_cast<const f32x4*>(Vn + a1 + (xi + 2 - 16) * (kPcTiles * kCB));
-                        }
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            acc[xi][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(An[cur][0][e], Bn[xi % kPcNB][e],
-                                                                              FIRST && e == 0 ? zero4 : acc[xi][0], 0, 0, 0);
-                            acc[xi][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(An[cur][1][e], Bn[xi % kPcNB][e],
-                                                                              FIRST && e == 0 ? zero4 : acc[xi][1], 0, 0, 0);
-                            // pin the order: the two row blocks alternate (no back-to-back dependent MFMAs) and the operand
-                            // streams keep their distances
-                            // the weight line of the point 7 ahead is requested HERE, in the second MFMA gap of the point, not at its top beside the two
-                            // LDS reads: a vector-memory instruction costs the wave ~50 issue cycles, and three memory instructions in one gap let the
-                            // matrix pipe run dry (tools/probes/mfma_stream_probe.hip: 78.5 -> 85.4 % busy)
-                            if (e == NRGBD_WPOS) Bn[(xi + kPcBD) % kPcNB] = xi + kPcBD < 16 ? wcur[(xi + kPcBD) * 256] : wnx[(xi + kPcBD - 16) * 256];
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                    }
-                    }
-                };
-                if (!(abl & 1)) {
-                    if (s == 0) body(std::true_type{}); else body(std::false_type{});
-                }
-#ifdef NRGBD_DEV
-                const long c1 = wall_clock64();
-#endif
+                if (s == 0) pc_mfma_stage<HALF, true>(acc, An, Bn, Vc, Vn, wcur, wnx, c);
+                else pc_mfma_stage<HALF, false>(acc, An, Bn, Vc, Vn, wcur, wnx, c);
                 __syncthreads();
-#ifdef NRGBD_DEV
-                const long c2 = wall_clock64();
-                t_mfma += c1 - c0; t_bar += c2 - c1;
-#endif
                 buf = nbuf;
             }
-#ifdef NRGBD_DEV
-            const long c3 = wall_clock64();
-#endif
-            // ---- inverse transform Y = A^T M A in registers + output + per-channel partial statistics ----
-            // lane (kq, jj): output channel co = 16 wv + jj; register r of row block m = tile 16 m + 4 kq + r, i.e. tile row
-            // 2m + (kq >> 1), tile column 4 (kq & 1) + r: the lane part of an output's address is loop-invariant (lane_yoff),
-            // the (m, r, a) part is uniform -> scalar base + 32-bit lane offset stores, no per-store address arithmetic
-            const int co = tl.cg * 64 + cwv * 16 + jj;
-            float* ybase = a.y + (((size_t)tl.n * a.H + tl.y0 + tl.py) * a.W + tl.x0 + tl.px) * ldy + (EPI == 1 ? a.ycoff : 0) + tl.cg * 64 + cwv * 16;
-            const bool cok = EPI != 1 || a.cout_valid == 0 || co < a.cout_valid;   // EPI = 1: a padded output column is not stored
-            const bool inside = tl.y0 + tl.py + DIL * (kPcTH - 1) < a.H && tl.x0 + tl.px + DIL * (kPcTW - 1) < a.W;
-            float s1 = 0.f, s2 = 0.f;
-            float bval = 0.f;
-            if constexpr (EPI == 1) bval = a.bias ? a.bias[co] : 0.f;
-            if (inside) {
-                // interior tile: the whole inverse transform, the statistics and the stores on register PAIRS (tiles r, r+1 of a
-                // row block): v_pk_add_f32 / v_pk_fma_f32 halve the epilogue's VALU instructions; a - b is fma(b, -1, a) with
-                // an opaque -1 (same rounding; a literal would be folded into two scalar v_sub)
-                float neg1 = -1.f;
-                asm volatile("" : "+v"(neg1));
-                const f32x2 n1 = {neg1, neg1};
-                const f32x2 bias2 = {bval, bval};
-                f32x2 S1 = {0.f, 0.f}, S2 = {0.f, 0.f};
-#pragma unroll
-                for (int mi = 0; mi < NM; ++mi) {
-                    const int m = HALF ? msel : mi;   // row block: address arithmetic uses m, the register index is mi
-#pragma unroll
-                    for (int rp = 0; rp < 2; ++rp) {
-                        f32x2 tr[2][4];   // t[a][xi_x] = sum_xi_y A^T[a][xi_y] M[xi_y][xi_x]
-#pragma unroll
-                        for (int xx = 0; xx < 4; ++xx) {
-                            const f32x2 m0 = rp ? acc[0 + xx][mi].hi : acc[0 + xx][mi].lo, m1 = rp ? acc[4 + xx][mi].hi : acc[4 + xx][mi].lo;
-                            const f32x2 m2 = rp ? acc[8 + xx][mi].hi : acc[8 + xx][mi].lo, m3 = rp ? acc[12 + xx][mi].hi : acc[12 + xx][mi].lo;
-                            tr[0][xx] = (m0 + m1) + m2;
-                            tr[1][xx] = __builtin_elementwise_fma(m3, n1, __builtin_elementwise_fma(m2, n1, m1));   // (m1 - m2) - m3
-                        }
-#pragma unroll
-                        for (int aa = 0; aa < 2; ++aa) {
-                            f32x2 o0 = (tr[aa][0] + tr[aa][1]) + tr[aa][2];
-                            f32x2 o1 = __builtin_elementwise_fma(tr[aa][3], n1, __builtin_elementwise_fma(tr[aa][2], n1, tr[aa][1]));
-                            if constexpr (EPI == 1) {   // m_submodule.py:18-27: bias, LeakyReLU(0.01) = max(z, 0.01 z)
-                                o0 = o0 + bias2; o1 = o1 + bias2;
-                                if (a.out_lrelu) {
-                                    const f32x2 sl = {0.01f, 0.01f};
-                                    o0 = __builtin_elementwise_max(o0, o0 * sl); o1 = __builtin_elementwise_max(o1, o1 * sl);
-                                }
-                            }
-                            float* oa = ybase + ((size_t)(DIL * (4 * m + aa)) * a.W + (size_t)(2 * (2 * rp) * DIL)) * ldy;       // tile r = 2 rp
-                            float* ob = ybase + ((size_t)(DIL * (4 * m + aa)) * a.W + (size_t)(2 * (2 * rp + 1) * DIL)) * ldy;   // tile r + 1
-                            if (cok) {
-                                oa[lane_yoff] = o0.x; oa[lane_yoff + DIL * ldy] = o1.x;
-                                ob[lane_yoff] = o0.y; ob[lane_yoff + DIL * ldy] = o1.y;
-                            }
-                            S1 = (S1 + o0) + o1;
-                            S2 = __builtin_elementwise_fma(o1, o1, __builtin_elementwise_fma(o0, o0, S2));
-                        }
-                    }
-                }
-                s1 = S1.x + S1.y; s2 = S2.x + S2.y;
-            } else {
-#pragma unroll
-                for (int mi = 0; mi < NM; ++mi) {
-                    const int m = HALF ? msel : mi;   // row block: address arithmetic uses m, the register index is mi
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        float tr[2][4];
-#pragma unroll
-                        for (int xx = 0; xx < 4; ++xx) {
-                            const float m0 = acc[0 + xx][mi][r], m1 = acc[4 + xx][mi][r], m2 = acc[8 + xx][mi][r], m3 = acc[12 + xx][mi][r];
-                            tr[0][xx] = (m0 + m1) + m2;
-                            tr[1][xx] = (m1 - m2) - m3;
-                        }
-#pragma unroll
-                        for (int aa = 0; aa < 2; ++aa) {
-                            float o0 = (tr[aa][0] + tr[aa][1]) + tr[aa][2];
-                            float o1 = (tr[aa][1] - tr[aa][2]) - tr[aa][3];
-                            if constexpr (EPI == 1) {
-                                o0 += bval; o1 += bval;
-                                if (a.out_lrelu) { o0 = fmaxf(o0, 0.01f * o0); o1 = fmaxf(o1, 0.01f * o1); }
-                            }
-                            float* o = ybase + ((size_t)(DIL * (4 * m + aa)) * a.W + (size_t)(2 * r * DIL)) * ldy;   // uniform
-                            const int tile = 16 * m + 4 * kq + r;
-                            const int gy = tl.y0 + tl.py + DIL * (2 * (tile >> 3) + aa), gx = tl.x0 + tl.px + DIL * (2 * (tile & 7));
-                            if (gy < a.H && cok) {
-                                if (gx < a.W) { o[lane_yoff] = o0; s1 += o0; s2 = __builtin_fmaf(o0, o0, s2); }
-                                if (gx + DIL < a.W) { o[lane_yoff + DIL * ldy] = o1; s1 += o1; s2 = __builtin_fmaf(o1, o1, s2); }
-                            }
-                        }
-                    }
-                }
-            }
-            if (a.stats) {   // the wave owns its 16 channels: reduce over the 4 lanes (kq) that share a channel
-                s1 += __shfl_xor(s1, 16, 64); s2 += __shfl_xor(s2, 16, 64);
-                s1 += __shfl_xor(s1, 32, 64); s2 += __shfl_xor(s2, 32, 64);
-                if (kq == 0) {
-                    // column-major partials [2 Cout][rows]: nrgbd_bn_finalize_cm reads a channel's partials as one run
-                    const int srow = HALF ? 2 * tl.row + msel : tl.row;   // HALF: two waves share a channel -> a row per (tile, row block)
-                    a.stats[(size_t)co * a.rows + srow] = s1;
-                    a.stats[(size_t)(a.Cout + co) * a.rows + srow] = s2;
-                }
-            }
+            pc_epilogue<DIL, EPI, HALF>(acc, a, tl, c);
             tl = tn;
             wt = wt_next;
-#ifdef NRGBD_DEV
-            t_epi += wall_clock64() - c3;
-#endif
         }
-#ifdef NRGBD_DEV
-        if ((abl & 64) && a.stats && wv == 0 && lane == 0) {   // timing record over the first statistics rows (results invalid)
-            float* o = a.stats + (size_t)blockIdx.x * 8;
-            o[0] = (float)t_mfma; o[1] = (float)t_bar; o[2] = (float)t_epi; o[3] = (float)count;
-            float* o3 = a.stats + 8192 + (size_t)blockIdx.x * 4;   // absolute 100 MHz ticks (low 24 bits: exact in a float)
-            o3[0] = (float)(t_entry & 0xFFFFFF); o3[1] = (float)(t_loop & 0xFFFFFF); o3[2] = (float)(wall_clock64() & 0xFFFFFF); o3[3] = 0.f;
-        }
-#endif
     } else {
-        // =========================================== producer: tile row pw (8 Winograd tiles) ===========================
-        const int pw = wv;
-        constexpr bool SH = NRGBD_PC_SHARED != 0;
-        constexpr int kItems = SH ? kPcShItems : kPcItems;
-        float* raw = SH ? rawb : rawb + pw * kPcRawWave;   // SH: the strip this iteration PUBLISHES into (set per iteration)
-        const float* rawT = raw;                            // ... and the one it TRANSFORMS from
-        const int w4 = lane & 3;
-        // load / publish items: item = lane + 64u -> strip pixel pi = item >> 2 in (row, de-interleaved column) order
-        // item u of this lane -> strip row, image-order column and strip offset (recomputed where needed: a few integer
-        // operations instead of 15 live registers)
-        // SH: item = 192 pw + lane + 64 u over the whole 10-row halo (every halo word has ONE loader)
-        auto item_id = [&](int u) { return (SH ? 192 * pw : 0) + lane + 64 * u; };
-        auto item_rr = [&](int u) { return (item_id(u) >> 2) / 18; };
-        auto item_cp = [&](int u) { const int pi = item_id(u) >> 2; return pi - (pi / 18) * 18; };
-        auto item_col = [&](int u) { const int cp = item_cp(u); return cp < 9 ? 2 * cp : 2 * cp - 17; };   // even columns first, then odd
-        // strip offset an item is published at; the 32 lanes without a fifth item (288 = 4.5 x 64) write a zero into the
-        // strip's 8 pad pixels (columns 18, 19 of the 20-pixel row pitch) so that the publish loop has no per-lane branch
-        int wr_off[kPcNPFx];
-#pragma unroll
-        for (int u = 0; u < kPcNPFx; ++u) {
-            const int item = item_id(u), e = (item - kItems) >> 2;
-            wr_off[u] = item < kItems ? (item_rr(u) * kPcRawW + item_cp(u)) * kCB + w4 * 4
-                                      : ((e >> 1) * kPcRawW + 18 + (e & 1)) * kCB + w4 * 4;
-        }
-        // transform item of this lane: (tile of the row, 16-byte word, half of the xi rows); 16 consecutive lanes = 4 tiles x 4
-        // words: conflict-free strip reads (the four tiles' columns are consecutive strip pixels) and V writes
-        const int tword = lane & 3, txl = ((lane >> 5) << 2) | ((lane >> 2) & 3), thalf = (lane >> 4) & 1;
-        const int ttile = pw * 8 + txl;
-        // Row transform without per-lane selects: the lane reads its three strip rows in a lane-dependent ORDER (R0, R1, R2) and
-        // computes ya = R0 - R1, yb = R1 + sg * R2:
-        //   half 0 (xi_y 0, 1): R = strip rows (0, 2, 1), sg = +1 ->  d0 - d2,  d2 + d1
-        //   half 1 (xi_y 2, 3): R = strip rows (2, 1, 3), sg = -1 ->  d2 - d1,  d1 - d3
-        // (strip columns of tile txl: cc = 0 at column pixel txl, cc = 1: +9 pixels, cc = 2: +1, cc = 3: +10)
-        const int rdc = txl * kCB + tword * 4 + (SH ? 2 * pw * kPcRawW * kCB : 0);   // SH: the tile row's halo rows start at strip row 2 pw
-        const int rdR0 = (thalf ? 2 : 0) * kPcRawW * kCB + rdc, rdR1 = (thalf ? 1 : 2) * kPcRawW * kCB + rdc,
-                  rdR2 = (thalf ? 3 : 1) * kPcRawW * kCB + rdc;
-        const float sg = thalf ? -1.f : 1.f;
-        float m1 = -1.f;                    // opaque to the optimiser: fma(a, -1, c) would otherwise be folded into four scalar
-        asm volatile("" : "+v"(m1));        // v_sub_f32; as a register operand it stays one v_pk_fma_f32 per pair (same rounding)
-
-        // Per-tile bookkeeping of this lane's items: in-plane element offset (a harmless in-tensor offset when outside),
-        // inside-the-image bits, owner bits (materialise target).  Two books: the raw words run TWO stages ahead of their
-        // use, so the last two stages of a tile already load the next tile's words.
-        unsigned cur_off[kPcNPFx], cur_own = 0, nxt_off[kPcNPFx], nxt_own = 0;   // BYTE offsets
-        float cur_keep[kPcNPFx], nxt_keep[kPcNPFx];                               // 1 inside the image, 0 outside (zero padding)
-        auto setup = [&](const PcTile& t, unsigned (&b_off)[kPcNPFx], float (&b_keep)[kPcNPFx], unsigned& b_own) __attribute__((always_inline)) {
-            b_own = 0;
-#pragma unroll
-            for (int u = 0; u < kPcNPFx; ++u) {
-                const int rr = item_rr(u), hy = SH ? rr : 2 * pw + rr, hx = item_col(u);
-                const int gy = t.y0 + t.py + DIL * (hy - 1), gx = t.x0 + t.px + DIL * (hx - 1);
-                const bool in = item_id(u) < kItems && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-                const unsigned n2 = KD == 3 ? 0u : (unsigned)t.n;
-                b_off[u] = 4u * (in ? (unsigned)((((size_t)n2 * a.H + gy) * a.W + gx) * a.Cin + w4 * 4) : (unsigned)(w4 * 4));
-                b_keep[u] = in ? 1.f : 0.f;
-                const bool mine = SH ? (hy >= 1 && hy <= kPcTH) : (rr == 1 || rr == 2);   // SH: the one loader of a pixel of the tile's own 8 x 16
-                if (in && mine && hx >= 1 && hx <= kPcTW) b_own |= 1u << u;
-            }
-        };
-        // One register set per stage parity: raw words (+ residual words) and the (scale, shift) of the stage's 4 channels.
-        // A set is refilled for stage s+2 right after stage s has published it, so a load has two stage periods to land:
-        // with a single set the chain load -> publish -> next load made the producers' period = memory latency + publish
-        // (measured 2.8 us against the consumers' 2.0 us of MFMAs), i.e. the matrix pipe waited for the producers.
-        struct Regs { f32x4 pre[kPcNPFx]; f32x4 prer[RES ? kPcNPFx : 1]; f32x4 ss[2]; f32x4 rs[2]; };
-        PcTile tl = pc_decode<KD, DIL>(first, a), tn = tl;
-        // raw words of stage s -> registers; nx: the stage belongs to the NEXT tile (book nxt_*, tile tn).  The book is
-        // selected per value, not per pointer: a pointer select would force both books into scratch memory.
-        auto issue = [&](bool nx, int s, Regs& r) __attribute__((always_inline)) {
-            const int cb = s / KD, kd = s - cb * KD;
-            r.ss[0] = r.ss[1] = r.rs[0] = r.rs[1] = f32x4{1.f, 1.f, 0.f, 0.f};
-            if constexpr (EPI == 0) {
-                r.ss[0] = *reinterpret_cast<const f32x4*>(ssl + 2 * (cb * kCB + w4 * 4));
-                r.ss[1] = *reinterpret_cast<const f32x4*>(ssl + 2 * (cb * kCB + w4 * 4) + 4);
-                if constexpr (RES) {
-                    r.rs[0] = *reinterpret_cast<const f32x4*>(ssl + 2 * a.Cin + 2 * (cb * kCB + w4 * 4));
-                    r.rs[1] = *reinterpret_cast<const f32x4*>(ssl + 2 * a.Cin + 2 * (cb * kCB + w4 * 4) + 4);
-                }
-            }
-            const int tz = nx ? tn.n : tl.n;
-            const int z = KD == 3 ? min(max(tz + kd - 1, 0), a.N - 1) : 0;   // clamped: an outside slice is zeroed when published
-            // uniform 64-bit base + per-lane 32-bit byte offset: the global_load saddr form, no per-lane 64-bit address math
-            const size_t base = ((size_t)z * plane + (size_t)(cb * kCB)) * sizeof(float);
-            const __amdgpu_buffer_rsrc_t xb = pc_rsrc(reinterpret_cast<const char*>(a.x) + base);
-            const __amdgpu_buffer_rsrc_t rb = pc_rsrc(reinterpret_cast<const char*>(RES ? a.res : a.x) + base);
-#pragma unroll
-            for (int u = 0; u < kPcNPFx; ++u) {
-                const unsigned o = nx ? nxt_off[u] : cur_off[u];
-                r.pre[u] = pc_bload(xb, o);
-                if constexpr (RES) r.prer[u] = pc_bload(rb, o);
-            }
-        };
-        setup(tl, cur_off, cur_keep, cur_own);
-        Regs set0, set1;
-        issue(false, 0, set0);
-        issue(false, 1, set1);               // NS >= 2 (checked by the launcher)
-        int qbuf = 0;
-#ifdef NRGBD_DEV
-        long t_pub = 0, t_tr = 0, t_pbar = 0, t_q0 = 0, t_q1 = 0, t_q2 = 0;
-#endif
-        bool has_next = false;
-        bool interior = false;   // the current tile's whole halo lies inside the image (set per tile below)
-        int gi = 0;              // iterations so far (SH: strip parity; the transform lags one iteration)
-        // (3) input transform B^T d B of this lane's (tile, word): rows (2 of the 4 xi_y), then columns; strip rawT -> V[qbuf]
-        auto transform = [&]() __attribute__((always_inline)) {
-            f32x4 ya[4], yb[4];
-#pragma unroll
-            for (int cc = 0; cc < 4; ++cc) {
-                const int co = ((cc & 1) * 9 + (cc >> 1)) * kCB;
-                const f32x4 R0 = *reinterpret_cast<const f32x4*>(rawT + rdR0 + co);
-                const f32x4 R1 = *reinterpret_cast<const f32x4*>(rawT + rdR1 + co);
-                const f32x4 R2 = *reinterpret_cast<const f32x4*>(rawT + rdR2 + co);
-                ya[cc] = pk_fma_s(R1, m1, R0);   // R0 - R1
-                yb[cc] = pk_fma_s(R2, sg, R1);     // R1 +- R2
-            }
-            float* Vq = Vb + qbuf * kPcV;
-            const int xa = (2 * thalf) * 4, xb = (2 * thalf + 1) * 4;
-            *reinterpret_cast<f32x4*>(Vq + pc_slot(xa + 0, ttile, tword)) = pk_fma_s(ya[2], m1, ya[0]);   // y0 - y2
-            *reinterpret_cast<f32x4*>(Vq + pc_slot(xa + 1, ttile, tword)) = pk_add(ya[1], ya[2]);
-            *reinterpret_cast<f32x4*>(Vq + pc_slot(xa + 2, ttile, tword)) = pk_fma_s(ya[1], m1, ya[2]);   // y2 - y1
-            *reinterpret_cast<f32x4*>(Vq + pc_slot(xa + 3, ttile, tword)) = pk_fma_s(ya[3], m1, ya[1]);   // y1 - y3
-            *reinterpret_cast<f32x4*>(Vq + pc_slot(xb + 0, ttile, tword)) = pk_fma_s(yb[2], m1, yb[0]);
-            *reinterpret_cast<f32x4*>(Vq + pc_slot(xb + 1, ttile, tword)) = pk_add(yb[1], yb[2]);
-            *reinterpret_cast<f32x4*>(Vq + pc_slot(xb + 2, ttile, tword)) = pk_fma_s(yb[1], m1, yb[2]);
-            *reinterpret_cast<f32x4*>(Vq + pc_slot(xb + 3, ttile, tword)) = pk_fma_s(yb[3], m1, yb[1]);
-        };
-        // one stage: publish set r (stage s of the current tile), refill it for stage s+2, transform, barrier
-        auto stage = [&](int s, Regs& r) __attribute__((always_inline)) {
-#ifdef NRGBD_DEV
-            const long p0 = wall_clock64();
-            long p1 = p0;
-#endif
-            const int cb = s / KD, kd = s - cb * KD;
-            const int z = KD == 3 ? tl.n + kd - 1 : tl.n;
-            const bool zin = KD != 3 || (z >= 0 && z < a.N);
-            if constexpr (SH) { raw = rawb + (gi & 1) * kPcShStrip; rawT = rawb + ((gi & 1) ^ 1) * kPcShStrip; }
-            if (!(abl & 2)) {
-#ifdef NRGBD_DEV
-                if (abl & 64) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-                const long q0 = wall_clock64();
-#endif
-                if (!(abl & 8)) {   // (1) normalise / activate the prefetched words and publish them to this wave's strip
-                    // Straight-line, packed, no per-lane branches or selects: as a chain of exec-masked blocks this phase took
-                    // 0.74 us alone and 2.0 us beside the consumers' MFMA stream — longer than the MFMAs it has to stay ahead of.
-                    if (!zin) {   // a depth tap outside the volume: the whole slice is zero padding
-#pragma unroll
-                        for (int u = 0; u < kPcNPFx; ++u) *reinterpret_cast<f32x4*>(raw + wr_off[u]) = f32x4{0.f, 0.f, 0.f, 0.f};
-                    } else {
-                        // (scale, shift) pairs re-paired for the packed FMAs: channels (0,1) and (2,3); identity = (1, 0)
-                        asm volatile("" : "+v"(r.ss[0]), "+v"(r.ss[1]));   // re-paired HERE, not behind their loads
-                        if constexpr (RES) asm volatile("" : "+v"(r.rs[0]), "+v"(r.rs[1]));
-                        const f32x2 sc01 = r.ss[0].lo, sh01 = r.ss[0].hi, sc23 = r.ss[1].lo, sh23 = r.ss[1].hi;   // the LDS table is stored pre-paired (pc_ss_slot)
-                        const f32x2 rc01 = r.rs[0].lo, rh01 = r.rs[0].hi, rc23 = r.rs[1].lo, rh23 = r.rs[1].hi;
-                        const bool wmat = MAT && (KD != 3 || kd == 1) && tl.cg == 0;
-                        // Breadth-first over the 5 items — all FMAs, then all ReLUs, then all masks, then the stores — and
-                        // pinned in that order: beside the consumer's MFMA stream a VALU instruction that has to wait for
-                        // its predecessor's result loses the issue port to the next MFMA (32 cycles), an independent one
-                        // issues back to back.
-                        // (with a residual operand: in two groups of items, which keeps the phase inside the register budget)
-                        auto group = [&](auto u0_tag, auto u1_tag, auto interior_tag) __attribute__((always_inline)) {
-                            constexpr int U0 = decltype(u0_tag)::value, U1 = decltype(u1_tag)::value, NU = U1 - U0;
-                            constexpr bool INTERIOR = decltype(interior_tag)::value;   // every item of every lane inside the image: no padding mask
-                            f32x2 lo[NU], hi[NU];
-                            if constexpr (EPI == 1) {   // the R-Net form has no prologue: no identity FMAs (x * 1 + 0 is not folded: -0)
-#pragma unroll
-                                for (int i = 0; i < NU; ++i) { lo[i] = r.pre[U0 + i].lo; hi[i] = r.pre[U0 + i].hi; }
-                            } else {
-#pragma unroll
-                                for (int i = 0; i < NU; ++i) {
-                                    lo[i] = __builtin_elementwise_fma(r.pre[U0 + i].lo, sc01, sh01);
-                                    hi[i] = __builtin_elementwise_fma(r.pre[U0 + i].hi, sc23, sh23);
-                                }
-                            }
-                            __builtin_amdgcn_sched_barrier(0);
-                            if (EPI == 0 && a.x_relu) {
-#pragma unroll
-                                for (int i = 0; i < NU; ++i) { lo[i].x = relu1(lo[i].x); lo[i].y = relu1(lo[i].y); hi[i].x = relu1(hi[i].x); hi[i].y = relu1(hi[i].y); }
-                            }
-                            __builtin_amdgcn_sched_barrier(0);
-                            if constexpr (RES) {
-                                f32x2 ql[NU], qh[NU];
-#pragma unroll
-                                for (int i = 0; i < NU; ++i) {
-                                    ql[i] = __builtin_elementwise_fma(r.prer[U0 + i].lo, rc01, rh01);
-                                    qh[i] = __builtin_elementwise_fma(r.prer[U0 + i].hi, rc23, rh23);
-                                }
-                                __builtin_amdgcn_sched_barrier(0);
-                                if (a.res_relu) {
-#pragma unroll
-                                    for (int i = 0; i < NU; ++i) { ql[i].x = relu1(ql[i].x); ql[i].y = relu1(ql[i].y); qh[i].x = relu1(qh[i].x); qh[i].y = relu1(qh[i].y); }
-                                }
-                                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                                for (int i = 0; i < NU; ++i) { lo[i] = lo[i] + ql[i]; hi[i] = hi[i] + qh[i]; }
-                                __builtin_amdgcn_sched_barrier(0);
-                            }
-                            // zero padding applies to the ACTIVATED tensor: out-of-image lanes (their loads read a harmless
-                            // in-tensor word) are multiplied by 0
-                            if constexpr (!INTERIOR) {
-#pragma unroll
-                                for (int i = 0; i < NU; ++i) {
-                                    const f32x2 kk = {cur_keep[U0 + i], cur_keep[U0 + i]};
-                                    lo[i] = lo[i] * kk; hi[i] = hi[i] * kk;
-                                }
-                                __builtin_amdgcn_sched_barrier(0);
-                            }
-#pragma unroll
-                            for (int i = 0; i < NU; ++i) {
-                                const int u = U0 + i;
-                                const f32x4 v = __builtin_shufflevector(lo[i], hi[i], 0, 1, 2, 3);
-                                // the activated input is written once: by the wave that owns the pixel, at the centre tap
-                                if (MAT && wmat) {
-                                    if ((cur_own >> u) & 1u)
-                                        *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(a.mat) + ((size_t)(KD == 3 ? z : 0) * plane + (size_t)(cb * kCB)) * sizeof(float) + cur_off[u]) = v;
-                                }
-                                *reinterpret_cast<f32x4*>(raw + wr_off[u]) = v;
-                            }
-                        };
-                        // a tile whose halo lies inside the image needs no zero-padding mask (its pad pixels of the strip — the
-                        // fifth item of lanes 32..63 — are never read by the transform)
-                        if (interior) {
-                            if constexpr (RES && kPcNPFx > 3) {
-                                group(std::integral_constant<int, 0>{}, std::integral_constant<int, 3>{}, std::true_type{});
-                                group(std::integral_constant<int, 3>{}, std::integral_constant<int, kPcNPFx>{}, std::true_type{});
-                            } else {
-                                group(std::integral_constant<int, 0>{}, std::integral_constant<int, kPcNPFx>{}, std::true_type{});
-                            }
-                        } else if constexpr (RES && kPcNPFx > 3) {
-                            group(std::integral_constant<int, 0>{}, std::integral_constant<int, 3>{}, std::false_type{});
-                            group(std::integral_constant<int, 3>{}, std::integral_constant<int, kPcNPFx>{}, std::false_type{});
-                        } else {
-                            group(std::integral_constant<int, 0>{}, std::integral_constant<int, kPcNPFx>{}, std::false_type{});
-                        }
-                    }
-                }
-#ifdef NRGBD_DEV
-                const long q1 = wall_clock64();
-#endif
-                // (2) refill the set: stage s+2 of this tile, or stage s+2-NS of the next one
-                {
-                    // UNCONDITIONAL (the last two stages of the last tile re-read this tile's first two: harmless, never used)
-                    const bool nx = s + 2 >= NS;
-                    issue(nx && has_next, nx ? s + 2 - NS : s + 2, r);
-                }
-#ifdef NRGBD_DEV
-                const long q2 = wall_clock64();
-#endif
-                if constexpr (!SH) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the strip is wave-private: in-order LDS, no barrier
-#ifdef NRGBD_DEV
-                p1 = wall_clock64();
-                t_q0 += q0 - p0; t_q1 += q1 - q0; t_q2 += q2 - q1;
-#endif
-                if (!(abl & 4) && (!SH || gi > 0)) transform();   // SH: of the stage published one iteration ago
-            }
-#ifdef NRGBD_DEV
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            const long p2 = wall_clock64();
-#endif
-            __syncthreads();
-#ifdef NRGBD_DEV
-            t_pub += p1 - p0; t_tr += p2 - p1; t_pbar += wall_clock64() - p2;
-#endif
-            if (!SH || gi > 0) qbuf = qbuf == kPcNBuf - 1 ? 0 : qbuf + 1;
-            ++gi;
-        };
+        // =========================================== producer: tile row wv (8 Winograd tiles) ===========================
+        PcProd P;
+        P.p = pc_items(wv, lane);
+        P.Vb = Vb; P.rawb = rawb; P.ssl = ssl;
+        P.plane = (unsigned)((size_t)a.H * a.W * a.Cin);
+        P.tl = pc_decode<KD, DIL>(first, a); P.tn = P.tl;
+        pc_book<KD, DIL>(a, P.p, P.tl, P.cur);
+        PcRegs<RES> set0, set1;
+        pc_issue<KD, RES, EPI>(a, P, false, 0, set0);
+        pc_issue<KD, RES, EPI>(a, P, false, 1, set1);   // NS >= 2 (checked by the launcher)
+        P.qbuf = 0; P.gi = 0;
         for (int it = 0; it < count; ++it) {
-            has_next = it + 1 < count;
-            interior = tl.y0 + tl.py - DIL >= 0 && tl.y0 + tl.py + DIL * kPcTH < a.H && tl.x0 + tl.px - DIL >= 0 && tl.x0 + tl.px + DIL * kPcTW < a.W;
+            P.has_next = it + 1 < count;
+            P.interior = P.tl.y0 + P.tl.py - DIL >= 0 && P.tl.y0 + P.tl.py + DIL * kPcTH < a.H && P.tl.x0 + P.tl.px - DIL >= 0 && P.tl.x0 + P.tl.px + DIL * kPcTW < a.W;
             if constexpr (!ODD) {   // stages in pairs: the register set of a stage is static
                 for (int s = 0; s < NS; s += 2) {
                     // the book of the next tile is needed from the first refill that reaches into it (stage NS-2 refills stage 0)
-                    if (s + 2 == NS && has_next) { tn = pc_decode<KD, DIL>(first + (it + 1) * step, a); setup(tn, nxt_off, nxt_keep, nxt_own); }
-                    stage(s, set0);
-                    stage(s + 1, set1);
+                    if (s + 2 == NS && P.has_next) { P.tn = pc_decode<KD, DIL>(first + (it + 1) * step, a); pc_book<KD, DIL>(a, P.p, P.tn, P.nxt); }
+                    pc_stage<KD, RES, EPI, MAT>(a, P, NS, s, set0);
+                    __syncthreads();
+                    pc_stage_end(P);
+                    pc_stage<KD, RES, EPI, MAT>(a, P, NS, s + 1, set1);
+                    __syncthreads();
+                    pc_stage_end(P);
                 }
             } else {                // odd stage count (16 input channels x 3 depth taps): set = parity of the running stage count
                 for (int s = 0; s < NS; ++s) {
-                    if (s + 2 == NS && has_next) { tn = pc_decode<KD, DIL>(first + (it + 1) * step, a); setup(tn, nxt_off, nxt_keep, nxt_own); }
-                    if (((unsigned)it * (unsigned)NS + (unsigned)s) & 1u) stage(s, set1);
-                    else stage(s, set0);
+                    if (s + 2 == NS && P.has_next) { P.tn = pc_decode<KD, DIL>(first + (it + 1) * step, a); pc_book<KD, DIL>(a, P.p, P.tn, P.nxt); }
+                    if (((unsigned)it * (unsigned)NS + (unsigned)s) & 1u) { pc_stage<KD, RES, EPI, MAT>(a, P, NS, s, set1); __syncthreads(); }
+                    else { pc_stage<KD, RES, EPI, MAT>(a, P, NS, s, set0); __syncthreads(); }
+                    pc_stage_end(P);
                 }
             }
-            tl = tn;
-#pragma unroll
-            for (int u = 0; u < kPcNPFx; ++u) { cur_off[u] = nxt_off[u]; cur_keep[u] = nxt_keep[u]; }
-            cur_own = nxt_own;
+            P.tl = P.tn;
+            P.cur = P.nxt;
         }
-        if constexpr (SH) {                    // the last published stage
-            rawT = rawb + ((gi & 1) ^ 1) * kPcShStrip;
-            if (!(abl & (2 | 4))) transform();
-            __syncthreads();
-        }
+        pc_transform(P.p, rawb + ((P.gi & 1) ^ 1) * kPcShStrip, Vb + P.qbuf * kPcV);   // the last published stage
+        __syncthreads();
         __syncthreads();                       // the consumers' last two stages
         __syncthreads();
-#ifdef NRGBD_DEV
-        if ((abl & 64) && a.stats && wv == 0 && lane == 0) {
-            float* o = a.stats + (size_t)blockIdx.x * 8 + 4;
-            o[0] = (float)t_pub; o[1] = (float)t_tr; o[2] = (float)t_pbar; o[3] = 0.f;
-            float* o2 = a.stats + 4096 + (size_t)blockIdx.x * 4;
-            o2[0] = (float)t_q0; o2[1] = (float)t_q1; o2[2] = (float)t_q2; o2[3] = 0.f;
-        }
-#endif
     }
 }
 
@@ -700,6 +691,38 @@ __global__ __launch_bounds__(256) void conv_wino_pack_kernel(const float* __rest
     wp[idx] = (float)u;
 }
 
+// ---- host side of conv_wino_pc_kernel, shared by nrgbd_conv_wino_f32 and nrgbd_conv_wino_rnet_ex_f32 ----
+// persistent workgroups: one per CU, or one per tile where the list is shorter
+static int pc_workgroups(long ntiles, int* nwg) {
+    int dev = 0, ncu = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e != hipSuccess) return (int)e;
+    if (ncu <= 0) return NRGBD_E_ARG;
+    *nwg = ntiles < ncu ? (int)ntiles : ncu;
+    return NRGBD_OK;
+}
+
+struct PcLaunch { int nwg; size_t lds; int lds_attr; hipStream_t stream; };   // lds: this call's dynamic LDS; lds_attr: the function's opt-in
+
+// one instantiation: > 64 KB of dynamic LDS needs the opt-in, once per function and device (common.hpp set_max_dynamic_lds)
+template <int KD, int DIL, bool RES, bool ODD = false, int EPI = 0, bool MAT = false, bool HALF = false>
+static hipError_t pc_launch(const PcLaunch& L, const WinoPcArgs& a) {
+    const hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void*>(&conv_wino_pc_kernel<KD, DIL, RES, ODD, EPI, MAT, HALF>), L.lds_attr);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((conv_wino_pc_kernel<KD, DIL, RES, ODD, EPI, MAT, HALF>), dim3(L.nwg), dim3(512), L.lds, L.stream, a);
+    return hipSuccess;
+}
+
+// the four (residual, materialise) forms of one <KD, DIL, HALF> (even stage count, EPI = 0)
+template <int KD, int DIL, bool HALF>
+static hipError_t pc_launch_forms(const void* res, const void* mat, const PcLaunch& L, const WinoPcArgs& a) {
+    if (res && mat) return pc_launch<KD, DIL, true, false, 0, true, HALF>(L, a);
+    if (res) return pc_launch<KD, DIL, true, false, 0, false, HALF>(L, a);
+    if (mat) return pc_launch<KD, DIL, false, false, 0, true, HALF>(L, a);
+    return pc_launch<KD, DIL, false, false, 0, false, HALF>(L, a);
+}
+
 }  // namespace nrgbd
 
 extern "C" int nrgbd_conv_wino_pack(const float* w, float* w_wino, int Cin, int Cout, int kd, int transposed, void* stream) {
@@ -750,58 +773,26 @@ extern "C" int nrgbd_conv_wino_f32(const float* x, const float* x_ss, int x_relu
     const long nt = (long)rows * (half ? 1 : Cout / 64);
     if (nt >= (1L << 30)) return NRGBD_E_SHAPE;
     WinoPcArgs a{x, x_ss, res, res_ss, materialized, w_wino, y, stats, x_relu, res_relu, N, H, W, Cin, Cout, (int)nt, half ? 2 * rows : rows,
-                 nullptr, 0, 0, 0, 0, dev_env_int("NRGBD_WINO_ABL")};
-    int dev = 0, ncu = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return (int)e;
-    if (ncu <= 0) return NRGBD_E_ARG;
-    const int nwg = nt < ncu ? (int)nt : ncu;   // persistent: one workgroup per CU
-    const size_t lds = (size_t)(kPcNBuf * kPcV + kPcStrips + 4 * Cin) * sizeof(float);   // 96 KB V + 25.6 (20) KB strips + (scale, shift) tables
+                 nullptr, 0, 0, 0, 0, 0};
+    int nwg = 0;
+    const int rc = pc_workgroups(nt, &nwg);
+    if (rc != NRGBD_OK) return rc;
+    const size_t lds = (size_t)(kPcNBuf * kPcV + kPcStrips + 4 * Cin) * sizeof(float);   // 96 KB V + 25.6 KB strips (2 x 12.8) + (scale, shift) tables
     // The opt-in for > 64 KB of dynamic LDS is a property of the FUNCTION, and a launch recorded in a hipGraph is replayed under whatever
     // value the function carries at that moment: it is therefore always set to the form's maximum (Cin = 2048), never to this call's size —
     // a later eager call with fewer channels would otherwise shrink it under a captured launch with more (round 6: a training graph
     // replayed after an eager iteration ran with part of its (scale, shift) tables cut off)
     const int lds_attr = (int)((size_t)(kPcNBuf * kPcV + kPcStrips + 4 * 2048) * sizeof(float));
-    hipStream_t st = (hipStream_t)stream;
-#define NRGBD_WINO_PC_LAUNCH(KD_, DIL_, RES_)                                                                       \
-    do { if (materialized) NRGBD_WINO_PC_LAUNCH_M(KD_, DIL_, RES_, true); else NRGBD_WINO_PC_LAUNCH_M(KD_, DIL_, RES_, false); } while (0)
-#define NRGBD_WINO_PC_LAUNCH_M(KD_, DIL_, RES_, MAT_)                                                               \
-    do {                                                                                                            \
-        /* > 64 KB of dynamic LDS needs the opt-in: once per function and device (common.hpp set_max_dynamic_lds)       */ \
-        e = set_max_dynamic_lds(reinterpret_cast<const void*>(&conv_wino_pc_kernel<KD_, DIL_, RES_, false, 0, MAT_>), \
-                                lds_attr);                              \
-        if (e != hipSuccess) return (int)e;                                                                         \
-        hipLaunchKernelGGL((conv_wino_pc_kernel<KD_, DIL_, RES_, false, 0, MAT_>), dim3(nwg), dim3(512), lds, st, a); \
-    } while (0)
     const bool odd = (((Cin / kCB) * kd) & 1) != 0;
     if (odd && (kd != 3 || res || materialized)) return NRGBD_E_SHAPE;   // an odd stage count is instantiated for the K-Net's first layer only
-#define NRGBD_WINO_PC_LAUNCH_H(RES_, MAT_)                                                                          \
-    do {                                                                                                            \
-        e = set_max_dynamic_lds(reinterpret_cast<const void*>(&conv_wino_pc_kernel<1, 1, RES_, false, 0, MAT_, true>), \
-                                lds_attr);                              \
-        if (e != hipSuccess) return (int)e;                                                                         \
-        hipLaunchKernelGGL((conv_wino_pc_kernel<1, 1, RES_, false, 0, MAT_, true>), dim3(nwg), dim3(512), lds, st, a); \
-    } while (0)
-    if (half) {
-        if (res && materialized) NRGBD_WINO_PC_LAUNCH_H(true, true);
-        else if (res) NRGBD_WINO_PC_LAUNCH_H(true, false);
-        else if (materialized) NRGBD_WINO_PC_LAUNCH_H(false, true);
-        else NRGBD_WINO_PC_LAUNCH_H(false, false);
-    } else if (kd == 3 && odd) {
-        e = set_max_dynamic_lds(reinterpret_cast<const void*>(&conv_wino_pc_kernel<3, 1, false, true>), lds_attr);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((conv_wino_pc_kernel<3, 1, false, true>), dim3(nwg), dim3(512), lds, st, a);
-    } else if (kd == 3) {
-        if (res) NRGBD_WINO_PC_LAUNCH(3, 1, true); else NRGBD_WINO_PC_LAUNCH(3, 1, false);
-    } else if (dilation == 1) {
-        if (res) NRGBD_WINO_PC_LAUNCH(1, 1, true); else NRGBD_WINO_PC_LAUNCH(1, 1, false);
-    } else {
-        if (res) NRGBD_WINO_PC_LAUNCH(1, 2, true); else NRGBD_WINO_PC_LAUNCH(1, 2, false);
-    }
-#undef NRGBD_WINO_PC_LAUNCH
-#undef NRGBD_WINO_PC_LAUNCH_M
-#undef NRGBD_WINO_PC_LAUNCH_H
+    const PcLaunch L{nwg, lds, lds_attr, (hipStream_t)stream};
+    hipError_t e;
+    if (half) e = pc_launch_forms<1, 1, true>(res, materialized, L, a);
+    else if (kd == 3 && odd) e = pc_launch<3, 1, false, true>(L, a);
+    else if (kd == 3) e = pc_launch_forms<3, 1, false>(res, materialized, L, a);
+    else if (dilation == 1) e = pc_launch_forms<1, 1, false>(res, materialized, L, a);
+    else e = pc_launch_forms<1, 2, false>(res, materialized, L, a);
+    if (e != hipSuccess) return (int)e;
     NRGBD_CHECK_LAUNCH();
     return NRGBD_OK;
 }
@@ -822,27 +813,19 @@ extern "C" int nrgbd_conv_wino_rnet_ex_f32(const float* x, const float* w_wino, 
     if (nt >= (1L << 30)) return NRGBD_E_SHAPE;
     WinoPcArgs a{x, nullptr, nullptr, nullptr, nullptr, w_wino, y, nullptr, 0, 0, N, H, W, Cin, Cout, (int)nt, half ? 2 * rows : rows,
                  bias, out_lrelu, ldy, ycoff, cout_valid, 0};
-    int dev = 0, ncu = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return (int)e;
-    if (ncu <= 0) return NRGBD_E_ARG;
-    const int nwg = nt < ncu ? (int)nt : ncu;
-    const size_t lds = (size_t)(kPcNBuf * kPcV + kPcStrips) * sizeof(float);
-#define NRGBD_WINO_RNET_LAUNCH(ODD_, HALF_)                                                                              \
-    do {                                                                                                                 \
-        e = set_max_dynamic_lds(reinterpret_cast<const void*>(&conv_wino_pc_kernel<1, 1, false, ODD_, 1, false, HALF_>), \
-                                (int)lds);                                   \
-        if (e != hipSuccess) return (int)e;                                                                              \
-        hipLaunchKernelGGL((conv_wino_pc_kernel<1, 1, false, ODD_, 1, false, HALF_>), dim3(nwg), dim3(512), lds, (hipStream_t)stream, a); \
-    } while (0)
+    int nwg = 0;
+    const int rc = pc_workgroups(nt, &nwg);
+    if (rc != NRGBD_OK) return rc;
+    const size_t lds = (size_t)(kPcNBuf * kPcV + kPcStrips) * sizeof(float);   // no (scale, shift) tables: the size does not depend on the call
+    const PcLaunch L{nwg, lds, (int)lds, (hipStream_t)stream};
     // an odd stage count (the R-Net's 67 -> 80 and 131 -> 144 channel pixels): the register set of a stage = parity of the running count
     const bool odd = ((Cin / kCB) & 1) != 0;
-    if (odd && half) NRGBD_WINO_RNET_LAUNCH(true, true);
-    else if (odd) NRGBD_WINO_RNET_LAUNCH(true, false);
-    else if (half) NRGBD_WINO_RNET_LAUNCH(false, true);
-    else NRGBD_WINO_RNET_LAUNCH(false, false);
-#undef NRGBD_WINO_RNET_LAUNCH
+    hipError_t e;
+    if (odd && half) e = pc_launch<1, 1, false, true, 1, false, true>(L, a);
+    else if (odd) e = pc_launch<1, 1, false, true, 1, false, false>(L, a);
+    else if (half) e = pc_launch<1, 1, false, false, 1, false, true>(L, a);
+    else e = pc_launch<1, 1, false, false, 1, false, false>(L, a);
+    if (e != hipSuccess) return (int)e;
     NRGBD_CHECK_LAUNCH();
     return NRGBD_OK;
 }

@@ -11,26 +11,18 @@ namespace nrgbd {
 constexpr int kPcTH = 8, kPcTW = 16;            // output pixels of a tile, in units of the dilation lattice
 constexpr int kPcTiles = 32;                    // Winograd tiles per workgroup tile: ty = tile >> 3, tx = tile & 7
 constexpr int kPcRawW = 20;                     // raw strip row pitch in pixels (18 used; a multiple of 4 keeps a row's bank map)
-constexpr int kPcRawWave = 4 * kPcRawW * kCB;   // floats of one producer wave's 4-row strip (5 KB)
 constexpr int kPcV = 16 * kPcTiles * kCB;       // floats of one V buffer [16 xi][32 tiles][16] (32 KB)
 constexpr int kPcNBuf = 3;
-constexpr int kPcItems = 4 * 18 * 4;            // (row, column, 16-byte word) items of a strip
-constexpr int kPcNPF = (kPcItems + 63) / 64;    // per producer lane and stage (5)
-#ifndef NRGBD_WPOS
-#define NRGBD_WPOS 1   // MFMA gap (0..3) of a transform point in which the consumers request the weight line 7 points ahead
-#endif
+constexpr int kPcWPos = 1;                      // MFMA gap (0..3) of a transform point in which the consumers request the weight line 7 points ahead
 constexpr int kPcBD = 7, kPcNB = 8;             // weight ring: distance / slots
 // SHARED strips (see wino_dw.hip): the 10 x 18 halo of a stage is split once over the 256 producer lanes into a strip all four
 // producer waves share (3 words per lane instead of 5 from four overlapping 4-row private strips), published one stage ahead of
 // its transform; the stage barrier is the only synchronisation.
-#ifndef NRGBD_PC_SHARED
-#define NRGBD_PC_SHARED 1   // 0: the private-strip producers (experimental A/B builds only)
-#endif
 constexpr int kPcShRows = kPcTH + 2;                       // halo rows of a tile
 constexpr int kPcShStrip = kPcShRows * kPcRawW * kCB;      // floats of one shared strip: [10 rows][20 pixels][16] = 12.8 KB
 constexpr int kPcShItems = kPcShRows * 18 * 4;             // (row, column, 16-byte word) items of a stage: 720
-constexpr int kPcNPFx = NRGBD_PC_SHARED ? 3 : kPcNPF;      // items per producer lane and stage in wino_pc.hip
-constexpr int kPcStrips = NRGBD_PC_SHARED ? 2 * kPcShStrip : 4 * kPcRawWave;   // floats of wino_pc.hip's strip region
+constexpr int kPcNPF = 3;                                  // items per producer lane and stage in wino_pc.hip (720 = 2.8 x 256)
+constexpr int kPcStrips = 2 * kPcShStrip;                  // floats of wino_pc.hip's strip region: two strips alternate
 
 struct WinoPcArgs {
     const float* x;       // [N][H][W][Cin] raw input (pre-activation); N = depth slices when KD = 3
@@ -49,8 +41,8 @@ struct WinoPcArgs {
     int out_lrelu;
     int ldy, ycoff, cout_valid;   // EPI = 1 only: pixel stride of y (0 = Cout), first output column, columns that exist (0 = Cout):
                                   // the R-Net writes into concat buffers and pads 67 / 96 outputs to the 64-column groups
-    int abl;              // developer ablation bits, honoured by -DNRGBD_DEV builds only: 1 = producers only, 2 = consumers only,
-                          // 4 = no transform, 8 = no publish, 16 / 32 = s_setprio 2 for the consumers / producers
+    int abl;              // developer ablation bits, honoured by wino_dw.hip in -DNRGBD_DEV builds only (its header lists the bits);
+                          // wino_pc.hip ignores it
     float x_unit;         // CLAMP instantiations only: 2^-k; (scale, shift) of x are multiplied by it and the ReLU is the [0, 1]
                           // clamp of the packed FMA; the weight stream carries the factor 2^k (see nrgbd_conv_wino_dw_unit_f32)
 };
@@ -75,6 +67,18 @@ __device__ __forceinline__ PcTile pc_decode(int t, const WinoPcArgs& a) {
     r.py = par / DIL; r.px = par - r.py * DIL;
     r.y0 = ty * kPcTH * DIL; r.x0 = tx * kPcTW * DIL;
     return r;
+}
+
+// This workgroup's share [first, end) of the tile list, walked with `step`: XCD x = blockIdx % 8 owns the x-th contiguous eighth,
+// its workgroups (slots) walk it interleaved, so the workgroups of one XCD are always on neighbouring tiles
+__device__ __forceinline__ void pc_tile_share(int ntiles, int& first, int& step, int& end) {
+    const int G = (int)gridDim.x, b = (int)blockIdx.x;
+    if ((G & 7) == 0) {
+        const int xc = b & 7;
+        first = (int)(((long)ntiles * xc) >> 3) + (b >> 3);
+        end = (int)(((long)ntiles * (xc + 1)) >> 3);
+        step = G >> 3;
+    } else { first = b; end = ntiles; step = G; }
 }
 
 // LDS image of V: [xi*32 + tile][16 floats]; the 16-byte slot s of a tile is stored at slot (s + 2*((tile >> 3) & 1)) & 3, so
@@ -104,6 +108,17 @@ __device__ __forceinline__ f32x4 pc_bload(__amdgpu_buffer_rsrc_t r, unsigned byt
 __device__ __forceinline__ int pc_ss_slot(int i) {
     const int c = i >> 1, t = i & 1;
     return ((c >> 2) << 3) + (((c >> 1) & 1) << 2) + (t << 1) + (c & 1);
+}
+
+// The [Cin][2] (scale, shift) table of x (times `unit`; identity where null) -> LDS through pc_ss_slot; RES_TABLE: the one of
+// the residual operand behind it.  All 512 threads; the caller's barrier follows.
+template <bool RES_TABLE>
+__device__ __forceinline__ void pc_load_ss_table(float* ssl, int Cin, const float* x_ss, const float* res_ss, float unit) {
+    for (int i = threadIdx.x; i < 2 * Cin; i += 512) {
+        const int j = pc_ss_slot(i);  // pairs as the packed FMAs take them: (s0, s1, t0, t1 | s2, s3, t2, t3) per 4 channels
+        ssl[j] = (x_ss ? x_ss[i] : ((i & 1) ? 0.f : 1.f)) * unit;
+        if constexpr (RES_TABLE) ssl[2 * Cin + j] = res_ss ? res_ss[i] : ((i & 1) ? 0.f : 1.f);
+    }
 }
 
 // Packed fp32 helpers (v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32: two lanes of a register pair per instruction).  The

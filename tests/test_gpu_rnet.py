@@ -147,6 +147,40 @@ def test_rnet_block_in_the_winograd_domain(N, H, W, Cin, Cout):
     assert err < 2e-5 * max(1.0, want.abs().max().item())
 
 
+@pytest.mark.parametrize("lrelu", [True, False])
+@pytest.mark.parametrize("N,H,W,Cin,cout,cout_valid,ycoff,ldy", [
+    (1, 19, 35, 80, 64, 64, 0, 96),      # odd stage count (5), full form
+    (1, 19, 35, 80, 32, 3, 64, 96),      # odd + the 32-column tail: the R-Net's 67 = 64 + 3 outputs
+    (2, 16, 32, 96, 64, 50, 8, 80),      # even (6), 14 padded columns not stored
+    (1, None, 256, 80, 64, 64, 0, 72),   # odd, more tiles than CUs: a workgroup starts its second tile on the other register set
+])
+def test_rnet_winograd_forms_into_a_wider_buffer(N, H, W, Cin, cout, cout_valid, ycoff, ldy, lrelu):
+    """nrgbd_conv_wino_rnet_ex_f32 by itself in the forms the R-Net uses around its 67- and 131-channel pixels: odd and even stage
+    counts, the 64- and the 32-column kernel, fewer valid columns than packed ones, at a column offset of a wider buffer; vs
+    F.conv2d + bias (+ LeakyReLU 0.01) in float64.  Columns outside [ycoff, ycoff + cout_valid) keep the buffer's sentinel."""
+    from neuralrgbd_amd import ops
+    if H is None:                        # 8 x 16 tiles, 16 per tile row at W = 256: the first whole tile row beyond one tile per CU
+        H = 8 * (torch.cuda.get_device_properties(0).multi_processor_count // 16 + 1)
+    x = _rand(N, Cin, H, W, seed=31)
+    w = _rand(cout_valid, Cin, 3, 3, seed=32, scale=0.05)
+    b = _rand(cout_valid, seed=33, scale=0.2)
+    want = F.conv2d(x.double(), w.double(), b.double(), 1, 1)
+    if lrelu:
+        want = F.leaky_relu(want, 0.01)
+    wp = torch.zeros(cout, Cin, 3, 3, device=DEV)
+    wp[:cout_valid] = w
+    bp = torch.zeros(cout, device=DEV)
+    bp[:cout_valid] = b
+    out = torch.full((N, H, W, ldy), 7.0, device=DEV)
+    ops.conv_wino_rnet(x.permute(0, 2, 3, 1).contiguous(), ops.conv_wino_pack32(wp) if cout == 32 else ops.conv_wino_pack(wp), cout,
+                       bias=bp, lrelu=lrelu, out=out, ycoff=ycoff, cout_valid=cout_valid)
+    err = (out[..., ycoff:ycoff + cout_valid].permute(0, 3, 1, 2).double() - want).abs().max().item()
+    print("[parity] R-Net Winograd form N%d %dx%d %d->%d (%d valid at %d of %d) lrelu=%d: max|d vs fp64|=%.2e (|y|max %.1f)"
+          % (N, H, W, Cin, cout, cout_valid, ycoff, ldy, lrelu, err, want.abs().max().item()))
+    assert err < 2e-5 * max(1.0, want.abs().max().item())
+    assert bool((out[..., :ycoff] == 7.0).all()) and bool((out[..., ycoff + cout_valid:] == 7.0).all())   # nothing else touched
+
+
 @pytest.mark.parametrize("N,C,H,W,slope", [(1, 128, 16, 24, 0.01), (2, 96, 32, 48, 0.01), (1, 64, 64, 96, 1.0), (1, 256, 9, 11, 0.01), (1, 8, 5, 7, 0.01)])
 def test_bias_leaky_relu_fused_forward_and_backward(N, C, H, W, slope):
     """autograd.BiasLeakyReLUCL (the bias + LeakyReLU tail of the R-Net blocks under autograd, m_submodule.py:18-27,36-45; slope 1 =

@@ -27,7 +27,7 @@ def main():
     ap.add_argument("--only", default="", help="substring filter on the variant names (e.g. 'wino-dw')")
     ap.add_argument("--cnn", action="store_true", help="also time the feature CNN's 2-D layer shapes")
     ap.add_argument("--dev", action="store_true", help="load libnrgbd_hip_dev.so (python -m neuralrgbd_amd.build --dev): "
-                    "NRGBD_WINO_ABL=1|2 (producers only / consumers only) is honoured there")
+                    "wino_dw.hip's NRGBD_WINO_ABL bits (see tools/abl_dw.py) are honoured there")
     args = ap.parse_args()
     if args.dev:
         from neuralrgbd_amd import _lib
@@ -53,17 +53,6 @@ def main():
             continue
         ms = timeit(fn, args.iters)
         print("%-16s %8.3f ms   %6.1f TFLOP/s nominal (27-tap flops)" % (name, ms, flops / ms / 1e9))
-    if args.dev and (int(os.environ.get("NRGBD_WINO_ABL", "0")) & 64):
-        # in-kernel clocks (dev build): per workgroup [mfma, consumer barrier, epilogue, tiles | publish, transform, producer barrier]
-        st = ops.conv_wino(x, ww, 64, 3, x_ss=ss, x_relu=True)[1]
-        torch.cuda.synchronize()
-        rec = st.reshape(-1)[:256 * 8].reshape(256, 8).double().cpu()
-        per = rec[:, 3:4] * 12
-        names = ("mfma", "c-barrier", "epilogue/tile*12", "tiles", "publish", "transform", "p-barrier")
-        vals = rec.clone(); vals[:, [0, 1, 2, 4, 5, 6]] /= per
-        r2 = st.reshape(-1)[4096:4096 + 256 * 4].reshape(256, 4).double().cpu() / per
-        print("publish split: wait-vmcnt %.0f  valu+ds_write %.0f  issue-loads %.0f" % tuple(r2.median(0).values.tolist()[:3]))
-        print("in-kernel wall_clock64 (10 ns ticks) per stage, median over workgroups: " + "  ".join("%s %.0f" % (n, v) for n, v in zip(names, vals.median(0).values.tolist())))
     if args.only:
         return
     y1 = ops.conv3d(x, wd, x_ss=ss, x_relu=True)[0]
