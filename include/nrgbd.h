@@ -53,7 +53,9 @@ extern "C" {
  * 0.8: nrgbd_dpv_keyframe_maps (the LBA driver's depth / confidence maps in one launch) is new; no existing entry changed.
  * 0.9: nrgbd_costvol_bwd_det and nrgbd_costvol_bwd_det_workspace (the bit-reproducible cost-volume backward) are new; no existing
  * entry changed.  0.10: nrgbd_warp_volume_cl (the K-Net input volume for temporal windows of 3, 5 and 7 frames, padded to whole
- * 16-channel blocks) is new, and nrgbd_conv3d_wgrad_f32 also takes Cin = 32; no existing entry changed. */
+ * 16-channel blocks) is new, and nrgbd_conv3d_wgrad_f32 also takes Cin = 32; no existing entry changed.  0.10 also gained
+ * nrgbd_depth_regress_rows and nrgbd_export_depth_u16_rows (the two reductions on a channels-last volume) and C = 256 in
+ * nrgbd_logsoftmax_rows / _rows_bwd (the R-Net with candidate up-sampling); no existing entry changed, the version string stays. */
 #define NRGBD_INTERFACE_VERSION "0.10"
 const char* nrgbd_version(void);
 const char* nrgbd_strerror(int code);
@@ -335,6 +337,20 @@ int nrgbd_depth_regress(const float* logp, const float* d_candi,
 int nrgbd_export_depth_u16(const float* logp, const float* d_candi, float depth_scale, float conf_scale,
                            float* depth, float* conf, unsigned short* depth_u16, unsigned short* conf_u16,
                            int D, long n, void* stream);
+
+/*
+ * nrgbd_depth_regress_rows / nrgbd_export_depth_u16_rows — the two entries above on a CHANNELS-LAST volume logp [n][D]: the
+ * refined DPV as the R-Net's last layer writes it (models/Refine.py:104; with candidate up-sampling, Refine.py:44-49, D is four
+ * times the candidates of the low-resolution volume: 0.8 GB per volume at 768x1024 with 256), regressed (mutils/misc.py:532-548)
+ * or exported without a transposing copy.  Arguments as the planar entries; the results are the SAME BITS as theirs on the
+ * transposed copy (one accumulator per pixel, acc = acc + exp(v_k) d_k for k = 0 .. D-1 from 0.f; expf / the correctly rounded
+ * exponential respectively).  D % 4 == 0, D <= 1024 (else NRGBD_E_SHAPE); logp 16-byte aligned (else NRGBD_E_ALIGN).
+ */
+int nrgbd_depth_regress_rows(const float* logp, const float* d_candi,
+                             float* depth, float* conf, int D, long n, void* stream);
+int nrgbd_export_depth_u16_rows(const float* logp, const float* d_candi, float depth_scale, float conf_scale,
+                                float* depth, float* conf, unsigned short* depth_u16, unsigned short* conf_u16,
+                                int D, long n, void* stream);
 
 /*
  * nrgbd_warp_depth_fwd / _bwd — photometric warp through a per-pixel depth map and its gradient w.r.t. the poses.
@@ -701,9 +717,10 @@ int nrgbd_spp_concat(const float* quarter, int Cq, const float* deep, int Cd,
                      const float* bz2, const float* bss2, int bh2, int bw2, const float* bz3, const float* bss3, int bh3, int bw3,
                      int Cb, float* out, int N, int h, int w, void* stream);
 /*
- * nrgbd_logsoftmax_rows — log_softmax over the channels of channels-last rows x [rows][C] (y may be x), C in {64, 128}.
+ * nrgbd_logsoftmax_rows — log_softmax over the channels of channels-last rows x [rows][C] (y may be x), C in {64, 128, 256}.
  * Replaces: F.log_softmax(conv2_2_out, dim=1) of models/Refine.py:104 once the last R-Net convolution runs on the Winograd kernel
  * (nrgbd_conv_wino_rnet_ex_f32), whose pixels are channels-last; the refined DPV is then an [N, D, H, W] VIEW of that memory.
+ * C = 256: the up-sampled volume of a 64-candidate net (Refine.py:44-49), one wave per row.
  */
 int nrgbd_logsoftmax_rows(const float* x, float* y, long rows, int C, void* stream);
 /*
@@ -711,7 +728,7 @@ int nrgbd_logsoftmax_rows(const float* x, float* y, long rows, int C, void* stre
  * with out = log_softmax(z), g_z = g - exp(out) * sum_k g (the _d form returns scale * g_z = the gradient of its operand a;
  * scale = 1 gives the gradient of b).  Replaces: autograd through torch.log_softmax at models/basic.py:299-300,
  * models/KVNET.py:172-173 and models/Refine.py:104 (ATen's SpatialSoftMaxBackward).
- *   _d:    logp, g, gz [D][n];   _rows: y, g, gx [rows][C], C in {64, 128}
+ *   _d:    logp, g, gz [D][n];   _rows: y, g, gx [rows][C], C in {64, 128, 256}
  */
 int nrgbd_logsoftmax_d_bwd(const float* logp, const float* g, float scale, float* gz, int D, long n, void* stream);
 int nrgbd_logsoftmax_rows_bwd(const float* y, const float* g, float* gx, long rows, int C, void* stream);

@@ -47,6 +47,8 @@ SIGNATURES = {
     "nrgbd_logsoftmax_d": (_I, [_P, _P, _F, _P, _I, _L, _P]),
     "nrgbd_depth_regress": (_I, [_P, _P, _P, _P, _I, _L, _P]),
     "nrgbd_export_depth_u16": (_I, [_P, _P, _F, _F, _P, _P, _P, _P, _I, _L, _P]),
+    "nrgbd_depth_regress_rows": (_I, [_P, _P, _P, _P, _I, _L, _P]),
+    "nrgbd_export_depth_u16_rows": (_I, [_P, _P, _F, _F, _P, _P, _P, _P, _I, _L, _P]),
     "nrgbd_warp_depth_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "nrgbd_warp_depth_bwd_workgroups": (_I, [_I, _I]),
     "nrgbd_warp_depth_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),

@@ -662,7 +662,7 @@ class LogSoftmaxCL(torch.autograd.Function):
 
     @staticmethod
     def supported(x):
-        return x.dim() == 4 and x.shape[1] in (64, 128) and x.is_cuda and x.dtype == torch.float32
+        return x.dim() == 4 and x.shape[1] in (64, 128, 256) and x.is_cuda and x.dtype == torch.float32
 
     @staticmethod
     def forward(ctx, x):

@@ -148,10 +148,66 @@ __global__ __launch_bounds__(256) void export_depth_u16_kernel(const float* __re
     if (cu) cu[p] = to_u16(c * conf_scale);
 }
 
+// The two reductions above on a CHANNELS-LAST volume logp [n][D] (the refined DPV as the R-Net's last layer leaves it, Refine.py:104;
+// D = 4 x the candidates with up-sampling, Refine.py:44-49): 128 pixels x 64 candidates at a time through LDS (pitch 65: the global reads
+// are 16-byte loads along the row, the walk over a pixel's candidates is conflict-free), ONE accumulator per pixel that walks the
+// candidates in order from 0.f across the chunks — the planar kernels' association, so the bits are theirs.  64-bit offsets throughout.
+constexpr int ROWS_PX = 128;
+template <bool EXPORT>
+__global__ __launch_bounds__(256) void depth_rows_kernel(const float* __restrict__ logp, const float* __restrict__ d_candi,
+                                                         float depth_scale, float conf_scale, float* __restrict__ depth,
+                                                         float* __restrict__ conf, unsigned short* __restrict__ du,
+                                                         unsigned short* __restrict__ cu, int D, size_t n) {
+    __shared__ float tile[ROWS_PX][65];
+    const int tid = threadIdx.x;
+    const size_t p0 = (size_t)blockIdx.x * ROWS_PX;
+    const size_t p = p0 + tid;                        // the pixel of threads 0 .. ROWS_PX-1
+    float acc = 0.f, m = -INFINITY;
+    for (int c0 = 0; c0 < D; c0 += 64) {
+        const int valid = min(64, D - c0);            // a multiple of 4
+        for (int t = tid; t < ROWS_PX * 16; t += 256) {
+            const int px = t >> 4, q = (t & 15) * 4;
+            if (p0 + px < n && q < valid) {
+                const float4 v = *reinterpret_cast<const float4*>(logp + (p0 + px) * (size_t)D + c0 + q);
+                tile[px][q] = v.x; tile[px][q + 1] = v.y; tile[px][q + 2] = v.z; tile[px][q + 3] = v.w;
+            }
+        }
+        __syncthreads();
+        if (tid < ROWS_PX && p < n) {
+            for (int c = 0; c < valid; ++c) {
+                const float v = tile[tid][c];
+                if constexpr (EXPORT) acc = acc + exp_rn(v) * d_candi[c0 + c];
+                else acc = acc + expf(v) * d_candi[c0 + c];
+                m = fmaxf(m, v);
+            }
+        }
+        __syncthreads();
+    }
+    if (tid >= ROWS_PX || p >= n) return;
+    if constexpr (EXPORT) {
+        const float c = exp_rn(m);
+        if (depth) depth[p] = acc;
+        if (conf) conf[p] = c;
+        if (du) du[p] = to_u16(acc * depth_scale);
+        if (cu) cu[p] = to_u16(c * conf_scale);
+    } else {
+        if (depth) depth[p] = acc;
+        if (conf) conf[p] = m;
+    }
+}
+
+// shapes the rows entries take: D a multiple of 4 up to 1024, rows 16-byte aligned, a grid that fits
+inline int depth_rows_check(const float* logp, int D, long n) {
+    if (D <= 0 || D > 1024 || (D & 3) || n <= 0 || (n + ROWS_PX - 1) / ROWS_PX > 0x7fffffffL) return NRGBD_E_SHAPE;
+    if ((uintptr_t)logp & 15) return NRGBD_E_ALIGN;
+    return NRGBD_OK;
+}
+
 }  // namespace nrgbd
 
 namespace nrgbd {
-// log_softmax over the channels of channels-last rows x [rows][C] (C = 64: 16 lanes x 16 bytes per row; C = 128: 32 lanes): the
+// log_softmax over the channels of channels-last rows x [rows][C] (C = 64: 16 lanes x 16 bytes per row; C = 128: 32 lanes; C = 256: the
+// whole wave, the butterfly's first step then crosses the two 32-lane halves — __shfl_xor is a ds_bpermute there, any lane to any): the
 // R-Net's last layer (models/Refine.py:104 F.log_softmax(conv2_2_out, dim=1)) after its convolution moved to the Winograd kernel,
 // whose epilogue writes pixels channels-last.  One HBM pass (read + write, in place allowed); the reduction over a row is a
 // butterfly of DPP / swizzle shuffles inside its lane group, in a fixed order.
@@ -168,6 +224,17 @@ __global__ __launch_bounds__(256) void logsoftmax_rows_kernel(const float* __res
     float s = (expf(v.x - m) + expf(v.y - m)) + (expf(v.z - m) + expf(v.w - m));
 #pragma unroll
     for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if constexpr (LPR == 64) {
+        // 256 channels: log-probabilities reach -8 and beyond, where the three fp32 roundings of (v - m) - logf(s) add up to more than
+        // 1e-6 (1.1e-6 against float64 over 960 rows of unit-normal inputs).  The row's constant m + log(s) and the subtraction in
+        // double, ONE rounding at the end; the narrower forms below are what they were.  A wave is one row here, so every lane holding
+        // the same c is one wave-wide fp64 log per row, what a single lane and a broadcast would issue too.  Measured once at
+        // 2 x 768 x 1024 rows: 0.56 ms for 3.2 GB read + written (5.8 TB/s): still bound by HBM
+        const double c = (double)m + log((double)s);
+        if (live) *reinterpret_cast<float4*>(y + (r * LPR + q) * 4) = make_float4((float)((double)v.x - c), (float)((double)v.y - c),
+                                                                                 (float)((double)v.z - c), (float)((double)v.w - c));
+        return;
+    }
     const float ls = logf(s);
     if (live) *reinterpret_cast<float4*>(y + (r * LPR + q) * 4) = make_float4((v.x - m) - ls, (v.y - m) - ls, (v.z - m) - ls, (v.w - m) - ls);
 }
@@ -291,11 +358,12 @@ extern "C" int nrgbd_logsoftmax_d_bwd(const float* logp, const float* g, float s
 extern "C" int nrgbd_logsoftmax_rows_bwd(const float* y, const float* g, float* gx, long rows, int C, void* stream) {
     using namespace nrgbd;
     if (!y || !g || !gx) return NRGBD_E_NULL;
-    if (rows <= 0 || (C != 64 && C != 128)) return NRGBD_E_SHAPE;
+    if (rows <= 0 || (C != 64 && C != 128 && C != 256)) return NRGBD_E_SHAPE;
     const long threads = rows * (C / 4);
     const dim3 grid((unsigned)((threads + 255) / 256));
     if (C == 64) hipLaunchKernelGGL(logsoftmax_rows_bwd_kernel<16>, grid, dim3(256), 0, (hipStream_t)stream, y, g, gx, rows);
-    else hipLaunchKernelGGL(logsoftmax_rows_bwd_kernel<32>, grid, dim3(256), 0, (hipStream_t)stream, y, g, gx, rows);
+    else if (C == 128) hipLaunchKernelGGL(logsoftmax_rows_bwd_kernel<32>, grid, dim3(256), 0, (hipStream_t)stream, y, g, gx, rows);
+    else hipLaunchKernelGGL(logsoftmax_rows_bwd_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, y, g, gx, rows);   // a whole wave per row
     NRGBD_CHECK_LAUNCH();
     return NRGBD_OK;
 }
@@ -329,11 +397,12 @@ extern "C" int nrgbd_nll_bwd(const long long* target, long ignore_index, const f
 extern "C" int nrgbd_logsoftmax_rows(const float* x, float* y, long rows, int C, void* stream) {
     using namespace nrgbd;
     if (!x || !y) return NRGBD_E_NULL;
-    if (rows <= 0 || (C != 64 && C != 128)) return NRGBD_E_SHAPE;
+    if (rows <= 0 || (C != 64 && C != 128 && C != 256)) return NRGBD_E_SHAPE;
     const long threads = rows * (C / 4);
     const dim3 grid((unsigned)((threads + 255) / 256));
     if (C == 64) hipLaunchKernelGGL(logsoftmax_rows_kernel<16>, grid, dim3(256), 0, (hipStream_t)stream, x, y, rows);
-    else hipLaunchKernelGGL(logsoftmax_rows_kernel<32>, grid, dim3(256), 0, (hipStream_t)stream, x, y, rows);
+    else if (C == 128) hipLaunchKernelGGL(logsoftmax_rows_kernel<32>, grid, dim3(256), 0, (hipStream_t)stream, x, y, rows);
+    else hipLaunchKernelGGL(logsoftmax_rows_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, x, y, rows);   // a whole wave per row (R-Net with candidate up-sampling)
     NRGBD_CHECK_LAUNCH();
     return NRGBD_OK;
 }
@@ -364,6 +433,30 @@ extern "C" int nrgbd_export_depth_u16(const float* logp, const float* d_candi, f
     if (D <= 0 || n <= 0) return NRGBD_E_SHAPE;
     hipLaunchKernelGGL(nrgbd::export_depth_u16_kernel, dim3(nrgbd::ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream,
                        logp, d_candi, depth_scale, conf_scale, depth, conf, depth_u16, conf_u16, D, (size_t)n);
+    NRGBD_CHECK_LAUNCH();
+    return NRGBD_OK;
+}
+
+extern "C" int nrgbd_depth_regress_rows(const float* logp, const float* d_candi, float* depth, float* conf, int D, long n,
+                                        void* stream) {
+    using namespace nrgbd;
+    if (!logp || !d_candi || (!depth && !conf)) return NRGBD_E_NULL;
+    if (const int rc = depth_rows_check(logp, D, n)) return rc;
+    hipLaunchKernelGGL(depth_rows_kernel<false>, dim3(ceil_div(n, ROWS_PX)), dim3(256), 0, (hipStream_t)stream, logp, d_candi, 0.f,
+                       0.f, depth, conf, (unsigned short*)nullptr, (unsigned short*)nullptr, D, (size_t)n);
+    NRGBD_CHECK_LAUNCH();
+    return NRGBD_OK;
+}
+
+extern "C" int nrgbd_export_depth_u16_rows(const float* logp, const float* d_candi, float depth_scale, float conf_scale,
+                                           float* depth, float* conf, unsigned short* depth_u16, unsigned short* conf_u16,
+                                           int D, long n, void* stream) {
+    using namespace nrgbd;
+    if (!logp || !d_candi) return NRGBD_E_NULL;
+    if (!depth && !conf && !depth_u16 && !conf_u16) return NRGBD_E_NULL;
+    if (const int rc = depth_rows_check(logp, D, n)) return rc;
+    hipLaunchKernelGGL(depth_rows_kernel<true>, dim3(ceil_div(n, ROWS_PX)), dim3(256), 0, (hipStream_t)stream, logp, d_candi,
+                       depth_scale, conf_scale, depth, conf, depth_u16, conf_u16, D, (size_t)n);
     NRGBD_CHECK_LAUNCH();
     return NRGBD_OK;
 }

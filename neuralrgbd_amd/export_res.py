@@ -24,7 +24,8 @@ def depth_conf_u16(BV_measure, d_candi, depth_scale=1000, conf_scale=1000):
     the CPU oracle): the uint16 maps are bit-identical to the oracle's."""
     assert BV_measure.shape[0] == 1 and BV_measure.shape[1] == len(d_candi)
     d_dev = _homo._d_candi_dev(d_candi, BV_measure.device)
-    return ops.export_depth_u16(BV_measure[0], d_dev, float(depth_scale), float(conf_scale))
+    return ops.export_depth_u16(BV_measure[0], d_dev, float(depth_scale), float(conf_scale),
+                                channels_last=ops.is_channels_last_view(BV_measure[0]))     # the R-Net's view: read where it lies
 
 
 def export2pgm(fpath, im):

@@ -23,6 +23,7 @@ from . import misc as m_misc
 from . import opt_pose
 from . import ops
 from . import test_step
+from ._lib import NrgbdError
 
 DW_SCALES = [4, 2, 1]
 
@@ -150,6 +151,8 @@ class LBADepthStream:
                  use_dso_t=False, opt_next_frame=False, dw_scales=DW_SCALES):
         if len(cams_intrin) != 3:
             raise ValueError("LBADepthStream: three camera dicts (quarter, half, image size), got %d" % len(cams_intrin))
+        if getattr(model, "if_upsample_d", False):
+            raise NrgbdError("LBADepthStream: a model with if_upsample_d refines to 4 D candidates, the keyframe maps take D (the reference's LBA driver never builds one)")
         self.model = model
         self.cams_intrin = list(cams_intrin)
         self.d_candi = np.asarray(d_candi)

@@ -33,14 +33,23 @@ def depth_val_regression(BV_measure, d_candi_cur, BV_log=True):
         'BV_measure should have the same # of slices as len(d_candi_cur) !'
     d_dev = _homo._d_candi_dev(d_candi_cur, BV_measure.device)
     logp = BV_measure[0] if BV_log else torch.log(BV_measure[0])
-    depth, _ = ops.depth_regress(logp, d_dev, want_conf=False)
+    # the refined volume is an NCHW view of channels-last memory (DPVUpsampleNet.forward_log, autograd.LogSoftmaxCL): read it there
+    depth, _ = ops.depth_regress(logp, d_dev, want_conf=False, channels_last=ops.is_channels_last_view(logp))
     return depth.unsqueeze(0)
+
+
+def d_candi_up4(d_candi):
+    """The candidates of an up-sampled refined volume (KVNET(if_upsample_d=True): [1, 4D, H, W]): np.linspace(d_min, d_max, 4 D), as
+    every data loader of the reference defines them next to `dmap_up4_imgsize_digit` (mdataloader/scanNet.py:327,419,
+    kitti.py:273,378, dl_7scenes.py:250,346).  Pass them to depth_val_regression / export_res_img with such a volume."""
+    d_candi = np.asarray(d_candi)
+    return np.linspace(d_candi.min(), d_candi.max(), 4 * len(d_candi))
 
 
 def dpv_confidence(BV_measure):
     """max_d log-prob -> [1,h,w] (test_utils/export_res.py:58-59)."""
     d_dev = torch.zeros(BV_measure.shape[1], dtype=torch.float32, device=BV_measure.device)
-    _, conf = ops.depth_regress(BV_measure[0], d_dev, want_conf=True)
+    _, conf = ops.depth_regress(BV_measure[0], d_dev, want_conf=True, channels_last=ops.is_channels_last_view(BV_measure[0]))
     return conf.unsqueeze(0)
 
 

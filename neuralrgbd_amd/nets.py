@@ -790,6 +790,22 @@ class DPVUpsampleNet(_PackedWeightsMixin, nn.Module):
             and self.trans_conv1[0].out_channels == D and self.conv2_1[0].out_channels == D
         return (D, 64 if D <= 64 else 128, C0, C1, C2) if ok else None
 
+    def _levels(self):
+        """((D, Dp) at 1/4, 1/2 and full resolution) — the real and the padded candidate width of the three levels —, or None when
+        the kernels do not cover the net.  Without candidate up-sampling every level is `_widths()`'s (D, Dp).  With it
+        (upsample_D, Refine.py:44-49: trans_conv0 doubles the candidate axis, trans_conv1 doubles it again) D = 32 and 64 are
+        covered: 32 (zero-padded to 64, as a 32-candidate net) / 64 / 128 and 64 / 128 / 256; the last level is then never padded."""
+        wd = self._widths()
+        if wd is not None:
+            return ((wd[0], wd[1]),) * 3
+        D = self.conv0[0].in_channels - 64
+        D0, D1 = self.trans_conv0[0].out_channels, self.conv2_2.out_channels
+        ok = D in (32, 64) and (D0, D1) == (2 * D, 4 * D) and self.conv1[0].in_channels == D0 + 32 \
+            and self.trans_conv1[0].out_channels == D1 and self.conv2[0].in_channels == D1 + 3 and self.conv2_1[0].out_channels == D1
+        return ((D, 64), (D0, D0), (D1, D1)) if ok else None
+
+    _FEATS = (64, 32, 3)        # image-feature channels behind the candidates at the three levels (every script of the reference)
+
     def mfma_ok(self, dpv):
         """Inference on the GPU -> the hand-written kernels (forward_log), at EVERY grid and candidate count the reference's
         scripts use: the six conv2d_leakyRelu layers and conv2_2 on the Winograd kernel's R-Net form (csrc/wino_pc.hip, 8x16-pixel
@@ -798,20 +814,22 @@ class DPVUpsampleNet(_PackedWeightsMixin, nn.Module):
 
     def _embedded(self):
         """{layer: (weight, bias)} in the channel layout of the kernels' buffers: a [candidates (D) | image features (C)] concat
-        lives as [D real | Dp - D zero | C], a D-wide output as [D real | Dp - D zero].  D == Dp: the module's own tensors."""
-        D, Dp, C0, C1, C2 = self._widths()
+        lives as [D real | Dp - D zero | C], a D-wide output as [D real | Dp - D zero], with the (D, Dp) of the level it lives at
+        (`_levels`).  No level padded: the module's own tensors."""
+        lv = self._levels()
+        C0, C1, C2 = self._FEATS
         mods = {"conv0": self.conv0[0], "conv0_1": self.conv0_1[0], "trans_conv0": self.trans_conv0[0], "conv1": self.conv1[0],
                 "conv1_1": self.conv1_1[0], "trans_conv1": self.trans_conv1[0], "conv2": self.conv2[0], "conv2_1": self.conv2_1[0],
                 "conv2_2": self.conv2_2}
-        if D == Dp:
+        if all(d == dp for d, dp in lv):
             return {k: (m.weight.detach(), m.bias.detach()) for k, m in mods.items()}
         dev = self.conv2_2.weight.device
-        cat = lambda C: torch.cat((torch.arange(D, device=dev), Dp + torch.arange(C, device=dev)))      # source channel -> position
-        plain = torch.arange(D, device=dev)
-        io = {"conv0": (cat(C0), Dp + C0, cat(C0), Dp + C0), "conv0_1": (cat(C0), Dp + C0, cat(C0), Dp + C0),
-              "trans_conv0": (cat(C0), Dp + C0, plain, Dp), "conv1": (cat(C1), Dp + C1, cat(C1), Dp + C1),
-              "conv1_1": (cat(C1), Dp + C1, cat(C1), Dp + C1), "trans_conv1": (cat(C1), Dp + C1, plain, Dp),
-              "conv2": (cat(C2), Dp + C2, cat(C2), Dp + C2), "conv2_1": (cat(C2), Dp + C2, plain, Dp), "conv2_2": (plain, Dp, plain, Dp)}
+        # source channel -> position: a [candidates | C features] concat and a plain candidate output of level l
+        cat = lambda l, C: (torch.cat((torch.arange(lv[l][0], device=dev), lv[l][1] + torch.arange(C, device=dev))), lv[l][1] + C)
+        plain = lambda l: (torch.arange(lv[l][0], device=dev), lv[l][1])
+        io = {"conv0": cat(0, C0) + cat(0, C0), "conv0_1": cat(0, C0) + cat(0, C0), "trans_conv0": cat(0, C0) + plain(1),
+              "conv1": cat(1, C1) + cat(1, C1), "conv1_1": cat(1, C1) + cat(1, C1), "trans_conv1": cat(1, C1) + plain(2),
+              "conv2": cat(2, C2) + cat(2, C2), "conv2_1": cat(2, C2) + plain(2), "conv2_2": plain(2) + plain(2)}
         out = {}
         for k, m in mods.items():
             in_idx, cin_p, out_idx, cout_p = io[k]
@@ -899,13 +917,14 @@ class DPVUpsampleNet(_PackedWeightsMixin, nn.Module):
         if key not in cache:
             for k in [k for k in cache if k[1:] != key[1:]]:
                 del cache[k]
-            D, Dp, C0, C1, C2 = self._widths()
+            (D, Dp), (_, Dp1), (_, Dp2) = self._levels()
+            C0, C1, C2 = self._FEATS
             z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
             p32 = lambda c: (c + 15) // 16 * 16                       # whole 16-channel Winograd stages (_rnet_packed pads its weights to the same widths)
-            w0, w1, w2 = p32(Dp + C0), p32(Dp + C1), p32(Dp + C2)     # 128, 96, 80 at Dp = 64; 192, 160, 144 at Dp = 128
+            w0, w1, w2 = p32(Dp + C0), p32(Dp1 + C1), p32(Dp2 + C2)   # 128, 96, 80 at Dp = 64; 192, 160, 144 at Dp = 128; up-sampling from 64: 128, 160, 272
             cache[key] = {"x0": z(n, h, w, w0), "a0": z(n, h, w, w0), "b0": z(n, h, w, w0),
                           "c1": z(n, 2 * h, 2 * w, w1), "a1": z(n, 2 * h, 2 * w, w1), "b1": z(n, 2 * h, 2 * w, w1),
-                          "c2": z(n, 4 * h, 4 * w, w2), "g2": z(n, 4 * h, 4 * w, w2), "h2": z(n, 4 * h, 4 * w, Dp)}
+                          "c2": z(n, 4 * h, 4 * w, w2), "g2": z(n, 4 * h, 4 * w, w2), "h2": z(n, 4 * h, 4 * w, Dp2)}
             if D != Dp:     # staging of the candidate planes: rows D.. stay -inf (exp -> the zero padding of the first concat)
                 cache[key]["dpv"] = torch.full((n, Dp, h, w), float("-inf"), dtype=torch.float32, device=dev)
         return cache[key]
@@ -913,7 +932,8 @@ class DPVUpsampleNet(_PackedWeightsMixin, nn.Module):
     def forward_log(self, dpv_log, img_features):
         """Same result as forward(torch.exp(dpv_log), img_features) (models/KVNET.py:128,176 + Refine.py:79-107) with the
         exp fused into the first concat.  Inference on the GPU runs on the hand-written kernels (a net they do not cover —
-        candidate up-sampling, other feature widths, D > 128 — raises NrgbdError: there is no vendor-library route);
+        other feature widths, D > 128, candidate up-sampling from other than 32 / 64 candidates — raises NrgbdError: there is no
+        vendor-library route).  With candidate up-sampling the result is [n, 4 D, 4 h, 4 w];
         `img_features` are ONE image's features, shared by every sample of the batch (KVNET.forward refines BV_cur and DPV of
         a frame as one batch of 2)."""
         first = dpv_log[0] if isinstance(dpv_log, (list, tuple)) else dpv_log
@@ -922,10 +942,11 @@ class DPVUpsampleNet(_PackedWeightsMixin, nn.Module):
                 dpv_log = torch.cat(list(dpv_log), dim=0)
             return self.forward(torch.exp(dpv_log), img_features)
         from . import ops
-        wd = self._widths()
-        if wd is None:
-            raise _no_kernel("this R-Net (candidate up-sampling, image-feature widths other than 64 / 32 / 3, or more than 128 candidates)")
-        D, Dp = wd[0], wd[1]
+        lv = self._levels()
+        if lv is None:
+            raise _no_kernel("this R-Net (image-feature widths other than 64 / 32 / 3, more than 128 candidates, or candidate "
+                             "up-sampling from other than 32 or 64 candidates)")
+        (D, Dp), (_, Dp1), (Dl, Dpl) = lv          # candidates (real, padded) at 1/4 resolution; padded at 1/2; at full resolution
         quarter, half, full = img_features
         if isinstance(dpv_log, (list, tuple)):     # the frame's two volumes (BV_cur, DPV) as they are: no torch.cat pass
             vols = [v[i:i + 1] for v in dpv_log for i in range(v.shape[0])]
@@ -975,18 +996,18 @@ class DPVUpsampleNet(_PackedWeightsMixin, nn.Module):
         # level 1/2: transposed conv (4 sub-pixel phases) straight into channels 0..Dp-1 of the concat buffer; features behind
         c1 = buf["c1"]
         deconv(x, pk["t0"]["all"], c1)
-        ops.scatter_channels(half[0], c1, Dp)          # the 1/2-resolution features behind the candidates of every sample (csrc/glue.hip)
+        ops.scatter_channels(half[0], c1, Dp1)         # the 1/2-resolution features behind the candidates of every sample (csrc/glue.hip)
         x = conv_w(conv_w(c1, "conv1", buf["a1"]), "conv1_1", buf["b1"])
         # full resolution: Dp + 3 channels in 16-aligned pixels (padding channels zero, with zero weights)
         c2 = buf["c2"]
         deconv(x, pk["t1"]["all"], c2)
-        ops.scatter_channels(full[0], c2, Dp)
+        ops.scatter_channels(full[0], c2, Dpl)
         x = conv_w(conv_w(c2, "conv2", buf["g2"]), "conv2_1", buf["h2"])
         # conv2_2 + bias on the Winograd kernel (pixels channels-last), then log-softmax over the channels of every pixel in place:
         # the refined DPV is handed out as an [n, D, H, W] VIEW of that channels-last memory (round 4; the direct kernel with the
         # log-softmax epilogue and a planar store took 1.0 ms at config B).  D != Dp: the padding's -1e30 bias keeps it out of the sum
         y = ops.logsoftmax_rows(conv_w(x, "conv2_2", None, lrelu=False)).permute(0, 3, 1, 2)
-        return y if D == Dp else y[:, :D]
+        return y if Dl == Dpl else y[:, :Dl]
 
     def forward(self, dpv_raw, img_features):
         """Refine.py:79-107 as a module call (probabilities in, per-sample features): the autograd-capable composition of the

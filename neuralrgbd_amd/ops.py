@@ -281,35 +281,63 @@ def logsoftmax_d(a, b=None, scale=1.0):
     return out
 
 
-def depth_regress(logp, d_candi, want_conf=True):
-    """logp [D, ...] -> (expected depth [...], max log-prob [...])."""
-    logp = _need(logp, "logp")
-    D = logp.shape[0]
-    n = logp.numel() // D
+def is_channels_last_view(logp):
+    """A [D, ...] volume that is a VIEW of contiguous channels-last memory [..., D] (what the R-Net's last layer hands out):
+    the `channels_last=True` form of depth_regress / export_depth_u16 reads it where it lies."""
+    return logp.dim() >= 2 and not logp.is_contiguous() and logp.movedim(0, -1).is_contiguous()
+
+
+def _rows_volume(logp):
+    """logp [D, ...] as a view of channels-last memory -> (that memory [..., D], D, pixels)."""
+    logp = _need(logp, "logp", strided=True)
+    rows = logp.movedim(0, -1)
+    if not rows.is_contiguous():
+        raise ValueError("channels_last=True: logp %s with strides %s is not a view of contiguous [..., D] memory"
+                         % (tuple(logp.shape), tuple(logp.stride())))
+    return rows, logp.shape[0], logp.numel() // logp.shape[0]
+
+
+def depth_regress(logp, d_candi, want_conf=True, channels_last=False):
+    """logp [D, ...] -> (expected depth [...], max log-prob [...]).  channels_last: logp is a [D, ...] view of contiguous
+    channels-last memory [..., D] and is read as it lies (nrgbd_depth_regress_rows: the same bits, no transposing copy)."""
+    if channels_last:
+        rows, D, n = _rows_volume(logp)
+    else:
+        logp = _need(logp, "logp")
+        D = logp.shape[0]
+        n = logp.numel() // D
     d_candi = _need(d_candi, "d_candi", (D,))
     depth = torch.empty(logp.shape[1:], dtype=torch.float32, device=logp.device)
     conf = torch.empty_like(depth) if want_conf else None
     with torch.cuda.device(logp.device):
-        rc = _lib.load().nrgbd_depth_regress(_p(logp), _p(d_candi), _p(depth), _p(conf), D, n, _stream(logp))
-    _lib.check(rc, "nrgbd_depth_regress")
+        if channels_last:
+            rc = _lib.load().nrgbd_depth_regress_rows(_p(rows), _p(d_candi), _p(depth), _p(conf), D, n, _stream(logp))
+        else:
+            rc = _lib.load().nrgbd_depth_regress(_p(logp), _p(d_candi), _p(depth), _p(conf), D, n, _stream(logp))
+    _lib.check(rc, "nrgbd_depth_regress_rows" if channels_last else "nrgbd_depth_regress")
     return depth, conf
 
 
-def export_depth_u16(logp, d_candi, depth_scale=1000.0, conf_scale=1000.0):
-    """logp [D, ...] -> (depth f32, conf f32 = exp(max logp), depth_u16, conf_u16 [as int16 storage viewed uint16])."""
-    logp = _need(logp, "logp")
-    D = logp.shape[0]
-    n = logp.numel() // D
+def export_depth_u16(logp, d_candi, depth_scale=1000.0, conf_scale=1000.0, channels_last=False):
+    """logp [D, ...] -> (depth f32, conf f32 = exp(max logp), depth_u16, conf_u16 [as int16 storage viewed uint16]).
+    channels_last: as depth_regress (nrgbd_export_depth_u16_rows)."""
+    if channels_last:
+        rows, D, n = _rows_volume(logp)
+    else:
+        logp = _need(logp, "logp")
+        D = logp.shape[0]
+        n = logp.numel() // D
     d_candi = _need(d_candi, "d_candi", (D,))
     shp = logp.shape[1:]
     depth = torch.empty(shp, dtype=torch.float32, device=logp.device)
     conf = torch.empty_like(depth)
     du = torch.empty(shp, dtype=torch.uint16, device=logp.device)
     cu = torch.empty(shp, dtype=torch.uint16, device=logp.device)
+    entry = "nrgbd_export_depth_u16_rows" if channels_last else "nrgbd_export_depth_u16"
     with torch.cuda.device(logp.device):
-        rc = _lib.load().nrgbd_export_depth_u16(_p(logp), _p(d_candi), float(depth_scale), float(conf_scale), _p(depth),
-                                                 _p(conf), _p(du), _p(cu), D, n, _stream(logp))
-    _lib.check(rc, "nrgbd_export_depth_u16")
+        rc = getattr(_lib.load(), entry)(_p(rows if channels_last else logp), _p(d_candi), float(depth_scale), float(conf_scale),
+                                         _p(depth), _p(conf), _p(du), _p(cu), D, n, _stream(logp))
+    _lib.check(rc, entry)
     return depth, conf, du, cu
 
 
@@ -1138,7 +1166,7 @@ def bn_finalize_cm(stats, count, gamma, beta, eps, momentum, running_mean=None, 
 
 
 def logsoftmax_rows(x, inplace=True):
-    """log_softmax over the last (channel) axis of a contiguous channels-last tensor [..., C], C in {64, 128} (nrgbd_logsoftmax_rows)."""
+    """log_softmax over the last (channel) axis of a contiguous channels-last tensor [..., C], C in {64, 128, 256} (nrgbd_logsoftmax_rows)."""
     x = _need(x, "x")
     C = x.shape[-1]
     y = x if inplace else torch.empty_like(x)
@@ -1161,7 +1189,7 @@ def logsoftmax_d_bwd(logp, g, scale=1.0):
 
 
 def logsoftmax_rows_bwd(y, g):
-    """Backward of logsoftmax_rows on contiguous channels-last tensors [..., C], C in {64, 128} (nrgbd_logsoftmax_rows_bwd)."""
+    """Backward of logsoftmax_rows on contiguous channels-last tensors [..., C], C in {64, 128, 256} (nrgbd_logsoftmax_rows_bwd)."""
     y = _need(y, "y")
     g = _need(g, "g", y.shape)
     C = y.shape[-1]

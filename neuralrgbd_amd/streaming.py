@@ -229,7 +229,7 @@ class DepthStream:
     # ------------------------------------------------------------------ public step
     def step(self, ref_frame, src_frames, src_cam_poses, cam_pose_next=None):
         """ref_frame [1,3,H,W], src_frames [1,V,3,H,W], src_cam_poses [1,V,4,4] (device tensors).
-        Returns (refined DPV [1,D,H,W], DPV [1,D,h,w]); the predicted state for the next frame is kept inside.
+        Returns (refined DPV [1,D,H,W] — [1,4D,H,W] from a model with if_upsample_d —, DPV [1,D,h,w]); the predicted state for the next frame is kept inside.
         pipeline=True: the pair belongs to the PREVIOUS call's frame (None when there is none yet); flush() returns the last one.
         With the hipGraph active and copy_outputs=False the returned tensors are only valid until the next step()."""
         pose = src_cam_poses[0, self.t_win_r] if cam_pose_next is None else cam_pose_next

@@ -11,6 +11,7 @@ at the end is the same single launch as at inference.
 """
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -44,9 +45,25 @@ def _predict(kv, pose_next, cam, d_candi):
                                        padding_value=math.log(1. / float(len(d_candi))), clamp=(-1000., 0.)).unsqueeze(0)
 
 
-def _train_windows(A, dev, model_KV, t_win_r, d_candi, Ref_Dats, Src_Dats, poses_all, BVs_predict, Cam_Intrinsics):
+def _check_dup(model_KV, refine_dup):
+    """refine_dup (the image-size label has 4 D bins, train_KVNet.py:107-108) and a model built with if_upsample_d (the refined
+    volume has 4 D channels, Refine.py:44-49) go together: anything else fails here, before any launch."""
+    if bool(refine_dup) != bool(getattr(model_KV, "if_upsample_d", False)):
+        raise ValueError("refine_dup=%s with a model built with if_upsample_d=%s: the up-sampled label needs the up-sampling R-Net "
+                         "and the other way round" % (bool(refine_dup), bool(getattr(model_KV, "if_upsample_d", False))))
+
+
+def _dup4_candi(d_candi):
+    """The candidates the reference regresses the up-sampled high-resolution map with, train_KVNet.py:75: linspace from 0 — not from
+    d_min as the loaders' label (misc.d_candi_up4).  Mirrored as it is: the map is the reference's logging output."""
+    return np.linspace(0, np.asarray(d_candi).max(), 4 * len(d_candi))
+
+
+def _train_windows(A, dev, model_KV, t_win_r, d_candi, Ref_Dats, Src_Dats, poses_all, BVs_predict, Cam_Intrinsics, refine_dup=False):
     """Forward, losses and backward of the A windows of one optimizer step (train() below); gradients accumulate in .grad."""
     outs = []
+    label = 'dmap_up4_imgsize_digit' if refine_dup else 'dmap_imgsize_digit'           # train_KVNet.py:107-110
+    d_candi_hres = _dup4_candi(d_candi) if refine_dup else d_candi                     # train_KVNet.py:183-191
     for b in range(A):
         ref_frame = Ref_Dats[b]['img'].to(dev)
         src_frames = torch.cat(tuple(f['img'] for f in Src_Dats[b]), dim=0).unsqueeze(0).to(dev)
@@ -61,14 +78,14 @@ def _train_windows(A, dev, model_KV, t_win_r, d_candi, Ref_Dats, Src_Dats, poses
             ref_frame=ref_frame, src_frames=src_frames, src_cam_poses=poses, BatchIdx=torch.zeros(1),
             cam_intrinsics=[cam], BV_predict=bv if valid else None, dpv_valid=True if valid else None)
         depth_ref = Ref_Dats[b]['dmap'].to(dev)                        # [1,h,w] int64 bin indices, 0 = ignore
-        depth_ref_imgsize = Ref_Dats[b]['dmap_imgsize_digit'].to(dev)  # [1,H,W]
+        depth_ref_imgsize = Ref_Dats[b][label].to(dev)                 # [1,H,W]
         loss = _nll_terms(d_dpv, dmap_cur_refined, kv_dpv, dmap_refined, depth_ref, depth_ref_imgsize, valid)
         loss.backward()                # accumulates: the mean over the A windows is taken once, after the all-reduce
         with torch.no_grad():
             kv = kv_dpv.detach()
             outs.append((dmap_cur_refined.detach(), _predict(kv, poses[0, t_win_r], cam, d_candi), loss.detach(),
                          depth_val_regression(kv, d_candi, BV_log=True),
-                         depth_val_regression(dmap_refined.detach(), d_candi, BV_log=True)))
+                         depth_val_regression(dmap_refined.detach(), d_candi_hres, BV_log=True)))
     return outs
 
 
@@ -78,6 +95,9 @@ def train(nGPU, model_KV, optimizer_KV, t_win_r, d_candi, Ref_Dats, Src_Dats, Sr
     """Returns (r_dpv, BVs_predict_out, loss, dmap_kv_lowres, dmap_kv_highres) — the two depth maps are device
     tensors (the reference stacks them with the ground truth into numpy arrays for TensorBoard).
 
+    refine_dup: the model was built with if_upsample_d (else ValueError): the image-size label is `dmap_up4_imgsize_digit`, the
+    refined volumes are [1, 4 D, H, W] and the high-resolution map is regressed with linspace(0, d_max, 4 D) (train_KVNet.py:75).
+
     accum_steps = A > 1 (BASELINE config 4: global batch 32 = 8 GPUs x 4): the call takes A trajectories the way the
     reference's batch dimension does — Ref_Dats / Src_Dats lists of length A, Src_CamPoses [A,V,4,4], BVs_predict None, a
     tensor [A,D,h,w] or a list of A (tensor | None) — and runs them as A SEQUENTIAL N = 1 windows (KVNET asserts N = 1 per
@@ -86,8 +106,9 @@ def train(nGPU, model_KV, optimizer_KV, t_win_r, d_candi, Ref_Dats, Src_Dats, Sr
 
     deterministic: None follows neuralrgbd_amd.autograd.is_deterministic(); True / False set that switch around this call's forward
     and backward (True: the bit-reproducible cost-volume backward — two identical runs give identical weights)."""
-    if loss_type != 'NLL' or refine_dup:
-        raise NotImplementedError("only the NLL loss without depth up-sampling is on this path")
+    if loss_type != 'NLL':
+        raise NotImplementedError("only the NLL loss is on this path")
+    _check_dup(model_KV, refine_dup)
     A = int(accum_steps)
     if A < 1:
         raise ValueError("accum_steps must be >= 1")
@@ -103,7 +124,8 @@ def train(nGPU, model_KV, optimizer_KV, t_win_r, d_candi, Ref_Dats, Src_Dats, Sr
         optimizer_KV.zero_grad()
 
     with pack_cache(), _deterministic(deterministic):   # the A windows run on the same weights: their packed streams are built by the first one
-        outs = _train_windows(A, dev, model_KV, t_win_r, d_candi, Ref_Dats, Src_Dats, poses_all, BVs_predict, Cam_Intrinsics)
+        outs = _train_windows(A, dev, model_KV, t_win_r, d_candi, Ref_Dats, Src_Dats, poses_all, BVs_predict, Cam_Intrinsics,
+                              refine_dup)
 
     if grad_reducer is not None:
         grad_reducer()                 # RCCL all-reduce (sum / (A * world)) of the 21 MB fp32 gradient: buckets whose gradients
@@ -144,9 +166,12 @@ class TrainGraph:
     """
 
     def __init__(self, model, optimizer, t_win_r, d_candi, cam_intrinsics, warmup=1, grad_reducer=None, accum_steps=1,
-                 deterministic=None):
-        """deterministic: None follows neuralrgbd_amd.autograd.is_deterministic() at each eager iteration and at capture (a graph
+                 deterministic=None, refine_dup=False):
+        """refine_dup: the model refines with candidate up-sampling (KVNET(if_upsample_d=True)); step()'s `dmap_full` is then the
+        up-sampled label `dmap_up4_imgsize_digit` (bins in [0, 4 D)).  A flag that disagrees with the model raises ValueError.
+        deterministic: None follows neuralrgbd_amd.autograd.is_deterministic() at each eager iteration and at capture (a graph
         keeps the kernels it was captured with); True / False set the switch around this object's forward and backward."""
+        _check_dup(model, refine_dup)
         self.deterministic = deterministic
         self.model, self.opt, self.t_win_r, self.d_candi, self.cam = model, optimizer, t_win_r, d_candi, cam_intrinsics
         self._graph = None
