@@ -55,7 +55,9 @@ extern "C" {
  * entry changed.  0.10: nrgbd_warp_volume_cl (the K-Net input volume for temporal windows of 3, 5 and 7 frames, padded to whole
  * 16-channel blocks) is new, and nrgbd_conv3d_wgrad_f32 also takes Cin = 32; no existing entry changed.  0.10 also gained
  * nrgbd_depth_regress_rows and nrgbd_export_depth_u16_rows (the two reductions on a channels-last volume) and C = 256 in
- * nrgbd_logsoftmax_rows / _rows_bwd (the R-Net with candidate up-sampling); no existing entry changed, the version string stays. */
+ * nrgbd_logsoftmax_rows / _rows_bwd (the R-Net with candidate up-sampling); no existing entry changed, the version string stays.
+ * 0.10 further gained global-norm gradient clipping — nrgbd_grad_norm_workspace, nrgbd_grad_norm, nrgbd_scale_tensors and
+ * nrgbd_adam_step_clipped; no existing entry changed its signature or disappeared, so by the rule above the version string stays. */
 #define NRGBD_INTERFACE_VERSION "0.10"
 const char* nrgbd_version(void);
 const char* nrgbd_strerror(int code);
@@ -758,6 +760,38 @@ int nrgbd_nll_bwd(const long long* target, long ignore_index, const float* g_out
 int nrgbd_adam_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                     float* const* steps, const long* numel, int ntensors, double lr, double beta1, double beta2, double eps,
                     double weight_decay, int maximize, void* stream);
+/*
+ * nrgbd_grad_norm — the global L2 norm of a LIST of fp32 tensors and the clipping coefficient for it, on the tensor-list idiom of
+ * nrgbd_adam_step (48 pointers per launch by value; nothing is allocated or uploaded, no atomics, no host synchronisation: capturable
+ * into a hipGraph, and the same bits in every run, on every stream and at every grid size).  Replaces: the first half of
+ * torch.nn.utils.clip_grad_norm_(model_KVnet.parameters(), grad_clip_max) of train_utils/train_KVNet.py:143-145,180-181 (ATen:
+ * _foreach_norm over ~460 tensors, a stack and a norm).
+ *   grads: HOST array of `ntensors` DEVICE pointers; numel: host array of element counts (each in (0, 2^30]).
+ *   workspace: nrgbd_grad_norm_workspace(numel, ntensors) bytes on the device (a negative code for a bad list): one fp32 partial per
+ *   2,048-element chunk of every tensor, at the chunk's index in list order.
+ *   Summation order: in a chunk, thread t of 256 adds the squares of elements t, t + 256, ..., t + 1792 in that order, a wave64
+ *   xor-shuffle tree (offsets 32, 16, ..., 1) adds the 64 lanes, ((w0 + w1) + w2) + w3 adds the four waves — all fp32, 17 roundings on
+ *   the longest path.  One workgroup then adds all partials in double (thread t: partials t, t + 256, ... in order; the same tree).
+ *   clip [4] (device): clip[0] = total_norm = (float)sqrt(sum);  clip[1] = coef = (float)min(1.0, max_norm / ((double)total_norm + 1e-6))
+ *   (clip_grad_norm_'s clip_coef clamped to 1; a NaN stays a NaN);  clip[2] = 1.0f if total_norm is inf or NaN, else 0.0f;  clip[3] = 0.
+ *   nonfinite_steps (device float, may be NULL): += 1.0f when clip[2] is set — once per call.
+ *   max_norm = +inf gives coef = 1 (the norm alone); max_norm <= 0 or NaN: NRGBD_E_SHAPE.  A workspace that is too small:
+ *   NRGBD_E_SHAPE; a NULL pointer: NRGBD_E_NULL.  Every argument is checked before the first launch.
+ * nrgbd_scale_tensors — t[i] *= clip[1] in place over a tensor list (one rounded fp32 multiply per element = torch.mul): the second
+ * half of clip_grad_norm_ (ATen: _foreach_mul_), for an optimizer other than nrgbd_adam_step_clipped.
+ * nrgbd_adam_step_clipped — nrgbd_adam_step on g * clip[1] (the product is formed as the gradient is read: the same bits as
+ * nrgbd_scale_tensors followed by nrgbd_adam_step, and the gradients in memory stay as they are; maximize and weight_decay apply to
+ * the scaled gradient, as in torch).  skip_nonfinite = 1: when clip[2] is set the launch writes nothing — parameters, both moments and
+ * the step counters stay as they were.  skip_nonfinite = 0: the arithmetic goes through as in torch (coef is 0 or NaN: inf * 0 = NaN
+ * reaches the parameters).
+ */
+long nrgbd_grad_norm_workspace(const long* numel, int ntensors);
+int nrgbd_grad_norm(const float* const* grads, const long* numel, int ntensors, double max_norm, void* workspace,
+                    size_t workspace_bytes, float* clip, float* nonfinite_steps, void* stream);
+int nrgbd_scale_tensors(float* const* tensors, const long* numel, int ntensors, const float* clip, void* stream);
+int nrgbd_adam_step_clipped(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                            float* const* steps, const long* numel, int ntensors, double lr, double beta1, double beta2, double eps,
+                            double weight_decay, int maximize, const float* clip, int skip_nonfinite, void* stream);
 /*
  * nrgbd_bias_lrelu_cl_fwd / _bwd — y = leaky_relu(x + bias[c], slope) on channels-last rows [rows][C] and its backward
  * (training path of the R-Net).  Replaces: the bias add + nn.LeakyReLU of m_submodule.conv2d_leakyRelu /

@@ -103,6 +103,10 @@ SIGNATURES = {
     "nrgbd_nll_fwd": (_I, [_P, _P, _L, _I, _L, _I, _P, _P, _P]),
     "nrgbd_nll_bwd": (_I, [_P, _L, _P, _P, _P, _I, _L, _I, _P]),
     "nrgbd_adam_step": (_I, [_P, _P, _P, _P, _P, _P, _I, _D, _D, _D, _D, _D, _I, _P]),
+    "nrgbd_grad_norm_workspace": (_L, [_P, _I]),
+    "nrgbd_grad_norm": (_I, [_P, _P, _I, _D, _P, _Z, _P, _P, _P]),
+    "nrgbd_scale_tensors": (_I, [_P, _P, _I, _P, _P]),
+    "nrgbd_adam_step_clipped": (_I, [_P, _P, _P, _P, _P, _P, _I, _D, _D, _D, _D, _D, _I, _P, _I, _P]),
     "nrgbd_bias_lrelu_cl_workgroups": (_I, [_L, _I]),
     "nrgbd_bias_lrelu_cl_fwd": (_I, [_P, _P, _F, _P, _L, _I, _P]),
     "nrgbd_bias_lrelu_cl_bwd": (_I, [_P, _P, _F, _P, _P, _P, _L, _I, _P]),

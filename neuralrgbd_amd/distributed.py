@@ -77,6 +77,10 @@ class GradAllReduce:
     4 x len(bucket) gradients have landed, and `__call__` divides by 4 * world: the mean over all 32 windows.  With one rank
     the division by accum_steps still happens (no collective).
 
+    Gradient clipping (train(..., grad_clip_max=M) / optim.FusedAdam(max_grad_norm=M)) comes after `__call__()`: every rank takes the
+    norm of the same all-reduced, divided buffers with the same kernels in the same fixed summation order, so the coefficient and
+    the decision to skip a non-finite step are bit-identical on all ranks — there is no collective for them, and none is needed.
+
     `hold = True` keeps the hooks from launching anything (train_step.TrainGraph: forward + backward are captured into a
     hipGraph, whose replays run no hooks; every bucket is then launched from `__call__`, in index order as always).
     """

@@ -59,6 +59,32 @@ def _dup4_candi(d_candi):
     return np.linspace(0, np.asarray(d_candi).max(), 4 * len(d_candi))
 
 
+def _check_clip(optimizer, grad_clip_max, skip_nonfinite):
+    """The clipping keywords of train() / TrainGraph, checked before any launch."""
+    from .optim import FusedAdam, _check_max_norm
+    _check_max_norm(grad_clip_max)
+    if skip_nonfinite and not isinstance(optimizer, FusedAdam):
+        raise ValueError("skip_nonfinite=True needs neuralrgbd_amd.optim.FusedAdam: only its kernel can leave a step out "
+                         "(got %s)" % type(optimizer).__name__)
+
+
+def _optimizer_step(optimizer, grad_clip_max, skip_nonfinite):
+    """optimizer.step(), after global-norm clipping of the gradients at grad_clip_max (train_KVNet.py:143-145,180-181).  FusedAdam
+    folds the coefficient into its update; any other optimizer gets its gradients scaled in place by optim.clip_grad_norm_.
+    None / False leave a FusedAdam to its own max_grad_norm / skip_nonfinite attributes."""
+    from . import optim
+    if isinstance(optimizer, optim.FusedAdam):
+        kw = {}
+        if grad_clip_max is not None:
+            kw["max_grad_norm"] = grad_clip_max
+        if skip_nonfinite:
+            kw["skip_nonfinite"] = True
+        return optimizer.step(**kw)
+    if grad_clip_max is not None:
+        optim.clip_grad_norm_([p for group in optimizer.param_groups for p in group["params"]], grad_clip_max)
+    return optimizer.step()
+
+
 def _train_windows(A, dev, model_KV, t_win_r, d_candi, Ref_Dats, Src_Dats, poses_all, BVs_predict, Cam_Intrinsics, refine_dup=False):
     """Forward, losses and backward of the A windows of one optimizer step (train() below); gradients accumulate in .grad."""
     outs = []
@@ -91,7 +117,8 @@ def _train_windows(A, dev, model_KV, t_win_r, d_candi, Ref_Dats, Src_Dats, poses
 
 def train(nGPU, model_KV, optimizer_KV, t_win_r, d_candi, Ref_Dats, Src_Dats, Src_CamPoses, BVs_predict,
           Cam_Intrinsics, refine_dup=False, weight_var=.001, loss_type='NLL', mGPU=False,
-          Cam_Intrinsics_spatial_up=None, return_confmap_up=False, grad_reducer=None, accum_steps=1, deterministic=None):
+          Cam_Intrinsics_spatial_up=None, return_confmap_up=False, grad_reducer=None, accum_steps=1, deterministic=None,
+          grad_clip_max=None, skip_nonfinite=False):
     """Returns (r_dpv, BVs_predict_out, loss, dmap_kv_lowres, dmap_kv_highres) — the two depth maps are device
     tensors (the reference stacks them with the ground truth into numpy arrays for TensorBoard).
 
@@ -105,10 +132,18 @@ def train(nGPU, model_KV, optimizer_KV, t_win_r, d_candi, Ref_Dats, Src_Dats, Sr
     division by A x world, ONE optimizer step.  Outputs are concatenated along the batch dimension; `loss` is the mean.
 
     deterministic: None follows neuralrgbd_amd.autograd.is_deterministic(); True / False set that switch around this call's forward
-    and backward (True: the bit-reproducible cost-volume backward — two identical runs give identical weights)."""
+    and backward (True: the bit-reproducible cost-volume backward — two identical runs give identical weights).
+
+    grad_clip_max = M (the reference's `--grad_clip --grad_clip_max M`, train_KVNet.py:143-145,180-181): the global L2 norm of the
+    gradient is clipped to M once per optimizer step, AFTER the all-reduce and the division by accum_steps x world — the norm of the
+    averaged gradient, what single-process DataParallel plus clip_grad_norm_ computes.  With optim.FusedAdam the scale is folded
+    into the update (the .grad tensors stay unscaled; optimizer_KV.last_grad_norm / last_clip_coef hold the step's figures); any
+    other optimizer gets optim.clip_grad_norm_ in place.  skip_nonfinite=True (FusedAdam only, else ValueError): a step whose
+    gradient norm is inf / NaN changes no parameter, moment or step count."""
     if loss_type != 'NLL':
         raise NotImplementedError("only the NLL loss is on this path")
     _check_dup(model_KV, refine_dup)
+    _check_clip(optimizer_KV, grad_clip_max, skip_nonfinite)
     A = int(accum_steps)
     if A < 1:
         raise ValueError("accum_steps must be >= 1")
@@ -133,7 +168,7 @@ def train(nGPU, model_KV, optimizer_KV, t_win_r, d_candi, Ref_Dats, Src_Dats, Sr
     if A > 1 and not (grad_reducer is not None and hasattr(grad_reducer, "prepare")):
         # a plain callable reducer (sum / world) knows nothing about the accumulation: the mean over the A windows is taken here
         torch._foreach_div_([p.grad for p in model_KV.parameters() if p.grad is not None], float(A))
-    optimizer_KV.step()
+    _optimizer_step(optimizer_KV, grad_clip_max, skip_nonfinite)
     if A == 1:
         return outs[0]
     r_dpv, pred, loss, lo, hi = zip(*outs)
@@ -166,12 +201,16 @@ class TrainGraph:
     """
 
     def __init__(self, model, optimizer, t_win_r, d_candi, cam_intrinsics, warmup=1, grad_reducer=None, accum_steps=1,
-                 deterministic=None, refine_dup=False):
-        """refine_dup: the model refines with candidate up-sampling (KVNET(if_upsample_d=True)); step()'s `dmap_full` is then the
+                 deterministic=None, refine_dup=False, grad_clip_max=None, skip_nonfinite=False):
+        """grad_clip_max / skip_nonfinite: as in train() — the clipped optimizer step is what the eager iterations run and what the
+        graph (graph 2 of the split form: after the all-reduce and the division) captures.
+        refine_dup: the model refines with candidate up-sampling (KVNET(if_upsample_d=True)); step()'s `dmap_full` is then the
         up-sampled label `dmap_up4_imgsize_digit` (bins in [0, 4 D)).  A flag that disagrees with the model raises ValueError.
         deterministic: None follows neuralrgbd_amd.autograd.is_deterministic() at each eager iteration and at capture (a graph
         keeps the kernels it was captured with); True / False set the switch around this object's forward and backward."""
         _check_dup(model, refine_dup)
+        _check_clip(optimizer, grad_clip_max, skip_nonfinite)
+        self.grad_clip_max, self.skip_nonfinite = grad_clip_max, bool(skip_nonfinite)
         self.deterministic = deterministic
         self.model, self.opt, self.t_win_r, self.d_candi, self.cam = model, optimizer, t_win_r, d_candi, cam_intrinsics
         self._graph = None
@@ -218,8 +257,11 @@ class TrainGraph:
 
     def _iteration(self, st):
         out = self._fwd_bwd(st)
-        self.opt.step()
+        self._opt_step()
         return out
+
+    def _opt_step(self):
+        _optimizer_step(self.opt, self.grad_clip_max, self.skip_nonfinite)
 
     def _mark_updated(self):
         """A replay of the captured optimizer step runs no Python: the parameters' version counters (the keys of the inference
@@ -325,7 +367,7 @@ class TrainGraph:
             with pack_cache():
                 outs = [self._fwd_bwd(dict(zip(keys, w), inv=inv)) for w, inv in zip(windows, invs)]
             self._reduce_grads()
-            self.opt.step()
+            self._opt_step()
             self._eager_steps += 1
             return torch.stack([o[0] for o in outs]).mean(), [o[1] for o in outs]
         if self._graph is None:
@@ -347,7 +389,7 @@ class TrainGraph:
                     st["out_rest"] = self._fwd_bwd(st)
             g2 = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g2, pool=g.pool(), capture_error_mode=_capture_mode()):
-                self.opt.step()
+                self._opt_step()
             st["consts"] = warp_homo.cache_snapshot()
             st["packed"] = packed
             self._graph, self._g_rest, self._g_opt, self._st = g, g_rest, g2, st

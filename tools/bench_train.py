@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Training-step throughput (BASELINE config 4 shape: ScanNet 384x256 image, grid 96x64x64, N = 1 per GPU).
 
-    python tools/bench_train.py [--iters 6] [--graph] [--deterministic]
+    python tools/bench_train.py [--iters 6] [--graph] [--deterministic] [--grad-clip M]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/bench_train.py
 
 One iteration = neuralrgbd_amd.train_step.train(): forward under autograd, 4 NLL terms, backward (fused cost-volume
@@ -23,6 +23,8 @@ def main():
     ap.add_argument("--iters", type=int, default=6)
     ap.add_argument("--graph", action="store_true", help="replay the captured hipGraph of the iteration (1 GPU)")
     ap.add_argument("--deterministic", action="store_true", help="bit-reproducible mode (csrc/costvol_bwd_det.hip)")
+    ap.add_argument("--grad-clip", type=float, default=None, metavar="M",
+                    help="clip the global gradient norm at M before the step (the reference's --grad_clip --grad_clip_max M)")
     args = ap.parse_args()
     import neuralrgbd_amd
     from neuralrgbd_amd import autograd
@@ -47,7 +49,7 @@ def main():
     if args.graph:
         from neuralrgbd_amd.train_step import TrainGraph
         assert world == 1, "--graph is the single-GPU form"
-        tg = TrainGraph(model, opt, 2, d_candi, cam)
+        tg = TrainGraph(model, opt, 2, d_candi, cam, grad_clip_max=args.grad_clip)
     for it in range(args.iters + (4 if args.graph else 2)):
         r, s, p = synth.noise_window(100 * rank + it, H, W)
         ref = [{"img": r, "dmap": torch.from_numpy(rng.randint(0, D, (1, H // 4, W // 4))),
@@ -58,7 +60,7 @@ def main():
         if tg is not None and it >= 3:      # eager iterations first: filter state, vendor find-mode, optimizer state
             loss, pred = tg.step(r.to(dev), s.to(dev), p.to(dev), ref[0]["dmap"].to(dev), ref[0]["dmap_imgsize_digit"].to(dev), pred)
         else:
-            _, pred, loss, _, _ = train(world, model, opt, 2, d_candi, ref, src, p, pred, [cam], grad_reducer=reducer)
+            _, pred, loss, _, _ = train(world, model, opt, 2, d_candi, ref, src, p, pred, [cam], grad_reducer=reducer, grad_clip_max=args.grad_clip)
         torch.cuda.synchronize()
         times.append(time.perf_counter() - t0)
     steady = times[5:] if args.graph else times[2:]
