@@ -53,7 +53,7 @@ def build_dev(verbose=False):
     """Developer variant libnrgbd_hip_dev.so (-DNRGBD_DEV: ablation bits and tile-order switches honoured, read from the
     environment).  Used only by tools/ for kernel analysis; never loaded by the package."""
     lib = os.path.join(CSRC, "libnrgbd_hip_dev.so")
-    extra = os.environ.get("NRGBD_DEV_DEFINES", "").split()      # e.g. NRGBD_DEV_DEFINES="-DNRGBD_DW_NT=1" for a one-off experiment
+    extra = os.environ.get("NRGBD_DEV_DEFINES", "").split()      # further -D defines for a one-off experiment
     cmd = [HIPCC] + FLAGS + ["-DNRGBD_DEV"] + extra + ["-I", INCLUDE] + sources() + ["-o", lib]
     if verbose:
         print(" ".join(cmd))
@@ -61,8 +61,9 @@ def build_dev(verbose=False):
     return lib
 
 
-def build_variant(name, defines, only=("wino_dw.hip",), verbose=False):
-    """Experimental A/B library libnrgbd_exp_<name>.so: the product objects with `only` recompiled under extra -D defines.
+def build_variant(name, defines, only, verbose=False):
+    """Experimental A/B library libnrgbd_exp_<name>.so: the product objects with the sources named in `only` (base names, e.g.
+    ("costvol_quad.hip",)) recompiled under extra -D defines.
     Git-ignored; loaded by tools/ through _lib.LIB_PATH, never by the package."""
     build()
     lib = os.path.join(CSRC, "libnrgbd_exp_%s.so" % name)

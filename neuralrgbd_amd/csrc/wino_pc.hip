@@ -773,7 +773,7 @@ extern "C" int nrgbd_conv_wino_f32(const float* x, const float* x_ss, int x_relu
     const long nt = (long)rows * (half ? 1 : Cout / 64);
     if (nt >= (1L << 30)) return NRGBD_E_SHAPE;
     WinoPcArgs a{x, x_ss, res, res_ss, materialized, w_wino, y, stats, x_relu, res_relu, N, H, W, Cin, Cout, (int)nt, half ? 2 * rows : rows,
-                 nullptr, 0, 0, 0, 0, 0};
+                 nullptr, 0, 0, 0, 0};
     int nwg = 0;
     const int rc = pc_workgroups(nt, &nwg);
     if (rc != NRGBD_OK) return rc;
@@ -812,7 +812,7 @@ extern "C" int nrgbd_conv_wino_rnet_ex_f32(const float* x, const float* w_wino, 
     const long nt = (long)rows * (half ? 1 : Cout / 64);
     if (nt >= (1L << 30)) return NRGBD_E_SHAPE;
     WinoPcArgs a{x, nullptr, nullptr, nullptr, nullptr, w_wino, y, nullptr, 0, 0, N, H, W, Cin, Cout, (int)nt, half ? 2 * rows : rows,
-                 bias, out_lrelu, ldy, ycoff, cout_valid, 0};
+                 bias, out_lrelu, ldy, ycoff, cout_valid};
     int nwg = 0;
     const int rc = pc_workgroups(nt, &nwg);
     if (rc != NRGBD_OK) return rc;

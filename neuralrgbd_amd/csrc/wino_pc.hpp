@@ -41,8 +41,6 @@ struct WinoPcArgs {
     int out_lrelu;
     int ldy, ycoff, cout_valid;   // EPI = 1 only: pixel stride of y (0 = Cout), first output column, columns that exist (0 = Cout):
                                   // the R-Net writes into concat buffers and pads 67 / 96 outputs to the 64-column groups
-    int abl;              // developer ablation bits, honoured by wino_dw.hip in -DNRGBD_DEV builds only (its header lists the bits);
-                          // wino_pc.hip ignores it
     float x_unit;         // CLAMP instantiations only: 2^-k; (scale, shift) of x are multiplied by it and the ReLU is the [0, 1]
                           // clamp of the packed FMA; the weight stream carries the factor 2^k (see nrgbd_conv_wino_dw_unit_f32)
 };

@@ -288,6 +288,38 @@ def test_conv_wino_dw_fused_prologue_and_materialize():
     assert torch.equal(y2, y3)
 
 
+def test_conv_wino_dw_residual_and_materialize_across_tiles():
+    """The residual / materialise forms where a workgroup walks MORE than one tile: 280 tile pairs, one workgroup per CU.  The walk
+    uses the next tile's book for the last stage's refills (with a residual operand in flight), hands the materialise owner bits
+    over, and continues the weight ring into the next tile's stream.  y and the materialised input against F.conv3d of the activated
+    input, tolerances of test_conv_wino_dw_fused_prologue_and_materialize; every form twice, bit for bit."""
+    from neuralrgbd_amd import _lib, ops
+    D, H, W, C = 8, 40, 224, 64
+    tiles = (D // 2) * (H // 8) * (W // 16)
+    nwg = _lib.load().nrgbd_conv_wino_dw_workgroups(D, H, W, 64)
+    assert 0 < nwg < tiles == 280, (nwg, tiles)              # fails if the walk is no longer exercised
+    g = torch.Generator().manual_seed(17)
+    x = torch.randn(C, D, H, W, generator=g).to(DEV)
+    r = torch.randn(C, D, H, W, generator=g).to(DEV)
+    w = (torch.randn(64, C, 3, 3, 3, generator=g) * 0.05).to(DEV)
+    ss = torch.randn(C, 2, generator=g).to(DEV)
+    rs = torch.randn(C, 2, generator=g).to(DEV)
+    wp = ops.conv_wino_dw_pack(w)
+    ax = torch.relu(x * ss[:, 0, None, None, None] + ss[:, 1, None, None, None])
+    forms = [("res_ss+relu", dict(res=_cl(r), res_ss=rs, res_relu=True), ax + torch.relu(r * rs[:, 0, None, None, None] + rs[:, 1, None, None, None])),
+             ("identity res", dict(res=_cl(r)), ax + r),
+             ("materialise alone", dict(), ax)]
+    for name, kw, act in forms:
+        want = F.conv3d(act[None], w, padding=1)[0]
+        y, _, mat = ops.conv_wino_dw(_cl(x), wp, 64, x_ss=ss, x_relu=True, materialize=True, **kw)
+        ey, em = (y.permute(3, 0, 1, 2) - want).abs().max().item(), (mat.permute(3, 0, 1, 2) - act).abs().max().item()
+        print("[parity] conv_wino_dw %dx%dx%d %s + materialise: max|dy| %.3e max|dmat| %.3e" % (D, H, W, name, ey, em))
+        assert ey < 2e-4, name
+        assert em < 1e-5, name
+        y2, _, mat2 = ops.conv_wino_dw(_cl(x), wp, 64, x_ss=ss, x_relu=True, materialize=True, **kw)
+        assert torch.equal(y, y2) and torch.equal(mat, mat2), name
+
+
 def test_conv_wino_dw_pack_and_shape_contract():
     """Device packer == torch einsum reference (incl. the data-gradient form); unsupported shapes are refused, not substituted."""
     from neuralrgbd_amd import _lib, ops

@@ -26,12 +26,7 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--only", default="", help="substring filter on the variant names (e.g. 'wino-dw')")
     ap.add_argument("--cnn", action="store_true", help="also time the feature CNN's 2-D layer shapes")
-    ap.add_argument("--dev", action="store_true", help="load libnrgbd_hip_dev.so (python -m neuralrgbd_amd.build --dev): "
-                    "wino_dw.hip's NRGBD_WINO_ABL bits (see tools/abl_dw.py) are honoured there")
     args = ap.parse_args()
-    if args.dev:
-        from neuralrgbd_amd import _lib
-        _lib.LIB_PATH = os.environ.get("NRGBD_DEV_LIB") or _lib.LIB_PATH.replace("libnrgbd_hip.so", "libnrgbd_hip_dev.so")   # NRGBD_DEV_LIB: a one-off experimental build
     from neuralrgbd_amd import ops
     D, H, W = GRIDS[args.config]
     g = torch.Generator().manual_seed(0)

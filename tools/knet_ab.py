@@ -1,6 +1,5 @@
 """The whole K-Net stack (nets.KalmanGainNet.forward_channels_last) at a K-Net grid with the product library or an experimental
-A/B build of it (python -c "from neuralrgbd_amd import build; build.build_variant('serp0', ['-DNRGBD_DW_SERP=0'])"; NRGBD_EXP_LIB=
-its path): run both in one session to compare on the same chip.  HIP events, steady state."""
+A/B build of it (neuralrgbd_amd.build.build_variant; NRGBD_EXP_LIB= its path): run both in one session to compare on the same chip.  HIP events, steady state."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from neuralrgbd_amd import _lib

@@ -3,7 +3,8 @@
 parent / new comparison:  python tools/wino_time.py [--lib PATH] [--dw] [--only SUBSTRING] [--out FILE]
 wino_pc.hip: the feature CNN's trunk, dilated, 320 -> 128 and HALF layers at config B, the R-Net's 80 -> 64 and 128 -> 128 blocks
 at both of its resolutions, the K-Net's any-grid fallback (kd = 3) plain and with residual + materialise.
---dw: wino_dw.hip / wino_dw4.hip 64 -> 64 at the K-Net's grid instead.
+--dw: every launched form of wino_dw.hip (plain, IDENT, CLAMP, res, res + materialise, identity res + materialise, materialise) and of
+wino_dw4.hip (IDENT, plain, CLAMP), 64 -> 64 at the K-Net's grid, instead.
 Per shape: warm-up, then 5 windows of at least 0.25 s each; prints the median window's mean in us and the windows' range."""
 import math, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -58,17 +59,30 @@ def rnet(name, N, H, W, Cin, Cout):
     return name, direct("nrgbd_conv_wino_rnet_ex_f32", (x, wp, b, out), x, wp, b, 1, out, N, H, W, Cin, Cout, Cout, 0, Cout)
 
 
-def dw(name, four):
+def dw(name, four, **kw):             # kw: the form, as keyword arguments of ops.conv_wino_dw / ops.conv_wino_dw4
     x, w = r(64, 192, 256, 64), r(64, 64, 3, 3, 3) * 0.05
     ss = torch.stack((0.5 + torch.rand(64, device=DEV), 0.2 * r(64)), 1).contiguous()
+    if kw.pop("ss", False):
+        kw.update(x_ss=ss, x_relu=True)
+    if "x_unit" in kw:                  # the CLAMP forms: the weight stream carries 1 / x_unit
+        w = w / kw["x_unit"]
+    if kw.pop("res", False):
+        kw["res"] = r(64, 192, 256, 64)
+    if kw.pop("res_ss", False):         # else the residual operand comes as it is (the RSID instantiations)
+        kw.update(res_ss=torch.stack((0.5 + torch.rand(64, device=DEV), 0.2 * r(64)), 1).contiguous(), res_relu=True)
     if four:
         wp = ops.conv_wino_dw4_pack(w)
-        return name, lambda: ops.conv_wino_dw4(x, wp, 64, x_ss=ss, x_relu=True)
-    wp, res = ops.conv_wino_dw_pack(w), r(64, 192, 256, 64)
-    return name, lambda: ops.conv_wino_dw(x, wp, 64, x_ss=ss, x_relu=True, res=res, materialize=True)
+        return name, lambda: ops.conv_wino_dw4(x, wp, 64, **kw)
+    wp = ops.conv_wino_dw_pack(w)
+    return name, lambda: ops.conv_wino_dw(x, wp, 64, **kw)
 
 
-CASES = [("dw  64->64 @64x192x256 res+mat", lambda n: dw(n, False)), ("dw4 64->64 @64x192x256", lambda n: dw(n, True))] if "--dw" in sys.argv else [
+# every launched form of the two depth-Winograd kernels at 64 -> 64 @ 64x192x256
+DW = [("dw  plain", False, dict(ss=True)), ("dw  IDENT", False, {}), ("dw  CLAMP", False, dict(ss=True, x_unit=2.0 ** -6)),
+      ("dw  res", False, dict(ss=True, res=True, res_ss=True)), ("dw  res+mat", False, dict(ss=True, res=True, res_ss=True, materialize=True)),
+      ("dw  RSID res+mat", False, dict(ss=True, res=True, materialize=True)), ("dw  mat", False, dict(ss=True, materialize=True)),
+      ("dw4 IDENT", True, {}), ("dw4 plain", True, dict(ss=True)), ("dw4 CLAMP", True, dict(ss=True, x_unit=2.0 ** -6))]
+CASES = [(n + " 64->64 @64x192x256", lambda n, four=four, kw=kw: dw(n, four, **kw)) for n, four, kw in DW] if "--dw" in sys.argv else [
     ("trunk 64->64 @5x192x256", lambda n: pc(n, 5, 192, 256, 64, 64)), ("128->128 dil 2 @5x64x96", lambda n: pc(n, 5, 64, 96, 128, 128, dil=2)),
     ("320->128 @5x64x96", lambda n: pc(n, 5, 64, 96, 320, 128)), ("HALF 32->32 @5x384x512", lambda n: pc(n, 5, 384, 512, 32, 32)),
     ("R-Net 80->64 @2x768x1024", lambda n: rnet(n, 2, 768, 1024, 80, 64)), ("R-Net 128->128 @2x768x1024", lambda n: rnet(n, 2, 768, 1024, 128, 128)),
