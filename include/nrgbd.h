@@ -57,7 +57,8 @@ extern "C" {
  * nrgbd_depth_regress_rows and nrgbd_export_depth_u16_rows (the two reductions on a channels-last volume) and C = 256 in
  * nrgbd_logsoftmax_rows / _rows_bwd (the R-Net with candidate up-sampling); no existing entry changed, the version string stays.
  * 0.10 further gained global-norm gradient clipping — nrgbd_grad_norm_workspace, nrgbd_grad_norm, nrgbd_scale_tensors and
- * nrgbd_adam_step_clipped; no existing entry changed its signature or disappeared, so by the rule above the version string stays. */
+ * nrgbd_adam_step_clipped; no existing entry changed its signature or disappeared, so by the rule above the version string stays.
+ * The same holds for nrgbd_frame_ingest_u8 and nrgbd_window_gather (the video stream's frame ingest and window assembly). */
 #define NRGBD_INTERFACE_VERSION "0.10"
 const char* nrgbd_version(void);
 const char* nrgbd_strerror(int code);
@@ -814,6 +815,33 @@ int nrgbd_bias_lrelu_cl_bwd(const float* y, const float* gy, float slope, float*
  */
 int nrgbd_upsample_bilinear_ac(const float* x, float* y, int N, int bh, int bw, int H, int W, int C, int backward,
                                void* stream);
+/*
+ * nrgbd_frame_ingest_u8 — one uint8 camera frame -> the normalised fp32 planar image [3][Hout][Wout] of the network, written into a
+ * caller-given slot (a frame ring: neuralrgbd_amd/video.py).  Replaces: the loaders' image preparation — PIL.Image.NEAREST resize
+ * to the network size, ToTensor, Normalize (mdataloader/scanNet.py:368-369,429-430; utils/preprocess.py:14-35) — and the upload of its
+ * fp32 result (12 bytes per pixel against 3).
+ *   src     DEVICE uint8.  layout 0 = HWC interleaved: channel c of pixel (y, x) at src[y * pitch + 3 x + c], pitch >= 3 Win bytes
+ *           (padded camera rows are fine);  layout 1 = CHW planar: src[(c * Hin + y) * pitch + x], pitch >= Win.
+ *   dst     [3][Hout][Wout] fp32, 16-byte aligned; only these 3 Hout Wout elements are written (Wout need not be a multiple of 4).
+ *   value   ((float)u / 255.0f - mean_c) / std_c, two IEEE fp32 divisions in this order: ToTensor then Normalize, bit for bit.
+ *   resize  when (Hin, Win) != (Hout, Wout): nearest at pixel centres, in integers — sy = ((2 y + 1) Hin) / (2 Hout),
+ *           sx = ((2 x + 1) Win) / (2 Wout): PIL.Image.resize(..., NEAREST).
+ *   errors  NRGBD_E_NULL: src / dst;  NRGBD_E_SHAPE: a dimension <= 0 or > 16384, a pitch below the row;  NRGBD_E_ARG: layout not
+ *           0 / 1, a std that is 0 or not finite (or a mean that is not finite);  NRGBD_E_ALIGN: dst not 16-byte aligned.
+ * nrgbd_window_gather — the temporal window out of the frame ring in one launch: a plain copy, bit-equal to torch.stack of the slots.
+ * Replaces: split_frame_list + the list of source images of test_KVNet.py:195,213 (ATen: torch.cat / per-tensor copy_).
+ *   ring    [R] images of [3][H][W] fp32, image s at ring + s * slot_stride (slot_stride >= 3 H W elements)
+ *   slots   idx[0 .. V - 1] = the ring slots of the sources in window order, idx[V] = the slot of the reference; 1 <= V <= 6
+ *   src     [V][3][H][W], ref [3][H][W]: every element written.  16 bytes per lane when 3 H W and slot_stride are multiples of 4 and
+ *           the three pointers are 16-byte aligned, one element per lane otherwise.
+ *   errors  NRGBD_E_NULL;  NRGBD_E_SHAPE: V outside 1 .. 6, a slot outside [0, R), R / H / W <= 0 or H / W > 16384, a short slot_stride.
+ */
+#define NRGBD_GATHER_MAX_V   6
+typedef struct { int idx[NRGBD_GATHER_MAX_V + 1]; } nrgbd_window_slots;
+int nrgbd_frame_ingest_u8(const unsigned char* src, int Hin, int Win, long pitch, int layout, float mean0, float mean1, float mean2,
+                          float std0, float std1, float std2, float* dst, int Hout, int Wout, void* stream);
+int nrgbd_window_gather(const float* ring, int R, long slot_stride, nrgbd_window_slots slots, int V, float* src, float* ref,
+                        int H, int W, void* stream);
 int nrgbd_nhwc_stats_workgroups(long P);
 int nrgbd_nhwc_stats(const float* x, long P, int C, float* stats, void* stream);
 int nrgbd_nhwc_act(const float* x, const float* x_ss, int x_relu, const float* res, const float* res_ss,

@@ -5,6 +5,8 @@ Drop-in surface (reference file it replaces):
     neuralrgbd_amd.homography       code/warping/homography.py (the operators on the hot path)
     neuralrgbd_amd.test_step.test   code/test_utils/test_KVNet.py::test
     neuralrgbd_amd.lba_step         code/test_KVNet_LBA.py:306-528 (the LBA step: keyframe maps, pose refinement, stream)
+    neuralrgbd_amd.video            code/test_KVNet.py:185-250 (the driver loop: push a frame and its extrinsic, get depth) and the loaders'
+                                    image preparation (mdataloader/scanNet.py:368-369,429-430) on the device
     neuralrgbd_amd.camera           the cam_intrinsics dict of code/mdataloader/scanNet.py:204-272
 The compute between the convolutions is hand-written HIP behind the C-ABI of include/nrgbd.h
 (libnrgbd_hip.so, built by `python -m neuralrgbd_amd.build`).
@@ -25,10 +27,13 @@ from . import camera, synth  # host-only helpers (numpy / torch CPU)
 def __getattr__(name):
     # the GPU-facing modules load libnrgbd_hip.so; import them lazily so that host-only tooling
     # (camera, synth, build) works before the library is built
-    if name in ("ops", "homography", "kvnet", "nets", "misc", "test_step", "lba_step", "_lib"):
+    if name in ("ops", "homography", "kvnet", "nets", "misc", "test_step", "lba_step", "video", "_lib"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "KVNET":
         from .kvnet import KVNET
         return KVNET
+    if name == "VideoDepthStream":
+        from .video import VideoDepthStream
+        return VideoDepthStream
     raise AttributeError(name)

@@ -17,6 +17,14 @@ _L = _c.c_long
 _D = _c.c_double
 _Z = _c.c_size_t
 
+GATHER_MAX_V = 6        # NRGBD_GATHER_MAX_V
+
+
+class WindowSlots(ctypes.Structure):
+    """nrgbd_window_slots: the ring slots of a window, passed by value (sources in window order, then the reference)."""
+    _fields_ = [("idx", _I * (GATHER_MAX_V + 1))]
+
+
 # name -> (restype, argtypes); one entry per function of include/nrgbd.h
 SIGNATURES = {
     "nrgbd_version": (_c.c_char_p, []),
@@ -113,6 +121,8 @@ SIGNATURES = {
     "nrgbd_upsample_bilinear_ac": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "nrgbd_bn_small_stats": (_I, [_I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "nrgbd_spp_concat": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _I, _I, _I, _P]),
+    "nrgbd_frame_ingest_u8": (_I, [_P, _I, _I, _L, _I, _F, _F, _F, _F, _F, _F, _P, _I, _I, _P]),
+    "nrgbd_window_gather": (_I, [_P, _I, _L, WindowSlots, _I, _P, _P, _I, _I, _P]),
     "nrgbd_nhwc_stats_workgroups": (_I, [_L]),
     "nrgbd_nhwc_stats": (_I, [_P, _L, _I, _P, _P]),
     "nrgbd_nhwc_act": (_I, [_P, _P, _I, _P, _P, _I, _P, _L, _I, _I, _P]),

@@ -1399,3 +1399,80 @@ def bias_act_(x, bias, slope):
         rc = _lib.load().nrgbd_bias_act_nchw(_p(x), _p(bias), float(slope), N, C, H * W, _stream(x))
     _lib.check(rc, "nrgbd_bias_act_nchw")
     return x
+
+
+# ---- the video stream's frame ingest and window assembly (ingest.hip; neuralrgbd_amd/video.py) -------------------------------
+
+LAYOUT = {"hwc": 0, "chw": 1}        # layout flag of nrgbd_frame_ingest_u8
+
+
+def frame_ingest(frame, dst, mean, std, layout="hwc"):
+    """One uint8 CUDA frame ([Hin,Win,3] for layout "hwc", [3,Hin,Win] for "chw"; rows may be padded: any row stride) -> dst, a
+    contiguous 16-byte aligned fp32 [3,Hout,Wout] view (a slot of a frame ring), as ((u / 255 - mean_c) / std_c) with a nearest
+    resize when the sizes differ (nrgbd_frame_ingest_u8: ToTensor + Normalize + PIL NEAREST of the loaders, bit for bit).
+    Returns dst."""
+    if layout not in LAYOUT:
+        raise ValueError("frame_ingest: layout %r, expected 'hwc' or 'chw'" % (layout,))
+    if not isinstance(frame, torch.Tensor):
+        raise TypeError("frame must be a torch.Tensor")
+    if not frame.is_cuda:
+        raise _lib.NrgbdError("frame is on %s: the frame ingest runs on the GPU only (no CPU fallback)" % (frame.device,))
+    if frame.dtype != torch.uint8:
+        raise TypeError("frame must be uint8, got %s" % frame.dtype)
+    hwc = layout == "hwc"
+    if frame.dim() != 3 or frame.shape[2 if hwc else 0] != 3:
+        raise ValueError("frame_ingest: frame %s is not %s" % (tuple(frame.shape), "[H,W,3]" if hwc else "[3,H,W]"))
+    Hin, Win = (frame.shape[0], frame.shape[1]) if hwc else (frame.shape[1], frame.shape[2])
+    # rows of any pitch are read in place; anything else (a permuted or sliced view) is made contiguous first
+    if hwc:
+        ok = frame.stride(2) == 1 and frame.stride(1) == 3 and (frame.stride(0) >= 3 * Win or Hin == 1)
+        pitch = frame.stride(0) if Hin > 1 else 3 * Win
+    else:
+        ok = frame.stride(2) == 1 and (frame.stride(1) >= Win or Hin == 1) and frame.stride(0) == Hin * frame.stride(1)
+        pitch = frame.stride(1) if Hin > 1 else Win
+    if not ok:
+        frame = frame.contiguous()
+        pitch = 3 * Win if hwc else Win
+    dst = _need(dst, "dst", strided=True)
+    if dst.dim() != 3 or dst.shape[0] != 3 or not dst.is_contiguous() or dst.device != frame.device:
+        raise ValueError("frame_ingest: dst must be a contiguous [3,Hout,Wout] tensor on the frame's device, got %s" % (tuple(dst.shape),))
+    mean, std = [float(m) for m in mean], [float(s) for s in std]
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("frame_ingest: mean and std take three values each")
+    with torch.cuda.device(dst.device):
+        rc = _lib.load().nrgbd_frame_ingest_u8(_p(frame), int(Hin), int(Win), int(pitch), LAYOUT[layout], mean[0], mean[1], mean[2],
+                                               std[0], std[1], std[2], _p(dst), int(dst.shape[1]), int(dst.shape[2]), _stream(dst))
+    _lib.check(rc, "nrgbd_frame_ingest_u8")
+    return dst
+
+
+def window_gather(ring, slots, src=None, ref=None):
+    """ring [R,3,H,W] (images contiguous, any slot stride), slots = the V ring slots of the sources in window order followed by the
+    slot of the reference -> (src [V,3,H,W], ref [3,H,W]) in one launch (nrgbd_window_gather; bit-equal to torch.stack of the
+    slots).  src / ref: optional contiguous output buffers."""
+    ring = _need(ring, "ring", strided=True)
+    if ring.dim() != 4 or ring.shape[1] != 3 or not ring[0].is_contiguous():
+        raise ValueError("window_gather: ring %s must be [R,3,H,W] with contiguous images" % (tuple(ring.shape),))
+    R, _, H, W = ring.shape
+    slots = [int(s) for s in slots]
+    V = len(slots) - 1
+    if V < 1 or V > _lib.GATHER_MAX_V:
+        raise ValueError("window_gather: %d source slots, expected 1 .. %d" % (V, _lib.GATHER_MAX_V))
+    if min(slots) < 0 or max(slots) >= R:
+        raise ValueError("window_gather: slots %s outside the ring of %d" % (slots, R))
+    if src is None:
+        src = torch.empty((V, 3, H, W), dtype=torch.float32, device=ring.device)
+    if ref is None:
+        ref = torch.empty((3, H, W), dtype=torch.float32, device=ring.device)
+    src, ref = _need(src, "src", strided=True), _need(ref, "ref", strided=True)
+    if src.numel() != V * 3 * H * W or ref.numel() != 3 * H * W or not src.is_contiguous() or not ref.is_contiguous():
+        raise ValueError("window_gather: src %s / ref %s must be contiguous buffers of %s / %s"
+                         % (tuple(src.shape), tuple(ref.shape), (V, 3, H, W), (3, H, W)))
+    st = _lib.WindowSlots()
+    for i, s in enumerate(slots):
+        st.idx[i] = s
+    with torch.cuda.device(ring.device):
+        rc = _lib.load().nrgbd_window_gather(_p(ring), int(R), int(ring.stride(0)) if R > 1 else 3 * H * W, st, V, _p(src), _p(ref),
+                                             int(H), int(W), _stream(ring))
+    _lib.check(rc, "nrgbd_window_gather")
+    return src, ref
