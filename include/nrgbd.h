@@ -444,7 +444,10 @@ int nrgbd_conv3d_3x3x3_cout1_f32(const float* x, const float* x_ss, int x_relu,
  *   gy [D][H][W] (gradient of the layer's output), x / gx [D][H][W][64] channels-last, w_tap_major [27][64] as for the forward,
  *   dw [64][27] = torch's [1][64][3][3][3] (overwritten); workspace: nrgbd_conv3d_cout1_wgrad_workspace() bytes, 16-byte aligned.
  *   gx[v][ci] = sum_tap gy[v - off(tap)] w[ci][tap];  dw[ci][tap] = sum_v gy[v - off(tap)] x[v][ci];  fixed summation orders.
+ * nrgbd_conv3d_cout1_bwd_workgroups: the grid of the weight-gradient (dgrad = 0) or data-gradient (dgrad != 0) launch, host only: one
+ * workgroup per 8 x 16 tile of a slice up to 512 / 2,048, beyond that the workgroups walk the tile list; < 0: a shape error.
  */
+int nrgbd_conv3d_cout1_bwd_workgroups(int D, int H, int W, int dgrad);
 int nrgbd_conv3d_cout1_dgrad_f32(const float* gy, const float* w_tap_major, float* gx, int D, int H, int W, void* stream);
 int nrgbd_conv3d_cout1_wgrad_workspace(int D, int H, int W, size_t* bytes);
 int nrgbd_conv3d_cout1_wgrad_f32(const float* x, const float* gy, float* dw, void* workspace, size_t workspace_bytes, int D, int H, int W,
@@ -457,8 +460,11 @@ int nrgbd_conv3d_cout1_wgrad_f32(const float* x, const float* gy, float* dw, voi
  *   partial: scratch of nrgbd_conv3d_wgrad_workgroups() * 27 * 64 * Cin floats.
  * The data gradient needs no new kernel: it is nrgbd_conv3d_3x3x3_f32 applied to gy with the weights
  * transposed (cin <-> cout) and flipped in all three tap axes.
+ * nrgbd_conv3d_wgrad_ranges: the tile ranges of the launch (host only) — the grid is (ranges, quadrants) whatever the volume, and a
+ * range walks its share of the 2 x 4 x 16-voxel tiles.
  */
 int nrgbd_conv3d_wgrad_workgroups(void);
+int nrgbd_conv3d_wgrad_ranges(void);
 int nrgbd_conv3d_wgrad_f32(const float* x, const float* gy, float* partial, float* dw,
                            int D, int H, int W, int Cin, void* stream);
 int nrgbd_bn3d_finalize(const float* stats, int num_workgroups, long count,

@@ -68,6 +68,7 @@ SIGNATURES = {
     "nrgbd_conv3d_pack_weights": (_I, [_P, _P, _I, _P]),
     "nrgbd_conv3d_3x3x3_f32": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "nrgbd_conv3d_3x3x3_cout1_f32": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P]),
+    "nrgbd_conv3d_cout1_bwd_workgroups": (_I, [_I, _I, _I, _I]),
     "nrgbd_conv3d_cout1_dgrad_f32": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "nrgbd_conv3d_cout1_wgrad_workspace": (_I, [_I, _I, _I, _P]),
     "nrgbd_conv3d_cout1_wgrad_f32": (_I, [_P, _P, _P, _P, _Z, _I, _I, _I, _P]),
@@ -85,6 +86,7 @@ SIGNATURES = {
     "nrgbd_conv_wino_dw4_workspace": (_I, [_I, _I, _I, _I, _P]),
     "nrgbd_conv_wino_dw4_f32": (_I, [_P, _P, _I, _F, _P, _P, _P, _P, _c.c_size_t, _I, _I, _I, _I, _I, _P]),
     "nrgbd_conv3d_wgrad_workgroups": (_I, []),
+    "nrgbd_conv3d_wgrad_ranges": (_I, []),
     "nrgbd_conv3d_wgrad_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "nrgbd_bn3d_finalize": (_I, [_P, _I, _L, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P]),
     "nrgbd_bn2d_partial_floats": (_I, [_I]),

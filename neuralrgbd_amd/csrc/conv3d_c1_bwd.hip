@@ -11,7 +11,7 @@
 //
 // Both walk 8 x 16-voxel tiles of one depth slice: the 3 x 10 x 18 halo of gy (one channel) sits in LDS, a thread = (voxel column of 16,
 // 4 consecutive channels) reads its 27 neighbours as LDS broadcasts and touches x / gx once, as whole 16-byte words of a channels-last voxel.
-// Summation orders are fixed (taps ascending; tiles in list order; workgroup partials in index order): bitwise reproducible.
+// Summation orders are fixed (taps ascending; tiles in list order; workgroup partials in index order); no atomics: bitwise reproducible.
 #include "common.hpp"
 
 namespace nrgbd {
@@ -148,21 +148,24 @@ __global__ __launch_bounds__(256) void conv3d_cout1_wgrad_reduce_kernel(const fl
     }
 }
 
-static int c1_bwd_workgroups(int D, int H, int W) {
-    const long nt = (long)D * ceil_div(H, kB1TH) * ceil_div(W, kB1TW);
-    return (int)(nt < 512 ? nt : 512);
-}
-
 }  // namespace nrgbd
+
+// workgroups of the two launches: one per 8 x 16 tile up to the cap (512 weight gradient — its partials are 6.9 KB each — / 2,048 data
+// gradient), beyond it the workgroups walk the tile list.  The ONE source of the number: both launchers and the workspace query call it.
+extern "C" int nrgbd_conv3d_cout1_bwd_workgroups(int D, int H, int W, int dgrad) {
+    using namespace nrgbd;
+    if (D <= 0 || H <= 0 || W <= 0 || (long)D * H * W >= (1L << 31)) return NRGBD_E_SHAPE;
+    const long nt = (long)D * ceil_div(H, kB1TH) * ceil_div(W, kB1TW), cap = dgrad ? 2048 : 512;
+    return (int)(nt < cap ? nt : cap);
+}
 
 extern "C" int nrgbd_conv3d_cout1_dgrad_f32(const float* gy, const float* w_tap_major, float* gx, int D, int H, int W, void* stream) {
     using namespace nrgbd;
     if (!gy || !w_tap_major || !gx) return NRGBD_E_NULL;
     if (D <= 0 || H <= 0 || W <= 0 || (long)D * H * W >= (1L << 31)) return NRGBD_E_SHAPE;
     if ((reinterpret_cast<uintptr_t>(gx) | reinterpret_cast<uintptr_t>(w_tap_major)) & 15) return NRGBD_E_ALIGN;
-    const long nt = (long)D * ceil_div(H, kB1TH) * ceil_div(W, kB1TW);
-    hipLaunchKernelGGL(conv3d_cout1_dgrad_kernel, dim3((unsigned)(nt < 2048 ? nt : 2048)), dim3(256), 0, (hipStream_t)stream, gy, w_tap_major,
-                       gx, D, H, W);
+    const int nwg = nrgbd_conv3d_cout1_bwd_workgroups(D, H, W, 1);
+    hipLaunchKernelGGL(conv3d_cout1_dgrad_kernel, dim3(nwg), dim3(256), 0, (hipStream_t)stream, gy, w_tap_major, gx, D, H, W);
     NRGBD_CHECK_LAUNCH();
     return NRGBD_OK;
 }
@@ -171,7 +174,7 @@ extern "C" int nrgbd_conv3d_cout1_wgrad_workspace(int D, int H, int W, size_t* b
     using namespace nrgbd;
     if (!bytes) return NRGBD_E_NULL;
     if (D <= 0 || H <= 0 || W <= 0 || (long)D * H * W >= (1L << 31)) return NRGBD_E_SHAPE;
-    *bytes = (size_t)c1_bwd_workgroups(D, H, W) * 27 * 64 * sizeof(float);
+    *bytes = (size_t)nrgbd_conv3d_cout1_bwd_workgroups(D, H, W, 0) * 27 * 64 * sizeof(float);
     return NRGBD_OK;
 }
 
@@ -181,7 +184,7 @@ extern "C" int nrgbd_conv3d_cout1_wgrad_f32(const float* x, const float* gy, flo
     if (!x || !gy || !dw || !workspace) return NRGBD_E_NULL;
     if (D <= 0 || H <= 0 || W <= 0 || (long)D * H * W >= (1L << 31)) return NRGBD_E_SHAPE;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(workspace)) & 15) return NRGBD_E_ALIGN;
-    const int nwg = c1_bwd_workgroups(D, H, W);
+    const int nwg = nrgbd_conv3d_cout1_bwd_workgroups(D, H, W, 0);
     if (workspace_bytes < (size_t)nwg * 27 * 64 * sizeof(float)) return NRGBD_E_NULL;
     float* partial = static_cast<float*>(workspace);
     hipLaunchKernelGGL(conv3d_cout1_wgrad_kernel, dim3(nwg), dim3(256), 0, (hipStream_t)stream, x, gy, partial, D, H, W);

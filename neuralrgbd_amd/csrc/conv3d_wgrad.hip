@@ -270,6 +270,9 @@ extern "C" int nrgbd_conv3d_wgrad_workgroups(void) {
     return (nrgbd::kWRanges * nrgbd::kWPts * 64 + 27 * 64 - 1) / (27 * 64);
 }
 
+// tile ranges = workgroups per (co, ci) quadrant of the launch, whatever the grid; a range walks ceil or floor of tiles / ranges tiles
+extern "C" int nrgbd_conv3d_wgrad_ranges(void) { return nrgbd::kWRanges; }
+
 extern "C" int nrgbd_conv3d_wgrad_f32(const float* x, const float* gy, float* partial, float* dw, int D, int H,
                                       int W, int Cin, void* stream) {
     using namespace nrgbd;

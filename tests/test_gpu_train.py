@@ -121,7 +121,10 @@ def test_one_training_iteration_updates_weights_and_predicts():
 def test_conv3d_backward_kernels_vs_torch_autograd(D, H, W, Cin):
     """Data gradient (forward kernel on flipped/transposed weights) and weight gradient (conv3d_wgrad.hip); the grids cover every
     kernel the 64 -> 64 layers can take (wino_dw4.hip: D % 4 == 0 and whole tiles; wino_dw.hip: even D; wino_pc.hip / conv3d.hip)
-    and the first layer's 16-channel forms."""
+    and the first layer's 16-channel forms.  The weight gradient is held against the vendor library's fp32 result AND against the float64
+    reference tests/wgrad_ref.py::wgrad3d at the bound of tests/test_gpu_wgrad_walk.py: e <= R_WINO * e_plain (e_plain: the reference
+    evaluated in fp32 on the device)."""
+    import wgrad_ref
     from neuralrgbd_amd.autograd import Conv3dCL
     g = torch.Generator().manual_seed(D + W)
     x = torch.randn(Cin, D, H, W, generator=g).to(DEV)
@@ -137,6 +140,14 @@ def test_conv3d_backward_kernels_vs_torch_autograd(D, H, W, Cin):
           (D, H, W, Cin, ex, x1.grad.abs().max().item(), ew, w1.grad.abs().max().item()))
     assert ex < 5e-5 * max(1.0, x1.grad.abs().max().item())
     assert ew < 1e-4 * max(1.0, w1.grad.abs().max().item())
+    x_cl, gy_cl = x2.detach(), gy.permute(1, 2, 3, 0).contiguous()
+    want64 = wgrad_ref.wgrad3d(x_cl.cpu(), gy_cl.cpu())
+    scale = want64.abs().max()
+    e = float((w2.grad.double().cpu() - want64).abs().max() / scale)
+    e_plain = float((wgrad_ref.wgrad3d(x_cl, gy_cl, torch.float32).double().cpu() - want64).abs().max() / scale)
+    print("[parity] conv3d_wgrad %dx%dx%d Cin=%d vs float64: e %.3e  e_plain %.3e  ratio %.4f (R %g)" %
+          (D, H, W, Cin, e, e_plain, e / e_plain, wgrad_ref.R_WINO))
+    assert e_plain > 0 and e <= wgrad_ref.R_WINO * e_plain
 
 
 @pytest.mark.parametrize("D,H,W", [(4, 8, 16), (5, 11, 21), (8, 24, 48)])

@@ -484,3 +484,37 @@ def test_conv3d_kernel_choice_table():
     assert ops.conv3d_kernel(64, 192, 256, 64, 64, ("direct", "dw4")) == "direct"
     assert ops.conv3d_kernel(64, 192, 256, 64, 64, ()) == "direct"
 
+
+def test_walking_grids_of_the_gradient_kernels_walk():
+    """The grids of tests/test_gpu_wgrad_walk.py (tests/wgrad_ref.py holds the tables) give every persistent gradient kernel fewer
+    workgroups than tiles, so a workgroup's tile loop takes more than one trip there: tile counts and workgroup counts as literals
+    against the launchers' own host-side queries.  A change of a cap or a tile size that ends the walk fails here, without a GPU."""
+    import wgrad_ref as ref
+    from neuralrgbd_amd import _lib
+    lib = _lib.load()
+    assert lib.nrgbd_conv3d_wgrad_ranges() == 128
+    assert lib.nrgbd_conv3d_wgrad_workgroups() * 27 * 64 >= 128 * 48 * 64      # the scratch unit covers 48 points per range
+    assert [r[4] for r in ref.WALK_3D] == [325, 512, 325, 153]
+    for D, H, W, Cin, tiles in ref.WALK_3D:
+        assert ref.tiles_3d(D, H, W) == tiles and lib.nrgbd_conv3d_wgrad_ranges() < tiles, (D, H, W)
+        assert ref.exact_3d(D, H, W)
+    assert tuple(r[4] % 128 != 0 for r in ref.WALK_3D) == (True, False, True, True)     # ranges of unequal length in three launches
+    assert [(r[6], r[7]) for r in ref.WALK_2D] == [(1024, 1050), (182, 198), (455, 480), (303, 322), (455, 480)]
+    for N, H, W, Cin, Cout, dil, nwg, tiles in ref.WALK_2D:
+        assert ref.tiles_2d(N, H, W) == tiles and ref.exact_sum(N * H * W)
+        assert lib.nrgbd_conv2d_wgrad_workgroups(N, H, W, Cin, Cout) == nwg < tiles, (N, H, W, Cin, Cout)
+    D, H, W, nwg, tiles = ref.WALK_C1_WGRAD
+    assert (nwg, tiles) == (512, 600) and ref.tiles_2d(D, H, W) == tiles and ref.exact_sum(D * H * W)
+    assert lib.nrgbd_conv3d_cout1_bwd_workgroups(D, H, W, 0) == nwg < tiles
+    D, H, W, nwg, tiles = ref.WALK_C1_DGRAD
+    assert (nwg, tiles) == (2048, 2340) and ref.tiles_2d(D, H, W) == tiles
+    assert lib.nrgbd_conv3d_cout1_bwd_workgroups(D, H, W, 1) == nwg < tiles
+    # below the caps: one workgroup per tile; the weight-gradient workspace is sized by the same number; shape errors are reported
+    import ctypes
+    assert lib.nrgbd_conv3d_cout1_bwd_workgroups(8, 24, 48, 0) == 72 == lib.nrgbd_conv3d_cout1_bwd_workgroups(8, 24, 48, 1)
+    assert lib.nrgbd_conv3d_cout1_bwd_workgroups(130, 20, 88, 0) == 512
+    n = ctypes.c_size_t(0)
+    for shape in ((8, 24, 48), (20, 36, 88), (130, 20, 88)):
+        assert lib.nrgbd_conv3d_cout1_wgrad_workspace(*shape, ctypes.byref(n)) == 0
+        assert n.value == lib.nrgbd_conv3d_cout1_bwd_workgroups(*shape, 0) * 27 * 64 * 4
+    assert lib.nrgbd_conv3d_cout1_bwd_workgroups(0, 8, 16, 0) < 0 and lib.nrgbd_conv3d_cout1_bwd_workgroups(2048, 1024, 1024, 1) < 0
