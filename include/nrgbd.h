@@ -58,7 +58,8 @@ extern "C" {
  * nrgbd_logsoftmax_rows / _rows_bwd (the R-Net with candidate up-sampling); no existing entry changed, the version string stays.
  * 0.10 further gained global-norm gradient clipping — nrgbd_grad_norm_workspace, nrgbd_grad_norm, nrgbd_scale_tensors and
  * nrgbd_adam_step_clipped; no existing entry changed its signature or disappeared, so by the rule above the version string stays.
- * The same holds for nrgbd_frame_ingest_u8 and nrgbd_window_gather (the video stream's frame ingest and window assembly). */
+ * The same holds for nrgbd_frame_ingest_u8 and nrgbd_window_gather (the video stream's frame ingest and window assembly), and for
+ * nrgbd_depth_ingest_u16 (the training stream's depth-label ingest). */
 #define NRGBD_INTERFACE_VERSION "0.10"
 const char* nrgbd_version(void);
 const char* nrgbd_strerror(int code);
@@ -848,6 +849,37 @@ int nrgbd_frame_ingest_u8(const unsigned char* src, int Hin, int Win, long pitch
                           float std0, float std1, float std2, float* dst, int Hout, int Wout, void* stream);
 int nrgbd_window_gather(const float* ring, int R, long slot_stride, nrgbd_window_slots slots, int V, float* src, float* ref,
                         int H, int W, void* stream);
+/*
+ * nrgbd_depth_ingest_u16 — one uint16 ground-truth depth frame -> the labels and the metric maps of a training step, one launch.
+ * Replaces: the loaders' depth preparation (mdataloader/scanNet.py:372-422: PIL NEAREST resizes of the frame and of its hole mask,
+ * `.float() * .001`, the digitising of mdataloader/misc.py:13-36 = np.digitize against float64 candidates, the clamp to
+ * [0, n - 1]) and the upload of its int64 results.  Every output is the loaders' result bit for bit.
+ *   depth        device, [Hin] rows of Win uint16 (raw units, ScanNet: millimetres), row r at depth + r * pitch (elements);
+ *                0 = a hole (`raw < 0.01`, scanNet.py:373)
+ *   rows_full [H], cols_full [W]   device int32: source row / column of every row / column of the image-size maps (scanNet.py:378)
+ *   rows_q [h], cols_q [w]         the same for the direct resize to the plane-sweep grid (scanNet.py:388)
+ *   mask_rows_q [h], mask_cols_q [w]   source row / column of the grid-size hole mask: the image-size table composed with the
+ *                image -> grid table, because the reference resizes the mask twice (scanNet.py:374-375,389)
+ *                The tables are the caller's because PIL's NEAREST accumulates a double per output index — idx = (int)xo, xo += s from
+ *                xo = 0.5 s, s = (double)n_in / n_out — and no integer formula gives that for every pair of sizes.  An entry outside
+ *                the frame is clamped to it (never read out of bounds).
+ *   depth_scale  metres per raw unit (.001), finite and > 0; metres = (float)u * depth_scale, one fp32 product
+ *   thr_q [n_q], thr_full [n_full]   HOST int32, read before the call returns: non-decreasing thresholds in [0, 65536] with
+ *                label(u) = min(#{k : thr[k] <= u}, n - 1), thr[k] = the smallest u whose metres, as a double, are >= d_candi[k]
+ *                (65536: none) — np.digitize followed by the loaders' clamp, in integers.  1 <= n <= NRGBD_DEPTH_MAX_THRESHOLDS.
+ *                n_full is D, or 4 D for `dmap_up4_imgsize_digit` (scanNet.py:419-421).
+ *   labels_q [h][w] int64 (`dmap`), labels_full [H][W] int64 (`dmap_imgsize_digit` / `dmap_up4_imgsize_digit`),
+ *   dmap_raw [h][w] fp32, dmap_imgsize [H][W] fp32 (masked metres): each may be NULL (not computed), not all four.
+ *                16 bytes per lane and store where a map's width is a multiple of 4 and its base 16-byte aligned, element stores
+ *                otherwise.  A grid pixel under a hole of the twice-resized mask is 0.0 / label(0).
+ *   errors       NRGBD_E_ARG: a NULL input or table, all four outputs NULL, a size <= 0 or > 16384, pitch < Win, n outside
+ *                1 .. 512, thresholds that decrease or leave [0, 65536], a depth_scale that is not finite and positive.
+ */
+#define NRGBD_DEPTH_MAX_THRESHOLDS 512
+int nrgbd_depth_ingest_u16(const unsigned short* depth, int Hin, int Win, long pitch, const int* rows_full, const int* cols_full,
+                           const int* rows_q, const int* cols_q, const int* mask_rows_q, const int* mask_cols_q, float depth_scale,
+                           const int* thr_q, int n_q, const int* thr_full, int n_full, long long* labels_q, long long* labels_full,
+                           float* dmap_raw, float* dmap_imgsize, int H, int W, int h, int w, void* stream);
 int nrgbd_nhwc_stats_workgroups(long P);
 int nrgbd_nhwc_stats(const float* x, long P, int C, float* stats, void* stream);
 int nrgbd_nhwc_act(const float* x, const float* x_ss, int x_relu, const float* res, const float* res_ss,

@@ -7,6 +7,9 @@ Drop-in surface (reference file it replaces):
     neuralrgbd_amd.lba_step         code/test_KVNet_LBA.py:306-528 (the LBA step: keyframe maps, pose refinement, stream)
     neuralrgbd_amd.video            code/test_KVNet.py:185-250 (the driver loop: push a frame and its extrinsic, get depth) and the loaders'
                                     image preparation (mdataloader/scanNet.py:368-369,429-430) on the device
+    neuralrgbd_amd.train_video      code/train_KVNet.py:283-330 over mdataloader/batch_loader.py (the training driver loop: push a frame, its
+                                    depth frame and its extrinsic, get a training step) and the loaders' depth preparation and
+                                    digitising (mdataloader/scanNet.py:372-422) on the device
     neuralrgbd_amd.camera           the cam_intrinsics dict of code/mdataloader/scanNet.py:204-272
 The compute between the convolutions is hand-written HIP behind the C-ABI of include/nrgbd.h
 (libnrgbd_hip.so, built by `python -m neuralrgbd_amd.build`).
@@ -27,7 +30,7 @@ from . import camera, synth  # host-only helpers (numpy / torch CPU)
 def __getattr__(name):
     # the GPU-facing modules load libnrgbd_hip.so; import them lazily so that host-only tooling
     # (camera, synth, build) works before the library is built
-    if name in ("ops", "homography", "kvnet", "nets", "misc", "test_step", "lba_step", "video", "_lib"):
+    if name in ("ops", "homography", "kvnet", "nets", "misc", "test_step", "lba_step", "video", "train_video", "_lib"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "KVNET":
@@ -36,4 +39,7 @@ def __getattr__(name):
     if name == "VideoDepthStream":
         from .video import VideoDepthStream
         return VideoDepthStream
+    if name in ("TrainVideoStream", "DepthLabeler", "run_training_sequence", "pillow_nearest_index", "label_thresholds"):
+        from . import train_video
+        return getattr(train_video, name)
     raise AttributeError(name)

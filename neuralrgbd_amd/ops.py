@@ -6,6 +6,7 @@ path: a CPU tensor raises.
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1476,3 +1477,60 @@ def window_gather(ring, slots, src=None, ref=None):
                                              int(H), int(W), _stream(ring))
     _lib.check(rc, "nrgbd_window_gather")
     return src, ref
+
+
+# ---- the training stream's depth-label ingest (depth_ingest.hip; neuralrgbd_amd/train_video.py) ------------------------------
+
+def _i32_table(t, name, n, dev):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != dev or t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+        raise ValueError("depth_ingest: %s must be a contiguous int32 tensor of %d entries on %s" % (name, n, dev))
+    return t
+
+
+def depth_ingest(depth, tables, depth_scale, thr_q, thr_full, labels_q=None, labels_full=None, dmap_raw=None, dmap_imgsize=None):
+    """One uint16 CUDA depth frame [Hin,Win] (torch.uint16, or the same bits as int16; rows may be padded: any row stride) -> the
+    given outputs, in one launch (nrgbd_depth_ingest_u16: the loaders' depth preparation, mdataloader/scanNet.py:372-422, bit for bit).
+    tables: the six int32 device tables (rows_full [H], cols_full [W], rows_q [h], cols_q [w], mask_rows_q [h], mask_cols_q [w]);
+    thr_q / thr_full: host int32 thresholds (train_video.label_thresholds).  labels_q [h,w] / labels_full [H,W] int64 and dmap_raw [h,w]
+    / dmap_imgsize [H,W] fp32: contiguous CUDA tensors (a leading 1 is accepted) or None = not computed; at least one is given.
+    Returns (labels_q, labels_full, dmap_raw, dmap_imgsize)."""
+    if not isinstance(depth, torch.Tensor):
+        raise TypeError("depth must be a torch.Tensor")
+    if not depth.is_cuda:
+        raise _lib.NrgbdError("depth is on %s: the depth ingest runs on the GPU only (no CPU fallback)" % (depth.device,))
+    if depth.dtype not in (torch.uint16, torch.int16):
+        raise TypeError("depth must be uint16 (or its bits as int16), got %s" % depth.dtype)
+    if depth.dim() != 2:
+        raise ValueError("depth_ingest: depth %s is not [Hin,Win]" % (tuple(depth.shape),))
+    Hin, Win = depth.shape
+    if depth.stride(1) != 1 or (Hin > 1 and depth.stride(0) < Win):
+        depth = depth.contiguous()
+    pitch = depth.stride(0) if Hin > 1 else Win
+    dev = depth.device
+    if len(tables) != 6:
+        raise ValueError("depth_ingest: six index tables, got %d" % len(tables))
+    H, W, h, w = (int(tables[i].numel()) if isinstance(tables[i], torch.Tensor) else -1 for i in (0, 1, 2, 3))
+    names = ("rows_full", "cols_full", "rows_q", "cols_q", "mask_rows_q", "mask_cols_q")
+    tables = [_i32_table(t, nm, n, dev) for t, nm, n in zip(tables, names, (H, W, h, w, h, w))]
+    outs = []
+    for t, nm, dt, shape in ((labels_q, "labels_q", torch.int64, (h, w)), (labels_full, "labels_full", torch.int64, (H, W)),
+                             (dmap_raw, "dmap_raw", torch.float32, (h, w)), (dmap_imgsize, "dmap_imgsize", torch.float32, (H, W))):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != dev or not t.is_contiguous()
+                              or tuple(t.shape) not in (shape, (1,) + shape)):
+            raise ValueError("depth_ingest: %s must be a contiguous %s tensor %s on %s" % (nm, dt, shape, dev))
+        outs.append(t)
+    if all(t is None for t in outs):
+        raise ValueError("depth_ingest: no output given")
+    thr = []
+    for t, nm in ((thr_q, "thr_q"), (thr_full, "thr_full")):
+        a = np.ascontiguousarray(t, dtype=np.int32)
+        if a.ndim != 1 or not 1 <= a.size <= _lib.DEPTH_MAX_THRESHOLDS:
+            raise ValueError("depth_ingest: %s holds %s thresholds, expected 1 .. %d" % (nm, a.shape, _lib.DEPTH_MAX_THRESHOLDS))
+        thr.append(a)
+    with torch.cuda.device(dev):
+        rc = _lib.load().nrgbd_depth_ingest_u16(
+            _p(depth), int(Hin), int(Win), int(pitch), *(_p(t) for t in tables), float(depth_scale),
+            ctypes.c_void_p(thr[0].ctypes.data), int(thr[0].size), ctypes.c_void_p(thr[1].ctypes.data), int(thr[1].size),
+            *(_p(t) for t in outs), H, W, h, w, _stream(depth))
+    _lib.check(rc, "nrgbd_depth_ingest_u16")
+    return tuple(outs)
