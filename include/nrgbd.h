@@ -59,7 +59,8 @@ extern "C" {
  * 0.10 further gained global-norm gradient clipping — nrgbd_grad_norm_workspace, nrgbd_grad_norm, nrgbd_scale_tensors and
  * nrgbd_adam_step_clipped; no existing entry changed its signature or disappeared, so by the rule above the version string stays.
  * The same holds for nrgbd_frame_ingest_u8 and nrgbd_window_gather (the video stream's frame ingest and window assembly), and for
- * nrgbd_depth_ingest_u16 (the training stream's depth-label ingest). */
+ * nrgbd_depth_ingest_u16 (the training stream's depth-label ingest).  0.10 also gained the on-device depth evaluation —
+ * nrgbd_depth_eval_workgroups, nrgbd_depth_eval_workspace and nrgbd_depth_eval; no existing entry changed, the version string stays. */
 #define NRGBD_INTERFACE_VERSION "0.10"
 const char* nrgbd_version(void);
 const char* nrgbd_strerror(int code);
@@ -884,6 +885,43 @@ int nrgbd_nhwc_stats_workgroups(long P);
 int nrgbd_nhwc_stats(const float* x, long P, int C, float* stats, void* stream);
 int nrgbd_nhwc_act(const float* x, const float* x_ss, int x_relu, const float* res, const float* res_ss,
                    int res_relu, float* y, long P, int C, int ldy, void* stream);
+/*
+ * On-device depth evaluation (depth_eval.hip; neuralrgbd_amd/evaluate.py): the error metrics of a depth map against ground truth
+ * as sums and counts that stay on the device, per confidence set.  Replaces: the host evaluation of test_utils/export_res.py:108-116
+ * (the maps downloaded, `dmap_ref > 0` as the mask, `np.abs(dmap_ref - dmap) * mask` in numpy) and the offline scoring behind it.
+ *
+ * nrgbd_depth_eval_workgroups — export_res.py:108-116: the partial records the first launch of nrgbd_depth_eval writes for n
+ *   pixels (a function of n alone, non-decreasing in n); NRGBD_E_SHAPE for n <= 0 or n > 2^40.
+ * nrgbd_depth_eval_workspace — export_res.py:108-116: the bytes nrgbd_depth_eval needs for n pixels and J confidence sets
+ *   (non-decreasing in both); NRGBD_E_SHAPE for a bad n or J outside 1 .. NRGBD_DEPTH_EVAL_MAX_SETS.
+ * nrgbd_depth_eval — export_res.py:108-116: one map against its ground truth, two launches, no synchronisation, no atomics; the same
+ *   inputs give the same bits in every run.
+ *   depth, logconf, gt   device fp32 [n]: the expected depth and max_k logp as nrgbd_depth_regress / _rows write them, and the ground
+ *                truth in metres, 0 = a hole.  With d, m, g the three values of a pixel:
+ *                  gt-valid  g > 0 && g >= gt_min && g <= gt_max (a NaN g is not valid)
+ *                  bad       gt-valid and not (d > 0, d finite, m not NaN): counted in the header, enters no metric
+ *                  set j     the pixels with m >= log_thr[j], fp32 against fp32
+ *   log_thr      HOST fp32 [J], read and checked at the call: strictly ascending, log_thr[0] = -inf (set 0 holds every pixel)
+ *   terms        in double from the promoted fp32 values, in this operation sequence: e = d - g; a = fabs(e); t0 = a; t1 = a / g;
+ *                t2 = (e * e) / g; t3 = e * e; q = d / g; l = log(q); t4 = l * l; t5 = l; r = max(q, g / d); the delta counts are
+ *                r < 1.25, r < 1.5625, r < 1.953125
+ *   frame_sums   float64 [J][6] = the sums of t0 .. t5 over set j;  frame_counts int64 [J][4] = n, delta1, delta2, delta3 of set j;
+ *   frame_header int64 [4] = 1, gt-valid pixels, bad pixels, 0: this call's record, every element written
+ *   total_*      the same three records, total = total + frame (the caller zeroes them); all three given or all three NULL
+ *   err_map      fp32 [n] or NULL: fabsf(g - d) where g > 0, else 0.f — export_res.py:113-116 on fp32 maps, independent of the
+ *                range and of the confidence
+ *   workspace    8-byte aligned, at least nrgbd_depth_eval_workspace(n, J) bytes; rewritten by every call
+ *   errors       NRGBD_E_NULL: a NULL required pointer, or only some of total_*;  NRGBD_E_SHAPE: a bad n or J, a workspace that is
+ *                too small;  NRGBD_E_ARG: log_thr[0] != -inf, a NaN threshold, thresholds not ascending, gt_min <= gt_max not true
+ *                (a NaN bound included);  NRGBD_E_ALIGN: the workspace.  Every argument is checked before the first launch.
+ */
+#define NRGBD_DEPTH_EVAL_MAX_SETS 8
+int nrgbd_depth_eval_workgroups(long n);
+long nrgbd_depth_eval_workspace(long n, int J);
+int nrgbd_depth_eval(const float* depth, const float* logconf, const float* gt, long n, float gt_min, float gt_max,
+                     const float* log_thr, int J, void* workspace, long workspace_bytes, double* frame_sums,
+                     long long* frame_counts, long long* frame_header, double* total_sums, long long* total_counts,
+                     long long* total_header, float* err_map, void* stream);
 
 #ifdef __cplusplus
 }

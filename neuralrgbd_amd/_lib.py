@@ -19,6 +19,7 @@ _Z = _c.c_size_t
 
 GATHER_MAX_V = 6        # NRGBD_GATHER_MAX_V
 DEPTH_MAX_THRESHOLDS = 512      # NRGBD_DEPTH_MAX_THRESHOLDS
+DEPTH_EVAL_MAX_SETS = 8         # NRGBD_DEPTH_EVAL_MAX_SETS
 
 
 class WindowSlots(ctypes.Structure):
@@ -127,6 +128,9 @@ SIGNATURES = {
     "nrgbd_frame_ingest_u8": (_I, [_P, _I, _I, _L, _I, _F, _F, _F, _F, _F, _F, _P, _I, _I, _P]),
     "nrgbd_window_gather": (_I, [_P, _I, _L, WindowSlots, _I, _P, _P, _I, _I, _P]),
     "nrgbd_depth_ingest_u16": (_I, [_P, _I, _I, _L, _P, _P, _P, _P, _P, _P, _F, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "nrgbd_depth_eval_workgroups": (_I, [_L]),
+    "nrgbd_depth_eval_workspace": (_L, [_L, _I]),
+    "nrgbd_depth_eval": (_I, [_P, _P, _P, _L, _F, _F, _P, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P]),
     "nrgbd_nhwc_stats_workgroups": (_I, [_L]),
     "nrgbd_nhwc_stats": (_I, [_P, _L, _I, _P, _P]),
     "nrgbd_nhwc_act": (_I, [_P, _P, _I, _P, _P, _I, _P, _L, _I, _I, _P]),

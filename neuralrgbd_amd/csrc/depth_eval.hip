@@ -1,0 +1,297 @@
+// depth_eval.hip — error metrics of a depth map against ground truth, running totals resident on the device
+// (neuralrgbd_amd/evaluate.py: DepthMetrics, EvalVideoStream).
+//
+// Replaces the host work of test_utils/export_res.py:108-116 — the maps pulled to the host, `dmap_ref > 0` as the mask,
+// `np.abs(dmap_ref - dmap) * mask` — and the offline evaluation that follows it: two launches per evaluated map, no host
+// synchronisation, one device-to-host copy when the caller asks for the numbers.
+//
+// depth_eval_kernel           depth [n], logconf [n] (= max_k logp, as nrgbd_depth_regress* writes it), gt [n] (fp32 metres, 0 = a hole)
+//                             -> one partial record per workgroup, and optionally err_map [n].  Per pixel (d, m, g the three fp32 values):
+//                               gt-valid  g > 0 && g >= gt_min && g <= gt_max          (a NaN g is not valid)
+//                               bad       gt-valid and not (d > 0, d finite, m not NaN): counted, enters no metric
+//                               err_map   fabsf(g - d) where g > 0, else 0.f           (fp32; independent of range and confidence)
+//                               bin       b = #{j : m >= log_thr[j]} - 1               (fp32 against fp32: exact; log_thr[0] = -inf)
+//                               terms, in double from the promoted values, in this operation sequence (a float64 host comparator
+//                               reproduces every term bit for bit; the library is built with -ffp-contract=off):
+//                                 e = d - g; a = fabs(e); t0 = a; t1 = a / g; t2 = (e * e) / g; t3 = e * e;
+//                                 q = d / g; l = log(q); t4 = l * l; t5 = l; r = max(q, g / d);
+//                                 delta counts r < 1.25, r < 1.5625, r < 1.953125
+//                             A lane keeps J x 6 doubles and J x 4 counts in registers, indexed statically: every bin gets a
+//                             predicated add (x + 0.0 is exact), never a dynamically indexed register — that would go to scratch.
+//                             The workgroup reduces in a fixed order (wave64 shuffles — for eight bins a folded tree that halves the
+//                             values a lane carries at every step, wave_fold_sum —, then the 4 wave sums through LDS in wave order)
+//                             and writes its record with plain vector stores.  The pixels of a lane depend on n alone
+//                             (the grid is a function of n), so the same inputs give the same bits in every run.  No atomics.
+// depth_eval_finalize_kernel  one workgroup: adds the partial records in a fixed order (double / int64), turns the bins into the
+//                             cumulative confidence sets (set j = bins J-1, J-2, ..., j added in that order), writes the frame
+//                             record and adds it into the running totals (total = total + frame).
+// Records: sums float64 [J][6] = sum t0 .. t5; counts int64 [J][4] = n, delta1, delta2, delta3;
+//          header int64 [4] = frames evaluated, gt-valid pixels, bad pixels, 0.
+// Workspace: value v of workgroup b at word v * nwg + b (8-byte words; the finaliser's reads coalesce): v < 6J the sums of bin
+// v / 6, then 4J counts, then gt-valid and bad.
+// Bound: 12 bytes read and 4 written per pixel — 12.6 MB at 768 x 1024 is under 2 us of HBM time, and the kernel takes 12.5 us
+// (J = 1) / 18.5 us (J = 8) there: the double-precision work (four IEEE divisions and a log per pixel, J x 6 predicated adds) and the
+// reduction behind it set the duration, neither the bandwidth nor the launch.
+#include "common.hpp"
+
+namespace nrgbd {
+
+constexpr int kEvalMaxSets = NRGBD_DEPTH_EVAL_MAX_SETS;       // 8
+constexpr int kEvalPixelsPerWg = 1024;                        // 4 pixels per lane up to 512 x 1024 pixels, more beyond (768 x 1024: 6)
+constexpr int kEvalMaxWg = 512;                               // two per CU; the finaliser holds kEvalMaxWg / 64 records of a value per lane
+constexpr long kEvalMaxN = 1L << 40;                          // a lane's int32 counts hold 2^40 / (512 * 256) pixels with room
+
+struct EvalThr {
+    float t[kEvalMaxSets];              // ascending, t[0] = -inf; entries from J on are NaN (no m compares >= NaN)
+};
+
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// Wave sums of N = 16 m values per lane with m + N / 2 + N / 4 + ... shuffles instead of 6 N: at each of four steps (lane bits 5, 4, 3, 2)
+// a lane keeps one half of its values and hands the other half to its partner, which keeps that one — statically indexed selects, no
+// dynamic register index —, then the m values left are added over the last two lane bits.  Afterwards a[0 .. m) of every lane hold the
+// wave's sums of the values fold_index(lane, i); the order of the additions is fixed.
+template <typename T, int N, int H>
+__device__ __forceinline__ void fold_step(T (&a)[N], bool upper, int offset) {
+#pragma unroll
+    for (int i = 0; i < H; ++i) {
+        const T send = upper ? a[i] : a[i + H];
+        const T keep = upper ? a[i + H] : a[i];
+        a[i] = keep + __shfl_xor(send, offset, 64);
+    }
+}
+template <typename T, int N>
+__device__ __forceinline__ void wave_fold_sum(T (&a)[N], int lane) {
+    static_assert(N % 16 == 0, "four halving steps");
+    fold_step<T, N, N / 2>(a, (lane & 32) != 0, 32);
+    fold_step<T, N, N / 4>(a, (lane & 16) != 0, 16);
+    fold_step<T, N, N / 8>(a, (lane & 8) != 0, 8);
+    fold_step<T, N, N / 16>(a, (lane & 4) != 0, 4);
+#pragma unroll
+    for (int i = 0; i < N / 16; ++i) {
+        a[i] += __shfl_xor(a[i], 2, 64);
+        a[i] += __shfl_xor(a[i], 1, 64);
+    }
+}
+template <int N>
+__device__ __forceinline__ int fold_index(int lane, int i) {
+    return i + ((lane & 32) ? N / 2 : 0) + ((lane & 16) ? N / 4 : 0) + ((lane & 8) ? N / 8 : 0) + ((lane & 4) ? N / 16 : 0);
+}
+
+// JN: the bins a lane keeps (1 or 8); J <= JN the bins that are written
+template <int JN>
+__global__ __launch_bounds__(256) void depth_eval_kernel(const float* __restrict__ depth, const float* __restrict__ logconf,
+                                                         const float* __restrict__ gt, long n, float gt_min, float gt_max,
+                                                         const EvalThr thr, int J, double* __restrict__ ws_sums,
+                                                         long long* __restrict__ ws_counts, float* __restrict__ err_map) {
+    constexpr int NV = JN * 10 + 2;
+    __shared__ double w_sum[4][JN * 6];
+    __shared__ int w_cnt[4][JN * 4 + 2];
+    double acc[JN * 6];                 // [bin][term]
+    int cnt[JN * 4];                    // [bin][n, delta1, delta2, delta3]
+#pragma unroll
+    for (int i = 0; i < JN * 6; ++i) acc[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < JN * 4; ++i) cnt[i] = 0;
+    int n_valid = 0, n_bad = 0;
+    const long stride = (long)gridDim.x * 256;
+    for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < n; p += stride) {
+        const float d = depth[p], m = logconf[p], g = gt[p];
+        if (err_map) err_map[p] = g > 0.f ? fabsf(g - d) : 0.f;
+        const bool valid = g > 0.f && g >= gt_min && g <= gt_max;
+        const bool ok = valid && d > 0.f && d <= 3.402823466e+38f && m == m;
+        n_valid += valid ? 1 : 0;
+        n_bad += (valid && !ok) ? 1 : 0;
+        int b = -1;
+#pragma unroll
+        for (int j = 0; j < JN; ++j) b += (m >= thr.t[j]) ? 1 : 0;
+        const double dd = (double)d, gd = (double)g;
+        const double e = dd - gd;
+        const double a = fabs(e);
+        const double ee = e * e;
+        const double q = dd / gd;
+        const double l = log(q);
+        const double r = fmax(q, gd / dd);
+        const double t[6] = {a, a / gd, ee / gd, ee, l * l, l};
+        const int c1 = r < 1.25 ? 1 : 0, c2 = r < 1.5625 ? 1 : 0, c3 = r < 1.953125 ? 1 : 0;
+#pragma unroll
+        for (int j = 0; j < JN; ++j) {
+            const bool in = ok && b == j;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) acc[j * 6 + k] += in ? t[k] : 0.0;
+            cnt[j * 4 + 0] += in ? 1 : 0;
+            cnt[j * 4 + 1] += in ? c1 : 0;
+            cnt[j * 4 + 2] += in ? c2 : 0;
+            cnt[j * 4 + 3] += in ? c3 : 0;
+        }
+    }
+    // the workgroup's record: the wave's sums (one shuffle tree per value for a single bin, the folded tree for eight), then the 4 wave
+    // sums through LDS in wave order
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if constexpr (JN == 1) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            const double s = wave_sum(acc[k]);
+            if (lane == 0) w_sum[wave][k] = s;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int s = wave_sum(cnt[k]);
+            if (lane == 0) w_cnt[wave][k] = s;
+        }
+    } else {
+        wave_fold_sum<double, JN * 6>(acc, lane);
+        wave_fold_sum<int, JN * 4>(cnt, lane);
+        if ((lane & 3) == 0) {
+#pragma unroll
+            for (int i = 0; i < JN * 6 / 16; ++i) w_sum[wave][fold_index<JN * 6>(lane, i)] = acc[i];
+#pragma unroll
+            for (int i = 0; i < JN * 4 / 16; ++i) w_cnt[wave][fold_index<JN * 4>(lane, i)] = cnt[i];
+        }
+    }
+    n_valid = wave_sum(n_valid);
+    n_bad = wave_sum(n_bad);
+    if (lane == 0) {
+        w_cnt[wave][JN * 4] = n_valid;
+        w_cnt[wave][JN * 4 + 1] = n_bad;
+    }
+    __syncthreads();
+    const int v = threadIdx.x;
+    const size_t nwg = gridDim.x;
+    if (v < JN * 6) {
+        if (v < J * 6) ws_sums[(size_t)v * nwg + blockIdx.x] = ((w_sum[0][v] + w_sum[1][v]) + w_sum[2][v]) + w_sum[3][v];
+    } else if (v < NV) {
+        const int c = v - JN * 6;                              // bins' counts, then gt-valid, bad
+        const long long s = (((long long)w_cnt[0][c] + w_cnt[1][c]) + w_cnt[2][c]) + w_cnt[3][c];
+        if (c < J * 4)
+            ws_counts[(size_t)c * nwg + blockIdx.x] = s;
+        else if (c >= JN * 4)
+            ws_counts[(size_t)(J * 4 + (c - JN * 4)) * nwg + blockIdx.x] = s;
+    }
+}
+
+constexpr int kFinBatch = 8, kFinLoads = kEvalMaxWg / 64;
+
+// out[v] = the sum over the nwg records of value v, v < nvalues (ws: value v of record b at v * nwg + b)
+template <typename T>
+__device__ __forceinline__ void eval_reduce_values(const T* __restrict__ ws, int nwg, int nvalues, T* out, int wave, int lane) {
+    for (int v0 = wave * kFinBatch; v0 < nvalues; v0 += 4 * kFinBatch) {
+        T x[kFinBatch][kFinLoads];
+#pragma unroll
+        for (int b = 0; b < kFinBatch; ++b) {
+#pragma unroll
+            for (int k = 0; k < kFinLoads; ++k) {
+                const int i = lane + 64 * k;
+                x[b][k] = (v0 + b < nvalues && i < nwg) ? ws[(size_t)(v0 + b) * nwg + i] : T(0);      // + 0 is exact
+            }
+        }
+        T s[kFinBatch];
+#pragma unroll
+        for (int b = 0; b < kFinBatch; ++b) {
+            s[b] = x[b][0];
+#pragma unroll
+            for (int k = 1; k < kFinLoads; ++k) s[b] += x[b][k];
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {                  // the batch's shuffle trees side by side: their latencies overlap
+#pragma unroll
+            for (int b = 0; b < kFinBatch; ++b) s[b] += __shfl_xor(s[b], o, 64);
+        }
+#pragma unroll
+        for (int b = 0; b < kFinBatch; ++b)
+            if (lane == 0 && v0 + b < nvalues) out[v0 + b] = s[b];
+    }
+}
+
+__global__ __launch_bounds__(256) void depth_eval_finalize_kernel(const double* __restrict__ ws_sums, const long long* __restrict__ ws_counts,
+                                                                  int nwg, int J, double* __restrict__ frame_sums,
+                                                                  long long* __restrict__ frame_counts, long long* __restrict__ frame_header,
+                                                                  double* __restrict__ total_sums, long long* __restrict__ total_counts,
+                                                                  long long* __restrict__ total_header) {
+    __shared__ double bin_sum[kEvalMaxSets * 6];
+    __shared__ long long bin_cnt[kEvalMaxSets * 4 + 2];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // 1. the partial records: a wave takes kFinBatch values at a time; lane i holds records i, i + 64, ... of each (all loads in flight
+    //    together), adds them in index order, then the shuffle tree
+    eval_reduce_values(ws_sums, nwg, J * 6, bin_sum, wave, lane);
+    eval_reduce_values(ws_counts, nwg, J * 4 + 2, bin_cnt, wave, lane);
+    __syncthreads();
+    // 2. - 4. cumulative sets (bins J-1 down to j, added in that order), the frame record, total = total + frame
+    const int t = threadIdx.x;
+    if (t < J * 6) {
+        const int j = t / 6, k = t - j * 6;
+        double s = bin_sum[(J - 1) * 6 + k];
+        for (int b = J - 2; b >= j; --b) s += bin_sum[b * 6 + k];
+        frame_sums[t] = s;
+        if (total_sums) total_sums[t] = total_sums[t] + s;
+    } else if (t >= 64 && t < 64 + J * 4) {
+        const int c = t - 64, j = c >> 2, k = c & 3;
+        long long s = bin_cnt[(J - 1) * 4 + k];
+        for (int b = J - 2; b >= j; --b) s += bin_cnt[b * 4 + k];
+        frame_counts[c] = s;
+        if (total_counts) total_counts[c] = total_counts[c] + s;
+    } else if (t >= 128 && t < 132) {
+        const int c = t - 128;
+        const long long s = c == 0 ? 1 : (c == 3 ? 0 : bin_cnt[J * 4 + c - 1]);
+        frame_header[c] = s;
+        if (total_header) total_header[c] = total_header[c] + s;
+    }
+}
+
+static int eval_workgroups(long n) {
+    if (n <= 0 || n > kEvalMaxN) return NRGBD_E_SHAPE;
+    const long w = (n + kEvalPixelsPerWg - 1) / kEvalPixelsPerWg;
+    return (int)(w < kEvalMaxWg ? w : kEvalMaxWg);
+}
+
+}  // namespace nrgbd
+
+// the host work of export_res.py:108-116 these entries replace: see the header
+extern "C" int nrgbd_depth_eval_workgroups(long n) { return nrgbd::eval_workgroups(n); }
+
+extern "C" long nrgbd_depth_eval_workspace(long n, int J) {
+    const int nwg = nrgbd::eval_workgroups(n);
+    if (nwg < 0) return nwg;
+    if (J < 1 || J > nrgbd::kEvalMaxSets) return NRGBD_E_SHAPE;
+    return (long)nwg * (10 * J + 2) * 8;
+}
+
+extern "C" int nrgbd_depth_eval(const float* depth, const float* logconf, const float* gt, long n, float gt_min, float gt_max,
+                                const float* log_thr, int J, void* workspace, long workspace_bytes, double* frame_sums,
+                                long long* frame_counts, long long* frame_header, double* total_sums, long long* total_counts,
+                                long long* total_header, float* err_map, void* stream) {
+    using namespace nrgbd;
+    if (!depth || !logconf || !gt || !log_thr || !workspace || !frame_sums || !frame_counts || !frame_header) return NRGBD_E_NULL;
+    const int have_total = (total_sums ? 1 : 0) + (total_counts ? 1 : 0) + (total_header ? 1 : 0);
+    if (have_total != 0 && have_total != 3) return NRGBD_E_NULL;
+    const int nwg = eval_workgroups(n);
+    if (nwg < 0) return nwg;
+    if (J < 1 || J > kEvalMaxSets) return NRGBD_E_SHAPE;
+    EvalThr thr;
+    for (int j = 0; j < kEvalMaxSets; ++j) thr.t[j] = __builtin_nanf("");
+    if (!(log_thr[0] == -__builtin_inff())) return NRGBD_E_ARG;
+    for (int j = 0; j < J; ++j) {
+        if (log_thr[j] != log_thr[j] || (j > 0 && !(log_thr[j] > log_thr[j - 1]))) return NRGBD_E_ARG;
+        thr.t[j] = log_thr[j];
+    }
+    if (!(gt_min <= gt_max)) return NRGBD_E_ARG;               // a NaN bound, or an empty range
+    if (workspace_bytes < (long)nwg * (10 * J + 2) * 8) return NRGBD_E_SHAPE;
+    if ((uintptr_t)workspace & 7) return NRGBD_E_ALIGN;
+    double* ws_sums = (double*)workspace;
+    long long* ws_counts = (long long*)workspace + (size_t)nwg * 6 * J;
+    if (J == 1)
+        hipLaunchKernelGGL(depth_eval_kernel<1>, dim3(nwg), dim3(256), 0, (hipStream_t)stream, depth, logconf, gt, n, gt_min, gt_max, thr, J,
+                           ws_sums, ws_counts, err_map);
+    else
+        hipLaunchKernelGGL(depth_eval_kernel<kEvalMaxSets>, dim3(nwg), dim3(256), 0, (hipStream_t)stream, depth, logconf, gt, n, gt_min,
+                           gt_max, thr, J, ws_sums, ws_counts, err_map);
+    NRGBD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(depth_eval_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)ws_sums,
+                       (const long long*)ws_counts, nwg, J, frame_sums, frame_counts, frame_header, total_sums, total_counts, total_header);
+    NRGBD_CHECK_LAUNCH();
+    return NRGBD_OK;
+}

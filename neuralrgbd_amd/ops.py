@@ -1534,3 +1534,61 @@ def depth_ingest(depth, tables, depth_scale, thr_q, thr_full, labels_q=None, lab
             *(_p(t) for t in outs), H, W, h, w, _stream(depth))
     _lib.check(rc, "nrgbd_depth_ingest_u16")
     return tuple(outs)
+
+
+# ---- on-device depth evaluation (depth_eval.hip; neuralrgbd_amd/evaluate.py) ----------------------------------------------------
+
+def depth_eval_workgroups(n):
+    """Partial records nrgbd_depth_eval writes for n pixels (needs no GPU)."""
+    rc = _lib.load().nrgbd_depth_eval_workgroups(int(n))
+    if rc < 0:
+        _lib.check(rc, "nrgbd_depth_eval_workgroups")
+    return rc
+
+
+def depth_eval_workspace(n, J):
+    """Bytes of workspace nrgbd_depth_eval needs for n pixels and J confidence sets (needs no GPU)."""
+    rc = _lib.load().nrgbd_depth_eval_workspace(int(n), int(J))
+    if rc < 0:
+        _lib.check(rc, "nrgbd_depth_eval_workspace")
+    return rc
+
+
+def _eval_record(t, name, dtype, shape, dev):
+    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shape):
+        raise ValueError("depth_eval: %s must be a contiguous %s tensor %s on %s" % (name, dtype, shape, dev))
+    return t
+
+
+def depth_eval(depth, logconf, gt, log_thr, gt_range, workspace, frame, total=None, err_map=None):
+    """One depth map against its ground truth (nrgbd_depth_eval: replaces the host evaluation of test_utils/export_res.py:108-116).
+    depth / logconf / gt: contiguous CUDA fp32 tensors of one shape (the two maps of depth_regress, metres with 0 = a hole);
+    log_thr: host fp32 [J], ascending from -inf; gt_range = (gt_min, gt_max); workspace: a CUDA tensor of at least
+    depth_eval_workspace(n, J) bytes; frame / total: (sums float64 [J,6], counts int64 [J,4], header int64 [4]) — frame is written,
+    total (or None) is added to; err_map: fp32 of the maps' shape or None.  Two launches, nothing allocated, nothing synchronised."""
+    depth = _need(depth, "depth", strided=True)
+    dev, shape = depth.device, tuple(depth.shape)
+    for t, nm in ((depth, "depth"), (logconf, "logconf"), (gt, "gt")) + (((err_map, "err_map"),) if err_map is not None else ()):
+        t = _need(t, nm, shape, strided=True)
+        if t.device != dev or not t.is_contiguous():
+            raise ValueError("depth_eval: %s must be contiguous and on %s" % (nm, dev))
+    thr = np.ascontiguousarray(log_thr, dtype=np.float32)
+    if thr.ndim != 1 or not 1 <= thr.size <= _lib.DEPTH_EVAL_MAX_SETS:
+        raise ValueError("depth_eval: log_thr holds %s thresholds, expected 1 .. %d" % (thr.shape, _lib.DEPTH_EVAL_MAX_SETS))
+    J = int(thr.size)
+    if not isinstance(workspace, torch.Tensor) or workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError("depth_eval: workspace must be a contiguous tensor on %s" % (dev,))
+    recs = []
+    for rec, nm in ((frame, "frame"), (total, "total")):
+        if rec is None and nm == "total":
+            recs += [None, None, None]
+            continue
+        if rec is None or len(rec) != 3:
+            raise ValueError("depth_eval: %s is (sums, counts, header)" % nm)
+        recs += [_eval_record(rec[0], nm + " sums", torch.float64, (J, 6), dev), _eval_record(rec[1], nm + " counts", torch.int64, (J, 4), dev),
+                 _eval_record(rec[2], nm + " header", torch.int64, (4,), dev)]
+    with torch.cuda.device(dev):
+        rc = _lib.load().nrgbd_depth_eval(_p(depth), _p(logconf), _p(gt), depth.numel(), float(gt_range[0]), float(gt_range[1]),
+                                          ctypes.c_void_p(thr.ctypes.data), J, _p(workspace), workspace.numel() * workspace.element_size(),
+                                          *(_p(t) for t in recs), _p(err_map), _stream(depth))
+    _lib.check(rc, "nrgbd_depth_eval")
