@@ -60,7 +60,8 @@ extern "C" {
  * nrgbd_adam_step_clipped; no existing entry changed its signature or disappeared, so by the rule above the version string stays.
  * The same holds for nrgbd_frame_ingest_u8 and nrgbd_window_gather (the video stream's frame ingest and window assembly), and for
  * nrgbd_depth_ingest_u16 (the training stream's depth-label ingest).  0.10 also gained the on-device depth evaluation —
- * nrgbd_depth_eval_workgroups, nrgbd_depth_eval_workspace and nrgbd_depth_eval; no existing entry changed, the version string stays. */
+ * nrgbd_depth_eval_workgroups, nrgbd_depth_eval_workspace and nrgbd_depth_eval; no existing entry changed, the version string stays.
+ * The same holds for nrgbd_dgf_refine_f32 (the guided-filter refinement net). */
 #define NRGBD_INTERFACE_VERSION "0.10"
 const char* nrgbd_version(void);
 const char* nrgbd_strerror(int code);
@@ -922,6 +923,35 @@ int nrgbd_depth_eval(const float* depth, const float* logconf, const float* gt, 
                      const float* log_thr, int J, void* workspace, long workspace_bytes, double* frame_sums,
                      long long* frame_counts, long long* frame_header, double* total_sums, long long* total_counts,
                      long long* total_header, float* err_map, void* stream);
+/*
+ * nrgbd_dgf_refine_f32 — the guided-filter refinement net of KVNET(refineNet_name='DGF') in one launch (dgf.hip;
+ * neuralrgbd_amd/nets.py: DGFRefineNet).  Replaces models/Refine.py:620-641 (RefineNet_DGF.forward), models/GF/guided_filter.py:54-97
+ * and models/GF/box_filter.py: bilinear up-sampling of the regressed low-resolution depth (align_corners = True), the per-pixel
+ * 3 -> 64 -> 1 network on the image as the guide, and a radius-1 guided filter.  The function is the reference's; the arithmetic is
+ * the centred form (direct sums over the clipped 3 x 3 window, var = sum (x - mx)^2 / N), because the reference's own fp32 form
+ * (differences of cumsums, E[x^2] - E[x]^2) cancels: its fp32 bits are not reproduced, its float64 values are (README, "DGF").
+ *   depth_lr   device fp32 [n][h][w], n in {1, 2} targets that share one guide
+ *   img        device fp32 [3][H][W], planar and contiguous; H = s h and W = s w for one integer s >= 2; H, W in 4 .. 16384
+ *   w1 [64][3], b1 [64], w2 [64], b2 [1]   the two 1 x 1 convolutions of RefineNet_DGF.feature_ext, read in place
+ *   eps        the filter's regulariser (the reference: 1e-8)
+ *   out        device fp32 [n][H][W], every element written; any alignment (16-byte stores where the address allows, element stores
+ *              otherwise: the same bits)
+ * Per pixel, in fp32 and in this order (every division an IEEE division): y = the bilinear sample with integer coordinates
+ * (num = i (h - 1), i0 = num / (H - 1), lam = float(num % (H - 1)) / float(H - 1), i1 = min(i0 + 1, h - 1); the same along columns;
+ * y = (1 - lr) ((1 - lc) d00 + lc d01) + lr ((1 - lc) d10 + lc d11));  x = b2 + sum_k w2[k] max(0, b1[k] + w1[k][0] r + w1[k][1] g +
+ * w1[k][2] b), k ascending, fused multiply-adds;  over the 3 x 3 window clipped to the image (N = 4, 6 or 9 pixels, row-major sums):
+ * mx = sum x / N, my = sum y / N, var = sum (x - mx)^2 / N, cov = sum (x - mx)(y - my) / N, A = cov / (var + eps), b = my - A mx;
+ * out = (sum A / N) x + (sum b / N).  A target's bits do not depend on n.  No atomics, no workspace: capturable, the same bits in
+ * every run.
+ *   errors     NRGBD_E_NULL: a NULL pointer;  NRGBD_E_SHAPE: an extent <= 0 or above 16384, H, W not one common integer multiple
+ *              s >= 2 of h, w, H <= 3 or W <= 3 (guided_filter.py:74);  NRGBD_E_ARG: n outside {1, 2}, eps negative or NaN.
+ *              Every argument is checked before anything touches the device.
+ */
+#define NRGBD_DGF_TILE_Y 16
+#define NRGBD_DGF_TILE_X 64
+int nrgbd_dgf_refine_f32(const float* depth_lr, int n, int h, int w, const float* img, int H, int W,
+                         const float* w1, const float* b1, const float* w2, const float* b2, float eps,
+                         float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -173,6 +173,8 @@ class EvalVideoStream:
 
     def __init__(self, model, cam_intrinsics, d_candi, t_win_r=2, depth_scale=.001, conf_thresholds=(0.,), gt_range=(1e-3, float("inf")),
                  net_size=None, **video_kwargs):
+        from .nets import require_volume_refiner
+        require_volume_refiner(model, "EvalVideoStream")
         self.video = VideoDepthStream(model, cam_intrinsics, d_candi, t_win_r=t_win_r, net_size=net_size, **video_kwargs)
         self.device, self.t_win_r, self.d_candi = self.video.device, t_win_r, d_candi
         h, w = _grid_size(cam_intrinsics)

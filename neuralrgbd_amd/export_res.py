@@ -22,6 +22,10 @@ def depth_conf_u16(BV_measure, d_candi, depth_scale=1000, conf_scale=1000):
     the files are identical whenever depth * scale < 65536 (65.5 m at the default scale), and beyond that a saturated
     pixel replaces a wrapped (meaningless) one.  exp is the path's exp_rn (correctly rounded, same operation sequence as
     the CPU oracle): the uint16 maps are bit-identical to the oracle's."""
+    if BV_measure.dim() == 4 and BV_measure.shape[1] == 1 and len(d_candi) > 1:
+        from ._lib import NrgbdError
+        raise NrgbdError("export_res: a one-channel map against %d candidates (e.g. the depth map a model with refineNet_name='DGF' "
+                         "returns) is not on this path — the exporters take a volume with one channel per candidate" % len(d_candi))
     assert BV_measure.shape[0] == 1 and BV_measure.shape[1] == len(d_candi)
     d_dev = _homo._d_candi_dev(d_candi, BV_measure.device)
     return ops.export_depth_u16(BV_measure[0], d_dev, float(depth_scale), float(conf_scale),

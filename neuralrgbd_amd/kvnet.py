@@ -127,16 +127,21 @@ class KVNET(nn.Module):
         self.if_refined = if_refined
         self.refineNet_name = refineNet_name
         self.if_upsample_d = if_upsample_d
-        if if_refined and refineNet_name != 'DPV':
-            raise NotImplementedError("only the 'DPV' refinement net is on this path (the reference scripts never select 'DGF')")
+        if if_refined and refineNet_name not in ('DPV', 'DGF'):
+            raise NotImplementedError("refineNet_name %r: the refinement nets are 'DPV' and 'DGF' (KVNET.py:43)" % (refineNet_name,))
 
-        dpv_refine = bool(if_refined)
+        # 'DGF' (KVNET.py:68-73,80-81): no multi-scale feature outputs, no R-Net volume — the regressed depth map through the
+        # guided-filter net; if_upsample_d has no effect there, as in the reference
+        dpv_refine = bool(if_refined) and refineNet_name == 'DPV'
         self.feature_extractor = nets.FeatureExtractor(feature_dim=feature_dim, multi_scale=dpv_refine)
         self.d_net = DNet(self.feature_extractor, cam_intrinsics, d_candi, sigma_soft_max,
                           use_img_intensity=True, BV_log=True, output_features=dpv_refine)
         self.kv_net = nets.KalmanGainNet(3 * (t_win_r * 2 + 1) + 1, feature_dim=KVNet_feature_dim,
                                          up_sample_ratio=d_upsample_ratio_KV_net)
-        if if_refined:
+        self.dgf_refine = bool(if_refined) and refineNet_name == 'DGF'
+        if self.dgf_refine:
+            self.r_net = nets.DGFRefineNet(refine_channel)
+        elif if_refined:
             self.r_net = nets.DPVUpsampleNet(int(feature_dim), int(feature_dim / 2), 3,
                                              D=len(d_candi), upsample_D=if_upsample_d)
 
@@ -150,17 +155,29 @@ class KVNET(nn.Module):
             return self.r_net.forward_log(dpv_log, features)      # exp fused into the first concat; matrix-core convs
         return self.r_net(torch.exp(dpv_log), img_features=features)
 
+    def _regress_lowres(self, volumes):
+        """The expected depths of n log-volumes [1,D,h,w] as one [n,1,h,w] tensor (misc.depth_val_regression: the depth_regress
+        kernel writing into its slice; on host tensors the same sum in torch)."""
+        v0 = volumes[0]
+        if v0.is_cuda:
+            out = torch.empty((len(volumes), 1) + tuple(v0.shape[2:]), dtype=torch.float32, device=v0.device)
+            for i, v in enumerate(volumes):
+                depth_val_regression(v, self.d_candi, BV_log=True, out=out[i])
+            return out
+        d = torch.as_tensor(np.asarray(self.d_candi), dtype=v0.dtype).view(1, -1, 1, 1)
+        return torch.cat([(torch.exp(v) * d).sum(1, keepdim=True) for v in volumes], dim=0)
+
     # ------------------------------------------------------------------ the frame in two halves (streaming.DepthStream pipelines them)
     def measure(self, ref_frame, src_frames, src_cam_poses):
         """FRONT half of an inference frame: everything that does not depend on the filter state — the feature CNN of the window,
         the texel pack, the fused warp + cost volume + log-softmax (KVNET.py:120-123: `self.d_net(...)`).  Returns the record
         `forward(..., measured=record)` continues from: the D-Net of frame t+1 can run while the K-Net of frame t is still busy
         (a2-a4 of the next frame are independent of this frame's state)."""
-        if self.if_refined:
+        if self.if_refined and not self.dgf_refine:
             BV_cur, features = self.d_net(ref_frame, src_frames, src_cam_poses, BV_predict=None)
             features.append(ref_frame)
-        else:
-            BV_cur, features = self.d_net(ref_frame, src_frames, src_cam_poses, BV_predict=None), None
+        else:       # 'DGF': the reference frame alone, as the guide (KVNET.py:132,178)
+            BV_cur, features = self.d_net(ref_frame, src_frames, src_cam_poses, BV_predict=None), ([ref_frame] if self.dgf_refine else None)
         return {"BV_cur": BV_cur, "features": features, "texels": self.d_net.texels, "rgb4": self.d_net.rgb4}
 
     def forward(self, ref_frame, src_frames, src_cam_poses, BatchIdx, cam_intrinsics=None,
@@ -170,6 +187,8 @@ class KVNET(nn.Module):
         cam_intrinsics: list of dicts, BV_predict [1,D,h,w] or None.
         Returns (dmap_cur_refined, dmap_refined, BV_cur, DPV); the first / invalid frame returns the
         D-Net pair twice; -1 sentinels when if_refined is False (KVNET.py:136-143,182).
+        refineNet_name='DGF': the two refined outputs are [1,1,H,W] depth maps in metres (the regressed quarter-resolution map
+        through nets.DGFRefineNet under the reference frame; KVNET.py:129-132,176-178), inference only on the GPU.
         `dpv_valid` (extension): host-side validity of BV_predict; None = probe the tensor like
         the reference's valid_dpv (one device->host read).
         `measured` (extension): the record of `measure()` for this window — the D-Net is then not run again.
@@ -179,6 +198,10 @@ class KVNET(nn.Module):
             dpv_valid = valid_dpv(BV_predict)
         if has_pred and dpv_valid:
             assert BV_predict.shape[0] == 1
+        if self.dgf_refine and torch.is_grad_enabled() and ref_frame.is_cuda:
+            from ._lib import NrgbdError
+            raise NrgbdError("KVNET(refineNet_name='DGF') is inference only on the GPU: nrgbd_dgf_refine_f32 has no backward "
+                             "(call it under torch.no_grad())")
 
         # update branch at inference: the two R-Net calls of the frame (on BV_cur and on DPV; Refine.py is a per-sample
         # network without BatchNorm) run as ONE batch of 2 after the K-Net — twice the workgroups per launch for the
@@ -188,7 +211,10 @@ class KVNET(nn.Module):
         if measured is None:
             measured = self.measure(ref_frame, src_frames, src_cam_poses)
         BV_cur, features = measured["BV_cur"], measured["features"]
-        if self.if_refined:
+        update = has_pred and bool(dpv_valid)
+        if self.dgf_refine:     # KVNET.py:129-132; on an update frame BV_cur and DPV go through one launch below
+            dmap_cur_refined = None if update else self.r_net(self._regress_lowres((BV_cur,)), features[-1])
+        elif self.if_refined:
             dmap_cur_refined = None if batch_refine else self._refine(BV_cur, features)
         else:
             dmap_cur_refined = -1
@@ -253,7 +279,10 @@ class KVNET(nn.Module):
             else:
                 DPV = torch.log_softmax(gain + BV_predict, dim=1)
 
-        if batch_refine:
+        if self.dgf_refine:                                                              # KVNET.py:176-178
+            both = self.r_net(self._regress_lowres((BV_cur, DPV)), features[-1])         # [2,1,H,W]: one launch, one guide
+            dmap_cur_refined, dmap_refined = both[0:1], both[1:2]
+        elif batch_refine:
             both = self.r_net.forward_log((BV_cur, DPV), features)                       # [2,D,H,W]; no concatenation pass
             dmap_cur_refined, dmap_refined = both[0:1], both[1:2]
         else:

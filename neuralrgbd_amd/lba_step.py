@@ -151,6 +151,8 @@ class LBADepthStream:
                  use_dso_t=False, opt_next_frame=False, dw_scales=DW_SCALES):
         if len(cams_intrin) != 3:
             raise ValueError("LBADepthStream: three camera dicts (quarter, half, image size), got %d" % len(cams_intrin))
+        from .nets import require_volume_refiner
+        require_volume_refiner(model, "LBADepthStream")
         if getattr(model, "if_upsample_d", False):
             raise NrgbdError("LBADepthStream: a model with if_upsample_d refines to 4 D candidates, the keyframe maps take D (the reference's LBA driver never builds one)")
         self.model = model

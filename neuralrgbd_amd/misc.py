@@ -26,15 +26,16 @@ def valid_dpv(dpv_in):
     return ok
 
 
-def depth_val_regression(BV_measure, d_candi_cur, BV_log=True):
+def depth_val_regression(BV_measure, d_candi_cur, BV_log=True, out=None):
     """Expected depth sum_d p_d * d of a [1,D,h,w] volume -> [1,h,w] (mutils/misc.py:532-548).
-    One kernel instead of a Python loop over D."""
+    One kernel instead of a Python loop over D.  `out` (extension): a contiguous fp32 [1,h,w] tensor to write the map into."""
     assert len(d_candi_cur) == BV_measure.shape[1], \
         'BV_measure should have the same # of slices as len(d_candi_cur) !'
     d_dev = _homo._d_candi_dev(d_candi_cur, BV_measure.device)
     logp = BV_measure[0] if BV_log else torch.log(BV_measure[0])
     # the refined volume is an NCHW view of channels-last memory (DPVUpsampleNet.forward_log, autograd.LogSoftmaxCL): read it there
-    depth, _ = ops.depth_regress(logp, d_dev, want_conf=False, channels_last=ops.is_channels_last_view(logp))
+    depth, _ = ops.depth_regress(logp, d_dev, want_conf=False, channels_last=ops.is_channels_last_view(logp),
+                                 out=None if out is None else out.view(logp.shape[1:]))
     return depth.unsqueeze(0)
 
 

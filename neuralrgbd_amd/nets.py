@@ -1032,3 +1032,85 @@ class DPVUpsampleNet(_PackedWeightsMixin, nn.Module):
         if LogSoftmaxCL.supported(x) and x.permute(0, 2, 3, 1).is_contiguous():
             return LogSoftmaxCL.apply(x)           # channels-last rows kernel; the result stays an NCHW view of that memory
         return torch.log_softmax(x, dim=1)
+
+
+# --------------------------------------------------------------------------- the guided-filter refinement net
+def dgf_host(dmap, img_guide, w1, b1, w2, b2, eps=1e-8):
+    """The function of nrgbd_dgf_refine_f32 in plain torch, at the tensors' dtype (host tensors: structure and numerics tests):
+    dmap [n,1,h,w], img_guide [1,3,H,W] -> [n,1,H,W].  Same formula as the kernel — integer-coordinate bilinear up-sampling
+    (align_corners=True), the 3 -> 64 -> 1 network, centred sums over the 3 x 3 window clipped to the image — in torch's own
+    summation order."""
+    n, _, h, w = dmap.shape
+    H, W = img_guide.shape[2:]
+    dt, dev = dmap.dtype, dmap.device
+
+    def table(lo, hi):
+        num = torch.arange(hi, dtype=torch.int64, device=dev) * (lo - 1)
+        i0 = num // (hi - 1)
+        lam = (num % (hi - 1)).to(dt) / float(hi - 1)
+        return i0, torch.clamp(i0 + 1, max=lo - 1), lam
+    r0, r1, lr = table(h, H)
+    c0, c1, lc = table(w, W)
+    lr, lc = lr.view(1, 1, H, 1), lc.view(1, 1, 1, W)
+    top, bot = dmap[:, :, r0], dmap[:, :, r1]
+    y = (1 - lr) * ((1 - lc) * top[..., c0] + lc * top[..., c1]) + lr * ((1 - lc) * bot[..., c0] + lc * bot[..., c1])
+    x = F.conv2d(torch.relu(F.conv2d(img_guide.to(dt), w1.reshape(64, 3, 1, 1).to(dt), b1.reshape(64).to(dt))),
+                 w2.reshape(1, 64, 1, 1).to(dt), b2.reshape(1).to(dt))                      # [1,1,H,W]
+
+    def window(t):      # [k,1,H,W] -> [9,k,1,H,W]: the 3 x 3 neighbours in row-major order, zeros outside the image
+        p = F.pad(t, (1, 1, 1, 1))
+        return torch.stack([p[..., dy:dy + H, dx:dx + W] for dy in range(3) for dx in range(3)])
+    inside = window(torch.ones((1, 1, H, W), dtype=dt, device=dev))
+    N = inside.sum(0)
+    wx, wy = window(x), window(y)
+    mx, my = wx.sum(0) / N, wy.sum(0) / N
+    cx, cy = (wx - mx) * inside, (wy - my) * inside
+    A = ((cx * cy).sum(0) / N) / ((cx * cx).sum(0) / N + eps)
+    b = my - A * mx
+    return (window(A).sum(0) / N) * x + window(b).sum(0) / N
+
+
+class DGFRefineNet(nn.Module):
+    """Drop-in for Refine.py:587-641 (RefineNet_DGF): the regressed low-resolution depth map, up-sampled bilinearly and filtered by a
+    radius-1 guided filter whose guide is a per-pixel 3 -> 64 -> 1 network on the image.  State-dict keys and shapes are the
+    reference's (feature_ext.0 / feature_ext.2).  On the GPU the whole net is ONE launch (ops.dgf_refine) that reads the parameters
+    in place; on host tensors the same formula runs in torch (dgf_host).  The arithmetic is the centred form of the reference's
+    function, not its fp32 bits (README, "DGF")."""
+
+    def __init__(self, in_channels):
+        super().__init__()
+        if in_channels != 3:
+            raise ValueError("DGFRefineNet: the guide network is Conv2d(3, 64, 1): in_channels = %s cannot run "
+                             "(nor can the reference's RefineNet_DGF, Refine.py:593,628)" % (in_channels,))
+        self.in_channels = in_channels
+        self.eps = 1e-8                                         # DGF.GuidedFilter(r=1, eps=1e-8), Refine.py:591
+        self.feature_ext = nn.Sequential(nn.Conv2d(3, 64, 1), nn.ReLU(inplace=True), nn.Conv2d(64, 1, 1))
+        _he_init(self)                                          # Refine.py:600-603: weights only, the biases keep torch's default
+
+    def forward(self, dmap, img_guide):
+        """dmap [n,1,h,w] (n in {1, 2} on the GPU), img_guide [1,3,H,W] -> [n,1,H,W] (Refine.py:620-641; asserts as there)."""
+        assert dmap.dim() == img_guide.dim() == 4 and dmap.size()[1] == 1, 'input format is wrong'
+        assert self.in_channels == img_guide.shape[1]
+        H, W = img_guide.shape[2:]
+        up_ratio_H, up_ratio_W = int(H / dmap.shape[2]), int(W / dmap.shape[3])
+        assert up_ratio_H == up_ratio_W, 'aspect ratio should correspond'
+        assert up_ratio_H > 1, 'guided image resolution should > depth res.'
+        assert H == up_ratio_H * dmap.shape[2] and W == up_ratio_W * dmap.shape[3]     # guided_filter.py:73 on the up-sampled map
+        assert H > 3 and W > 3                                  # guided_filter.py:74
+        c1, c2 = self.feature_ext[0], self.feature_ext[2]
+        if dmap.is_cuda:
+            from . import ops
+            if dmap.dtype != torch.float32:
+                raise _no_kernel("the DGF refinement net in %s (fp32 only)" % dmap.dtype)
+            return ops.dgf_refine(dmap.detach(), img_guide.detach(), c1.weight.detach(), c1.bias.detach(), c2.weight.detach(),
+                                  c2.bias.detach(), self.eps)
+        return dgf_host(dmap, img_guide, c1.weight, c1.bias, c2.weight, c2.bias, self.eps)
+
+
+def require_volume_refiner(model, who):
+    """The drivers that take a refined VOLUME from the model (training losses, evaluation, keyframe maps) refuse a
+    KVNET(refineNet_name='DGF'), which refines to a depth map: an error by name where the driver is built or called."""
+    if getattr(model, "if_refined", False) and getattr(model, "refineNet_name", "DPV") == "DGF":
+        from ._lib import NrgbdError
+        raise NrgbdError("%s: refineNet_name='DGF' is not on this path — the model refines to a [1,1,H,W] depth map, "
+                         "%s takes a refined volume (use refineNet_name='DPV')" % (who, who))

@@ -298,9 +298,10 @@ def _rows_volume(logp):
     return rows, logp.shape[0], logp.numel() // logp.shape[0]
 
 
-def depth_regress(logp, d_candi, want_conf=True, channels_last=False):
+def depth_regress(logp, d_candi, want_conf=True, channels_last=False, out=None):
     """logp [D, ...] -> (expected depth [...], max log-prob [...]).  channels_last: logp is a [D, ...] view of contiguous
-    channels-last memory [..., D] and is read as it lies (nrgbd_depth_regress_rows: the same bits, no transposing copy)."""
+    channels-last memory [..., D] and is read as it lies (nrgbd_depth_regress_rows: the same bits, no transposing copy).
+    out: a contiguous fp32 tensor of the depth map's shape to write it into (default: a fresh one)."""
     if channels_last:
         rows, D, n = _rows_volume(logp)
     else:
@@ -308,7 +309,9 @@ def depth_regress(logp, d_candi, want_conf=True, channels_last=False):
         D = logp.shape[0]
         n = logp.numel() // D
     d_candi = _need(d_candi, "d_candi", (D,))
-    depth = torch.empty(logp.shape[1:], dtype=torch.float32, device=logp.device)
+    depth = torch.empty(logp.shape[1:], dtype=torch.float32, device=logp.device) if out is None else out
+    if (depth.shape != logp.shape[1:] or depth.dtype != torch.float32 or depth.device != logp.device or not depth.is_contiguous()):
+        raise ValueError("depth_regress: out must be a contiguous float32 tensor %s on %s" % (tuple(logp.shape[1:]), logp.device))
     conf = torch.empty_like(depth) if want_conf else None
     with torch.cuda.device(logp.device):
         if channels_last:
@@ -1592,3 +1595,43 @@ def depth_eval(depth, logconf, gt, log_thr, gt_range, workspace, frame, total=No
                                           ctypes.c_void_p(thr.ctypes.data), J, _p(workspace), workspace.numel() * workspace.element_size(),
                                           *(_p(t) for t in recs), _p(err_map), _stream(depth))
     _lib.check(rc, "nrgbd_depth_eval")
+
+
+# ---- the guided-filter refinement net (dgf.hip; neuralrgbd_amd/nets.py: DGFRefineNet) -------------------------------------------
+
+DGF_TILE = _lib.DGF_TILE        # (rows, columns) of the image tile a workgroup of nrgbd_dgf_refine_f32 owns
+
+
+def dgf_refine(depth_lr, img, w1, b1, w2, b2, eps=1e-8, out=None):
+    """The DGF refinement of n in {1, 2} low-resolution depth maps under one guide image, one launch (nrgbd_dgf_refine_f32: replaces
+    Refine.py:620-641, GF/guided_filter.py:54-97 and GF/box_filter.py).
+    depth_lr [n,h,w] or [n,1,h,w]; img [3,H,W] or [1,3,H,W] with H = s h, W = s w, s >= 2; w1 / b1 / w2 / b2: the parameters of
+    Conv2d(3, 64, 1) and Conv2d(64, 1, 1) in any shape of 192 / 64 / 64 / 1 contiguous elements (read in place).
+    Returns [n,1,H,W]; `out`: a contiguous fp32 tensor of n H W elements to write into instead (any alignment)."""
+    depth_lr, img = _need(depth_lr, "depth_lr"), _need(img, "img")
+    if depth_lr.dim() == 4 and depth_lr.shape[1] == 1:
+        depth_lr = depth_lr[:, 0]
+    if img.dim() == 4 and img.shape[0] == 1:
+        img = img[0]
+    if depth_lr.dim() != 3 or img.dim() != 3 or img.shape[0] != 3:
+        raise ValueError("dgf_refine: depth_lr [n,h,w] and img [3,H,W], got %s and %s" % (tuple(depth_lr.shape), tuple(img.shape)))
+    n, h, w = depth_lr.shape
+    H, W = img.shape[1:]
+    params = []
+    for t, nm, numel in ((w1, "w1", 192), (b1, "b1", 64), (w2, "w2", 64), (b2, "b2", 1)):
+        t = _need(t, nm)
+        if t.numel() != numel or t.device != img.device:
+            raise ValueError("dgf_refine: %s holds %d elements on %s, expected %d on %s" % (nm, t.numel(), t.device, numel, img.device))
+        params.append(t)
+    if depth_lr.device != img.device:
+        raise ValueError("dgf_refine: depth_lr on %s, img on %s" % (depth_lr.device, img.device))
+    if out is None:
+        out = torch.empty((n, 1, H, W), dtype=torch.float32, device=img.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != img.device or not out.is_contiguous()
+          or out.numel() != n * H * W):
+        raise ValueError("dgf_refine: out must be a contiguous float32 tensor of %d elements on %s" % (n * H * W, img.device))
+    with torch.cuda.device(img.device):
+        rc = _lib.load().nrgbd_dgf_refine_f32(_p(depth_lr), n, h, w, _p(img), H, W, *(_p(t) for t in params), float(eps), _p(out),
+                                              _stream(img))
+    _lib.check(rc, "nrgbd_dgf_refine_f32")
+    return out.view(n, 1, H, W)

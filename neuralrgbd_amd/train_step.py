@@ -5,7 +5,8 @@ Differences from the reference, all forced by replacing single-process `DataPara
   * each process owns ONE trajectory (N = 1: the reference asserts N = 1 per replica anyway, KVNET.py:116);
   * the `loss / nGPU` + DataParallel reduce-add (:149-152) becomes an all-reduce of the gradient (sum / world)
     right after `backward()` — pass `grad_reducer=neuralrgbd_amd.distributed.GradAllReduce(model)`;
-  * only loss_type 'NLL' (what every training script of the reference uses; 'L1' needs the DGF net).
+  * only loss_type 'NLL' (what every training script of the reference uses; 'L1' is for the DGF net, which runs at
+    inference only here: train() and TrainGraph refuse a KVNET(refineNet_name='DGF') by name).
 Forward/backward run the fused HIP sampling kernels behind autograd (neuralrgbd_amd.autograd); the PREDICT step
 at the end is the same single launch as at inference.
 """
@@ -19,6 +20,7 @@ from . import homography as warp_homo
 from . import ops
 from .autograd import deterministic as _deterministic, nll_loss_d, pack_cache
 from .misc import depth_val_regression, valid_dpv
+from .nets import require_volume_refiner as _require_volume_refiner
 
 
 def _capture_mode():
@@ -141,7 +143,9 @@ def train(nGPU, model_KV, optimizer_KV, t_win_r, d_candi, Ref_Dats, Src_Dats, Sr
     other optimizer gets optim.clip_grad_norm_ in place.  skip_nonfinite=True (FusedAdam only, else ValueError): a step whose
     gradient norm is inf / NaN changes no parameter, moment or step count."""
     if loss_type != 'NLL':
-        raise NotImplementedError("only the NLL loss is on this path")
+        raise NotImplementedError("only the NLL loss is on this path (the reference's 'L1' / depth_var terms are for "
+                                  "refineNet_name='DGF', whose net runs at inference only here)")
+    _require_volume_refiner(model_KV, "train_step.train")
     _check_dup(model_KV, refine_dup)
     _check_clip(optimizer_KV, grad_clip_max, skip_nonfinite)
     A = int(accum_steps)
@@ -208,6 +212,7 @@ class TrainGraph:
         up-sampled label `dmap_up4_imgsize_digit` (bins in [0, 4 D)).  A flag that disagrees with the model raises ValueError.
         deterministic: None follows neuralrgbd_amd.autograd.is_deterministic() at each eager iteration and at capture (a graph
         keeps the kernels it was captured with); True / False set the switch around this object's forward and backward."""
+        _require_volume_refiner(model, "TrainGraph")
         _check_dup(model, refine_dup)
         _check_clip(optimizer, grad_clip_max, skip_nonfinite)
         self.grad_clip_max, self.skip_nonfinite = grad_clip_max, bool(skip_nonfinite)

@@ -180,6 +180,8 @@ class TrainVideoStream:
             raise ValueError("TrainVideoStream: t_win_r %s, expected 1 .. %d" % (t_win_r, _lib.GATHER_MAX_V // 2))
         if getattr(model, "t_win_r", t_win_r) != t_win_r:
             raise ValueError("TrainVideoStream: the model was built for t_win_r %s, the stream for %s" % (model.t_win_r, t_win_r))
+        from .nets import require_volume_refiner
+        require_volume_refiner(model, "TrainVideoStream")
         _check_dup(model, refine_dup)
         _check_clip(optimizer, grad_clip_max, skip_nonfinite)
         mean, std = tuple(float(m) for m in mean), tuple(float(s) for s in std)
