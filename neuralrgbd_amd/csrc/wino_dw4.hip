@@ -28,13 +28,24 @@
 //   * producers: a stage combines 3 or 4 slices with rational coefficients.  The unit of prefetch stays one (slice, channel block) in one of
 //     four register sets (the fourth empty for t = 0 and t = 5), all requested one stage ahead; the stage's combination sum_k c_k act(x_k)
 //     is formed in registers and the strip written once (wino_dw.hip publishes unit A and read-modify-writes the strip for unit B).
+//   * PAIRED PHASES (Cin <= 64, i.e. every K-Net layer).  For t = 1..4 the four units are the same slices j = 4, 1, 2, 3; only the
+//     coefficients differ.  A stage of t = 1 (t = 3) therefore runs a second FMA chain with the coefficients of t = 2 (t = 4) on the
+//     units it has just activated — same slot order, same first-slot rule, same outside-slice test: the bits are those of the stage
+//     that loaded them afresh — and keeps its three words per lane in registers (one set per channel block, up to four in flight:
+//     48 VGPRs).  The stage of t = 2 (t = 4) loads and activates nothing: kept words, plane mask, strip.  Unit loads per tile and
+//     channel block: 4+0+4+0+3+3 = 14 instead of 22.  Prefetch: the last stage of a loading phase requests nothing, and the stages
+//     of the restoring phase request the sets of the next loading stage spread over themselves (d4_restore).
+//     Measured on one MI355X, 64 -> 64 at 64x192x256, parent and this file alternated (profiles/dw4_pair_reuse.txt): the producers'
+//     vector-memory reads fall by exactly 8/22 (16.17 M -> 13.81 M instructions per launch with the consumers'), beyond-L2 fetch by
+//     11-12 %; the pairing alone 1.781 -> 1.736 ms IDENT, 1.752 -> 1.731 ms CLAMP; with the two select-to-branch changes below
+//     (d4_mask, the first slot) 1.721 ms and 1.713 ms: -3.4 % and -2.2 %.
 //   * only the two forms the K-Net uses behind its materialise passes: IDENT (x as it is) and CLAMP (relu(x * s + t) as a clamped FMA).
-// Work per four output slices: 24 stages (wino_dw: 32); producer units 88 (64): 5.5 per output slice instead of 4, MFMAs 0.75x.
+// Work per four output slices: 24 stages (wino_dw: 32), 16 of them loading; producer units 56 (wino_dw: 64), MFMAs 0.75x.
 //
 // In wino_dw.hpp, shared with wino_dw.hip: the constants, DwTile + dw_decode<4>, the serpentine order dw_cb, the barrier protocol, the
 // consumers' steps (dw_lane, dw_prime, dw_phase / dw_mfma_stage, dw_plane_inverse, dw_emit, dw_store_stats), the producers' (dw_items,
 // dw_book, dw_activate, dw_transform, DwProd), the weight packer (dw_pack<6>) and the host helpers.  Here: the F(4, 3) depth transform
-// — the coefficient tables d4_*, d4_issue, d4_combine, d4_fold — the kernel and its launcher.
+// — the coefficient tables d4_*, d4_issue, d4_combine, d4_restore, d4_stage, d4_fold — the kernel and its launcher.
 #include "wino_dw.hpp"
 
 namespace nrgbd {
@@ -123,6 +134,35 @@ __device__ __forceinline__ void d4_fold(const DwAcc& acc, const WinoPcArgs& a, c
 
 // ======================================================= producer steps =====================================================
 struct D4Regs { f32x4 pre[kDwNPF]; };
+// the combination of depth index t + 1 a stage of t = 1 or t = 3 formed beside its own: a lane's three words of one channel block
+struct D4Keep { f32x2 lo[kDwNPF], hi[kDwNPF]; };
+
+// one more unit into the running combination(s): + c u (and, PAIR, + cp u into the kept one)
+template <bool PAIR>
+__device__ __forceinline__ void d4_chain(const f32x2 (&ul)[kDwNPF], const f32x2 (&uh)[kDwNPF], float c, float cp, f32x2 (&lo)[kDwNPF],
+                                         f32x2 (&hi)[kDwNPF], D4Keep& kp) {
+    const f32x2 c2 = {c, c};
+#pragma unroll
+    for (int i = 0; i < kDwNPF; ++i) { lo[i] = __builtin_elementwise_fma(ul[i], c2, lo[i]); hi[i] = __builtin_elementwise_fma(uh[i], c2, hi[i]); }
+    if constexpr (PAIR) {
+        const f32x2 p2 = {cp, cp};
+#pragma unroll
+        for (int i = 0; i < kDwNPF; ++i) { kp.lo[i] = __builtin_elementwise_fma(ul[i], p2, kp.lo[i]); kp.hi[i] = __builtin_elementwise_fma(uh[i], p2, kp.hi[i]); }
+    }
+}
+
+// the zero padding of the plane: one multiply of the combined words, in tiles that touch the plane's edge only (80 % are interior).
+// A branch (the empty asm keeps it one): as selects, 6 multiplies and 12 selects in every stage of every tile.
+__device__ __forceinline__ void d4_mask(const DwProd& P, f32x2 (&lo)[kDwNPF], f32x2 (&hi)[kDwNPF]) {
+    if (!P.interior) {
+        asm volatile("");
+#pragma unroll
+        for (int i = 0; i < kDwNPF; ++i) {
+            const f32x2 kk = {P.cur.keep[i], P.cur.keep[i]};
+            lo[i] = lo[i] * kk; hi[i] = hi[i] * kk;
+        }
+    }
+}
 
 // raw words of one unit = (slice z0 - 1 + j, channel block cb) -> registers; nx: of the NEXT tile (book nxt, tile tn)
 __device__ __forceinline__ void d4_issue(const WinoPcArgs& a, const DwProd& P, bool nx, int j, int cb, D4Regs& r) {
@@ -143,66 +183,127 @@ __device__ __forceinline__ void d4_issue(const WinoPcArgs& a, const DwProd& P, b
 // one register set per unit slot, a whole stage for the load to land (two sets alternating inside the stage left one unit of work
 // between request and use).  The refills stay spread over the stage: twelve loads in one burst cost ~600 issue cycles in a row, and
 // one wait for all four sets exposes the slowest — measured +3 % against this order.
-template <bool IDENT, bool CLAMP>
+// PAIR (phases t = 1 and t = 3 when the kept sets are in use): t + 1 names the SAME four slices with other coefficients, so every
+// activated unit feeds a second FMA chain — same slot order, same "first slot copied or zero" rule, same outside-slice test as the
+// stage of t + 1 would apply, hence the same bits — whose three words per lane wait in `kp` for d4_restore.  The last stage of such
+// a phase requests nothing: its successor loads nothing, and d4_restore requests the sets of the next loading stage.
+template <bool IDENT, bool CLAMP, bool PAIR>
 __device__ __forceinline__ void d4_combine(const WinoPcArgs& a, const DwProd& P, int NS, int ncb, int s, int p, int cbi, D4Regs& set0, D4Regs& set1,
-                                           D4Regs& set2, D4Regs& set3) {
+                                           D4Regs& set2, D4Regs& set3, D4Keep& kp) {
     float* raw = P.strip(P.gi & 1);
-    const int t = d4_t(p), cb = dw_cb(p, cbi, ncb), nsl = d4_nslot(t);
-    // stage s + 1: (position, channel block, depth index), possibly of the next tile
-    const bool nx = s + 1 >= NS;
+    const int t = d4_t(p), cb = PAIR ? cbi : dw_cb(p, cbi, ncb), nsl = d4_nslot(t);      // PAIR: p is even, a forward sweep
+    // stage s + 1: (position, channel block, depth index), possibly of the next tile; PAIR: the next block of this phase, if any
+    const bool nx = !PAIR && s + 1 >= NS;
+    const bool refill = !PAIR || cbi + 1 < ncb;
     const int cbn = cbi + 1 == ncb ? 0 : cbi + 1, pn = nx ? 0 : (cbi + 1 == ncb ? p + 1 : p);
-    const int tnx = d4_t(pn), cbne = dw_cb(pn, cbn, ncb);
+    const int tnx = PAIR ? t : d4_t(pn), cbne = PAIR ? cbi + 1 : dw_cb(pn, cbn, ncb);
     f32x4 ssw[2] = {{1.f, 1.f, 0.f, 0.f}, {1.f, 1.f, 0.f, 0.f}};     // (scale, shift) pairs of the stage's channel block (pre-paired table)
     if constexpr (!IDENT) {
         ssw[0] = *reinterpret_cast<const f32x4*>(P.ssl + 2 * (cb * kCB + P.p.w4 * 4));
         ssw[1] = *reinterpret_cast<const f32x4*>(P.ssl + 2 * (cb * kCB + P.p.w4 * 4) + 4);
     }
     const int nsn = d4_nslot(tnx);
-    float c[4];
+    float c[4], cp[4];                                       // cp: the partner's (t + 1) coefficients, PAIR only
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int z = P.tl.z0 - 1 + d4_j(t, k < nsl ? k : 0);
-        c[k] = (k < nsl && z >= 0 && z < a.N) ? d4_c(t, k) : 0.f;
+        const bool in = k < nsl && z >= 0 && z < a.N;
+        c[k] = in ? d4_c(t, k) : 0.f;
+        cp[k] = PAIR && in ? d4_c(t + 1, k) : 0.f;
     }
     f32x2 lo[kDwNPF], hi[kDwNPF], ul[kDwNPF], uh[kDwNPF];
-    dw_activate<IDENT, CLAMP>(set0.pre, ssw, a.x_relu, ul, uh);
-    // the first slot's coefficient is 1 (every row of Bd has one) unless its slice is outside the volume (then 0)
-    if (c[0] != 0.f) {
-#pragma unroll
-        for (int i = 0; i < kDwNPF; ++i) { lo[i] = ul[i]; hi[i] = uh[i]; }
-    } else {
+    // the first slot's coefficient is 1 (every row of Bd has one): its unit IS the running combination — unless its slice is outside
+    // the volume (t = 5 of the last depth tile), then 0.  A branch (the empty asm keeps it one): as a select it is 12 moves to zero
+    // and 12 moves back in every stage.
+    dw_activate<IDENT, CLAMP>(set0.pre, ssw, a.x_relu, lo, hi);
+    if (c[0] == 0.f) {
+        asm volatile("");
 #pragma unroll
         for (int i = 0; i < kDwNPF; ++i) { lo[i] = f32x2{0.f, 0.f}; hi[i] = f32x2{0.f, 0.f}; }
     }
-    d4_issue(a, P, nx && P.has_next, d4_j(tnx, 0), cbne, set0);
+    if constexpr (PAIR) {                                    // the partner's first slot is the same slice with the same coefficient
+#pragma unroll
+        for (int i = 0; i < kDwNPF; ++i) { kp.lo[i] = lo[i]; kp.hi[i] = hi[i]; }
+    }
+    if (refill) d4_issue(a, P, nx && P.has_next, d4_j(tnx, 0), cbne, set0);
     dw_activate<IDENT, CLAMP>(set1.pre, ssw, a.x_relu, ul, uh);
-    {
-        const f32x2 c1 = {c[1], c[1]};
-#pragma unroll
-        for (int i = 0; i < kDwNPF; ++i) { lo[i] = __builtin_elementwise_fma(ul[i], c1, lo[i]); hi[i] = __builtin_elementwise_fma(uh[i], c1, hi[i]); }
-    }
-    d4_issue(a, P, nx && P.has_next, d4_j(tnx, 1), cbne, set1);
+    d4_chain<PAIR>(ul, uh, c[1], cp[1], lo, hi, kp);
+    if (refill) d4_issue(a, P, nx && P.has_next, d4_j(tnx, 1), cbne, set1);
     dw_activate<IDENT, CLAMP>(set2.pre, ssw, a.x_relu, ul, uh);
-    {
-        const f32x2 c2 = {c[2], c[2]};
-#pragma unroll
-        for (int i = 0; i < kDwNPF; ++i) { lo[i] = __builtin_elementwise_fma(ul[i], c2, lo[i]); hi[i] = __builtin_elementwise_fma(uh[i], c2, hi[i]); }
-    }
-    d4_issue(a, P, nx && P.has_next, d4_j(tnx, 2), cbne, set2);
+    d4_chain<PAIR>(ul, uh, c[2], cp[2], lo, hi, kp);
+    if (refill) d4_issue(a, P, nx && P.has_next, d4_j(tnx, 2), cbne, set2);
     if (nsl > 3) {
         dw_activate<IDENT, CLAMP>(set3.pre, ssw, a.x_relu, ul, uh);
-        const f32x2 c3 = {c[3], c[3]};
-#pragma unroll
-        for (int i = 0; i < kDwNPF; ++i) { lo[i] = __builtin_elementwise_fma(ul[i], c3, lo[i]); hi[i] = __builtin_elementwise_fma(uh[i], c3, hi[i]); }
+        d4_chain<PAIR>(ul, uh, c[3], cp[3], lo, hi, kp);
     }
-    if (nsn > 3) d4_issue(a, P, nx && P.has_next, d4_j(tnx, 3), cbne, set3);
+    if (refill && nsn > 3) d4_issue(a, P, nx && P.has_next, d4_j(tnx, 3), cbne, set3);
+    d4_mask(P, lo, hi);
+#pragma unroll
+    for (int i = 0; i < kDwNPF; ++i) *reinterpret_cast<f32x4*>(raw + P.p.wr_off[i]) = __builtin_shufflevector(lo[i], hi[i], 0, 1, 2, 3);
+}
+
+// A stage of t = 2 or t = 4 (position p = 1 or 3) when the kept sets are in use: no load, no activation, no combination — the
+// words its partner stage left in `kp`, the plane-padding mask, the strip.  The register sets are idle through such a phase, so
+// its stages request, spread over themselves, the units of the NEXT LOADING stage — the first of phase p + 1, same tile: slot k
+// goes out in the stage at position 4 cbi / ncb <= k < 4 (cbi + 1) / ncb (one per stage at four channel blocks, two at two, all
+// four at one), each between two strip writes.  Nothing reads a set between the partner phase's last stage and that stage.
+__device__ __forceinline__ void d4_restore(const WinoPcArgs& a, const DwProd& P, int ncb, int p, int cbi, const D4Keep& kp, D4Regs& set0,
+                                           D4Regs& set1, D4Regs& set2, D4Regs& set3) {
+    float* raw = P.strip(P.gi & 1);
+    const int tnx = d4_t(p + 1), cbne = 0, nsn = d4_nslot(tnx);          // p + 1 is even: its sweep starts at block 0
+    const int k0 = 4 * cbi / ncb, k1 = 4 * (cbi + 1) / ncb;
+    f32x2 lo[kDwNPF], hi[kDwNPF];
+#pragma unroll
+    for (int i = 0; i < kDwNPF; ++i) { lo[i] = kp.lo[i]; hi[i] = kp.hi[i]; }
+    d4_mask(P, lo, hi);
+    if (k0 <= 0 && 0 < k1) d4_issue(a, P, false, d4_j(tnx, 0), cbne, set0);
+    *reinterpret_cast<f32x4*>(raw + P.p.wr_off[0]) = __builtin_shufflevector(lo[0], hi[0], 0, 1, 2, 3);
+    if (k0 <= 1 && 1 < k1) d4_issue(a, P, false, d4_j(tnx, 1), cbne, set1);
+    *reinterpret_cast<f32x4*>(raw + P.p.wr_off[1]) = __builtin_shufflevector(lo[1], hi[1], 0, 1, 2, 3);
+    if (k0 <= 2 && 2 < k1) d4_issue(a, P, false, d4_j(tnx, 2), cbne, set2);
+    *reinterpret_cast<f32x4*>(raw + P.p.wr_off[2]) = __builtin_shufflevector(lo[2], hi[2], 0, 1, 2, 3);
+    if (k0 <= 3 && 3 < k1 && nsn > 3) d4_issue(a, P, false, d4_j(tnx, 3), cbne, set3);
+}
+
+// The kept set of a stage's channel block is picked by a uniform branch, one marker (an empty asm statement) per set: the four
+// branches stay branches on registers of their own.  Merged by the compiler they become a dynamically indexed array, which lives in
+// scratch memory; as selects they cost 36 instructions a stage.  (The two phases written out stage by stage in straight-line code
+// — every set named at compile time — spilled: 156 to 436 bytes of scratch.)
+template <int SET>
+__device__ __forceinline__ void d4_keep(D4Keep& k, const D4Keep& v) {
 #pragma unroll
     for (int i = 0; i < kDwNPF; ++i) {
-        if (!P.interior) {
-            const f32x2 kk = {P.cur.keep[i], P.cur.keep[i]};
-            lo[i] = lo[i] * kk; hi[i] = hi[i] * kk;
-        }
-        *reinterpret_cast<f32x4*>(raw + P.p.wr_off[i]) = __builtin_shufflevector(lo[i], hi[i], 0, 1, 2, 3);
+        asm volatile("v_mov_b64 %0, %1 ; keep set %2" : "+v"(k.lo[i]) : "v"(v.lo[i]), "n"(SET));
+        asm volatile("v_mov_b64 %0, %1 ; keep set %2" : "+v"(k.hi[i]) : "v"(v.hi[i]), "n"(SET));
+    }
+}
+template <int SET>
+__device__ __forceinline__ void d4_restore_set(const WinoPcArgs& a, const DwProd& P, int ncb, int p, int cbi, const D4Keep& k, D4Regs& set0,
+                                               D4Regs& set1, D4Regs& set2, D4Regs& set3) {
+    asm volatile("; kept set %0" ::"n"(SET));
+    d4_restore(a, P, ncb, p, cbi, k, set0, set1, set2, set3);
+    asm volatile("; kept set %0 written" ::"n"(SET));
+}
+
+// the tile's stage (p, cbi); pair: the kept sets are in use
+template <bool IDENT, bool CLAMP>
+__device__ __forceinline__ void d4_stage(const WinoPcArgs& a, const DwProd& P, bool pair, int NS, int ncb, int s, int p, int cbi, D4Regs& set0,
+                                         D4Regs& set1, D4Regs& set2, D4Regs& set3, D4Keep& k0, D4Keep& k1, D4Keep& k2, D4Keep& k3) {
+    const int cb = dw_cb(p, cbi, ncb);
+    D4Keep kp;
+    if (!pair || p >= 4) {
+        d4_combine<IDENT, CLAMP, false>(a, P, NS, ncb, s, p, cbi, set0, set1, set2, set3, kp);
+    } else if (!(p & 1)) {
+        d4_combine<IDENT, CLAMP, true>(a, P, NS, ncb, s, p, cbi, set0, set1, set2, set3, kp);
+        if (cb == 0) d4_keep<0>(k0, kp);
+        else if (cb == 1) d4_keep<1>(k1, kp);
+        else if (cb == 2) d4_keep<2>(k2, kp);
+        else d4_keep<3>(k3, kp);
+    } else {
+        if (cb == 0) d4_restore_set<0>(a, P, ncb, p, cbi, k0, set0, set1, set2, set3);
+        else if (cb == 1) d4_restore_set<1>(a, P, ncb, p, cbi, k1, set0, set1, set2, set3);
+        else if (cb == 2) d4_restore_set<2>(a, P, ncb, p, cbi, k2, set0, set1, set2, set3);
+        else d4_restore_set<3>(a, P, ncb, p, cbi, k3, set0, set1, set2, set3);
     }
 }
 
@@ -274,12 +375,16 @@ __global__ __launch_bounds__(512) void conv_wino_dw4_kernel(const WinoD4Args aa)
             d4_issue(a, P, false, d4_j(t0, 2), cb0, set2);
             d4_issue(a, P, false, d4_j(t0, 3 < d4_nslot(t0) ? 3 : 0), cb0, set3);
         }
+        // up to four channel blocks (Cin <= 64: every K-Net layer) pair t = 1 with 2 and t = 3 with 4; a wider input loads every
+        // phase's units afresh, as t = 0 and t = 5 always do
+        const bool pair = ncb <= 4;
+        D4Keep k0 = {}, k1 = {}, k2 = {}, k3 = {};     // one kept combination per channel block in flight (t = 1 -> 2, t = 3 -> 4)
         for (int it = 0; it < count; ++it) {
             dw_tile_begin(a, P, it + 1 < count);
             int cbi = 0, p = 0;
             for (int s = 0; s < NS; ++s) {
                 if (s == NS - 1 && P.has_next) dw_next_tile<4, false>(a, P, first + (it + 1) * step);
-                d4_combine<IDENT, CLAMP>(a, P, NS, ncb, s, p, cbi, set0, set1, set2, set3);
+                d4_stage<IDENT, CLAMP>(a, P, pair, NS, ncb, s, p, cbi, set0, set1, set2, set3, k0, k1, k2, k3);
                 if (P.gi > 0) dw_transform(P.p, P.strip((P.gi & 1) ^ 1), Vb + P.qbuf * kPcV);   // the stage published one iteration ago
                 __syncthreads();
                 dw_stage_end(P);
