@@ -61,7 +61,8 @@ extern "C" {
  * The same holds for nrgbd_frame_ingest_u8 and nrgbd_window_gather (the video stream's frame ingest and window assembly), and for
  * nrgbd_depth_ingest_u16 (the training stream's depth-label ingest).  0.10 also gained the on-device depth evaluation —
  * nrgbd_depth_eval_workgroups, nrgbd_depth_eval_workspace and nrgbd_depth_eval; no existing entry changed, the version string stays.
- * The same holds for nrgbd_dgf_refine_f32 (the guided-filter refinement net). */
+ * The same holds for nrgbd_dgf_refine_f32 (the guided-filter refinement net), and for the TSDF fusion entries
+ * nrgbd_tsdf_integrate_f32, nrgbd_tsdf_extract_workspace and nrgbd_tsdf_extract_points. */
 #define NRGBD_INTERFACE_VERSION "0.10"
 const char* nrgbd_version(void);
 const char* nrgbd_strerror(int code);
@@ -952,6 +953,63 @@ int nrgbd_depth_eval(const float* depth, const float* logconf, const float* gt, 
 int nrgbd_dgf_refine_f32(const float* depth_lr, int n, int h, int w, const float* img, int H, int W,
                          const float* w1, const float* b1, const float* w2, const float* b2, float eps,
                          float* out, void* stream);
+/*
+ * TSDF fusion (tsdf.hip; neuralrgbd_amd/fusion.py: TSDFVolume, FusionVideoStream): the depth maps of a trajectory accumulated in
+ * the world frame as a dense truncated-signed-distance volume on the device, and the volume's surface as points.  None of the
+ * three entries has a counterpart in the reference, which drops every map after export; the conventions are the ones written here.
+ * Everything is fp32, every operation below is ONE IEEE fp32 operation in the order written (no fused multiply-add, no reciprocal),
+ * there are no atomics, and the same inputs give the same bits in every run.
+ *
+ * The volume: two planar device arrays tsdf [Z][Y][X] and weight [Z][Y][X], X fastest; lattice point (ix, iy, iz) lies at the world
+ * position origin + voxel_size (ix, iy, iz); a fresh volume is tsdf = 0, weight = 0.
+ *
+ * nrgbd_tsdf_integrate_f32 — no counterpart in the reference: one depth frame into the volume, one launch, capturable.
+ *   depth        device fp32 [H][W]: z-depth in metres (rays have z = 1, the convention of unit_ray_array)
+ *   gate         device fp32 [H][W] or NULL: a pixel counts where gate >= gate_thr (a NaN fails); e.g. max_k logp against log c
+ *   wmap         device fp32 [H][W] or NULL (= 1): the weight of a pixel's observation
+ *   pose         HOST fp32 [12], read at the call: float32(extM[:3,:4]) row-major, world -> camera (r00 r01 r02 tx | r10 ...)
+ *   fx fy cx cy  the pinhole intrinsics at the depth map's size; pixel x covers [x, x + 1) (centres at + 0.5)
+ *   box          HOST int [6] = x0, y0, z0, x1, y1, z1, a half-open voxel box, read at the call, or NULL = the whole grid
+ *   per voxel of the box, with T, Wt its two stored values:
+ *     xw = ox + vs * (float)ix                              (likewise yw, zw)
+ *     xc = ((r00 * xw + r01 * yw) + r02 * zw) + tx          (likewise yc, zc with rows 1 and 2)
+ *     skip unless zc > 0
+ *     u = fx * (xc / zc) + cx;  v = fy * (yc / zc) + cy
+ *     skip unless u >= 0 && u < (float)W && v >= 0 && v < (float)H       (a NaN fails)
+ *     iu = (int)floorf(u);  iv = (int)floorf(v);  d = depth[iv][iu];  skip unless d is finite, d > d_near, d <= d_far
+ *     skip unless gate[iv][iu] >= gate_thr  (when given);   w = wmap ? wmap[iv][iu] : 1;  skip unless w is finite and w > 0
+ *     s = d - zc;  skip if s < -trunc;  t = fminf(1, s / trunc)
+ *     T' = (T * Wt + t * w) / (Wt + w);  W' = fminf(Wt + w, w_max)
+ *   A skipped voxel keeps its bits.  Four x-neighbours per lane with 16-byte loads and stores when X % 4 == 0 and both arrays are
+ *   16-byte aligned, one voxel per lane otherwise: the same bits.
+ *   errors       NRGBD_E_NULL: tsdf, weight, depth or pose NULL;  NRGBD_E_SHAPE: a dimension <= 0, X Y Z > 2^31, a box that leaves
+ *                the grid or is empty;  NRGBD_E_ARG: voxel_size, trunc or w_max <= 0 or not finite, d_near < d_far not true (a NaN
+ *                bound included).  Checked in this order, before anything touches the device.
+ * nrgbd_tsdf_extract_workspace — no counterpart in the reference: the bytes nrgbd_tsdf_extract_points needs for an X Y Z grid
+ *   (16 per NRGBD_TSDF_EXTRACT_VOXELS voxels; needs no GPU); NRGBD_E_SHAPE as above.
+ * nrgbd_tsdf_extract_points — no counterpart in the reference: the volume's zero crossings as points, three launches (per-workgroup
+ *   counts; a one-workgroup exclusive scan in index order, NRGBD_TSDF_SCAN_PASS records per pass; re-evaluate and write at offset +
+ *   rank), no atomics.  Between a = (ix, iy, iz) and b = a + e_k (k = x, y, z; b inside the grid) there is a crossing iff
+ *     W_a >= w_min && W_b >= w_min  &&  fabsf(T_a) < 1 && fabsf(T_b) < 1  &&  (T_a < 0) != (T_b < 0)        (a NaN fails)
+ *   at q = T_a / (T_a - T_b): coordinate k of the point is o_k + vs * ((float)i_k + q), the other two are o + vs * (float)i.
+ *   points       device fp32 [capacity][3]: the first min(found, capacity) crossings in ascending (linear voxel index, axis) order;
+ *                nothing behind them is written.  May be NULL when capacity is 0 (the third launch is left out).
+ *   counts       device int64 [2] = crossings found, points written
+ *   workspace    8-byte aligned, at least nrgbd_tsdf_extract_workspace(X, Y, Z) bytes; rewritten by every call
+ *   errors       NRGBD_E_NULL: a NULL pointer (points only when capacity > 0);  NRGBD_E_SHAPE: the grid as above, capacity < 0, a
+ *                workspace that is too small;  NRGBD_E_ARG: voxel_size <= 0 or not finite, a NaN w_min;  NRGBD_E_ALIGN: workspace or
+ *                counts.  Checked in this order, before anything touches the device.
+ */
+#define NRGBD_TSDF_EXTRACT_VOXELS 1024
+#define NRGBD_TSDF_SCAN_PASS 1024
+int nrgbd_tsdf_integrate_f32(float* tsdf, float* weight, int X, int Y, int Z, float ox, float oy, float oz, float voxel_size,
+                             const float* depth, const float* gate, float gate_thr, const float* wmap, int H, int W,
+                             const float* pose, float fx, float fy, float cx, float cy, float trunc, float d_near, float d_far,
+                             float w_max, const int* box, void* stream);
+long nrgbd_tsdf_extract_workspace(int X, int Y, int Z);
+int nrgbd_tsdf_extract_points(const float* tsdf, const float* weight, int X, int Y, int Z, float ox, float oy, float oz,
+                              float voxel_size, float w_min, void* workspace, long workspace_bytes, float* points, long capacity,
+                              long long* counts, void* stream);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,7 @@ Drop-in surface (reference file it replaces):
                                     digitising (mdataloader/scanNet.py:372-422) on the device
     neuralrgbd_amd.evaluate         code/test_utils/export_res.py:108-116 and the offline scoring behind it: error metrics of the depth maps
                                     against ground truth, per confidence set, as running totals on the device
+    neuralrgbd_amd.fusion           (no counterpart) TSDF fusion of the depth stream into a voxel volume on the device, surface points
     neuralrgbd_amd.camera           the cam_intrinsics dict of code/mdataloader/scanNet.py:204-272
 The compute between the convolutions is hand-written HIP behind the C-ABI of include/nrgbd.h
 (libnrgbd_hip.so, built by `python -m neuralrgbd_amd.build`).
@@ -32,7 +33,7 @@ from . import camera, synth  # host-only helpers (numpy / torch CPU)
 def __getattr__(name):
     # the GPU-facing modules load libnrgbd_hip.so; import them lazily so that host-only tooling
     # (camera, synth, build) works before the library is built
-    if name in ("ops", "homography", "kvnet", "nets", "misc", "test_step", "lba_step", "video", "train_video", "evaluate", "_lib"):
+    if name in ("ops", "homography", "kvnet", "nets", "misc", "test_step", "lba_step", "video", "train_video", "evaluate", "fusion", "_lib"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "KVNET":
@@ -47,4 +48,7 @@ def __getattr__(name):
     if name in ("DepthMetrics", "EvalVideoStream", "evaluate_sequence", "metrics_from_record"):
         from . import evaluate
         return getattr(evaluate, name)
+    if name in ("TSDFVolume", "FusionVideoStream", "fuse_sequence", "frustum_box", "intrinsics_at", "save_ply"):
+        from . import fusion
+        return getattr(fusion, name)
     raise AttributeError(name)

@@ -21,6 +21,8 @@ GATHER_MAX_V = 6        # NRGBD_GATHER_MAX_V
 DEPTH_MAX_THRESHOLDS = 512      # NRGBD_DEPTH_MAX_THRESHOLDS
 DEPTH_EVAL_MAX_SETS = 8         # NRGBD_DEPTH_EVAL_MAX_SETS
 DGF_TILE = (16, 64)             # NRGBD_DGF_TILE_Y, NRGBD_DGF_TILE_X
+TSDF_EXTRACT_VOXELS = 1024      # NRGBD_TSDF_EXTRACT_VOXELS
+TSDF_SCAN_PASS = 1024           # NRGBD_TSDF_SCAN_PASS
 
 
 class WindowSlots(ctypes.Structure):
@@ -133,6 +135,9 @@ SIGNATURES = {
     "nrgbd_depth_eval_workspace": (_L, [_L, _I]),
     "nrgbd_depth_eval": (_I, [_P, _P, _P, _L, _F, _F, _P, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P]),
     "nrgbd_dgf_refine_f32": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _F, _P, _P]),
+    "nrgbd_tsdf_integrate_f32": (_I, [_P, _P, _I, _I, _I, _F, _F, _F, _F, _P, _P, _F, _P, _I, _I, _P, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P]),
+    "nrgbd_tsdf_extract_workspace": (_L, [_I, _I, _I]),
+    "nrgbd_tsdf_extract_points": (_I, [_P, _P, _I, _I, _I, _F, _F, _F, _F, _F, _P, _L, _P, _L, _P, _P]),
     "nrgbd_nhwc_stats_workgroups": (_I, [_L]),
     "nrgbd_nhwc_stats": (_I, [_P, _L, _I, _P, _P]),
     "nrgbd_nhwc_act": (_I, [_P, _P, _I, _P, _P, _I, _P, _L, _I, _I, _P]),

@@ -1,0 +1,257 @@
+"""On-device TSDF fusion: the depth and confidence maps of a trajectory accumulated in the world frame.
+
+The reference stops at the maps (test_utils/export_res.py writes them to files); nothing in it accumulates them.  Here a depth frame
+costs one launch (ops.tsdf_integrate) that updates a dense truncated-signed-distance volume on the device, and the surface is read out
+as points by a deterministic compaction (ops.tsdf_extract_points): fp32 throughout, no atomics, the same bits in every run.  The
+conventions (lattice, projection, update rule, crossings) are written out in include/nrgbd.h.
+
+  * `TSDFVolume`: the volume, `integrate` (one launch, nothing allocated, nothing synchronised) and `points`;
+  * `frustum_box`: the voxel box a camera can touch, in float64 on the host — `integrate(cull=True)` launches over it alone;
+  * `FusionVideoStream`: a video.VideoDepthStream that integrates the map of every frame that comes out, with the extrinsic that was
+    pushed with that frame;
+  * `fuse_sequence`, `save_ply`.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import misc, ops
+from . import homography as warp_homo
+from .evaluate import GtRing
+from .video import VideoDepthStream
+
+
+def intrinsics_at(cam_intrinsics, H, W):
+    """(fx, fy, cx, cy) of an H x W map from the dict's fields of view, as camera.make_cam_intrinsics forms them (the principal point at
+    the centre; pixel x covers [x, x + 1))."""
+    fx = (W / 2.0) / math.tan(math.radians(cam_intrinsics["hfov"] / 2.0))
+    fy = (H / 2.0) / math.tan(math.radians(cam_intrinsics["vfov"] / 2.0))
+    return fx, fy, W / 2.0, H / 2.0
+
+
+def _indexed(device):
+    """(type, index) of a device, "cuda" without an index standing for the current one."""
+    d = torch.device(device)
+    return d.type, (torch.cuda.current_device() if d.type == "cuda" and d.index is None else d.index)
+
+
+def _host_matrix(extM, who):
+    if isinstance(extM, torch.Tensor):
+        extM = extM.detach().cpu().numpy()
+    m = np.asarray(extM, dtype=np.float64)
+    if m.shape not in ((3, 4), (4, 4)):
+        raise ValueError("%s: extM is a [3,4] or [4,4] world-to-camera matrix, got %s" % (who, m.shape))
+    return m
+
+
+def frustum_box(extM, intrinsics, size, depth_max, volume):
+    """The half-open voxel box (x0, y0, z0, x1, y1, z1) of `volume` that a camera at extM (world -> camera) can touch out to z-depth
+    `depth_max` (d_far + trunc): the index box of the camera centre and of the four corners of the pixel rectangle [0, W] x [0, H] at
+    that depth — the convex hull of every lattice point the kernel can update —, widened by one voxel and clipped to the grid.  float64
+    on the host.  None when the clipped box is empty (or the pose is not finite): nothing to launch; the whole grid when depth_max is
+    infinite."""
+    dims = volume.dims
+    m = _host_matrix(extM, "frustum_box")
+    if not math.isfinite(float(m.sum())) or math.isnan(depth_max):  # a NaN or infinite entry makes the sum NaN or infinite
+        return None
+    if math.isinf(depth_max):
+        return (0, 0, 0) + tuple(dims)
+    fx, fy, cx, cy = (float(k) for k in intrinsics)
+    H, W = size
+    x0, x1, y0, y1 = -cx / fx * depth_max, (W - cx) / fx * depth_max, -cy / fy * depth_max, (H - cy) / fy * depth_max
+    cam = np.array([[0.0, 0.0, 0.0], [x0, y0, depth_max], [x0, y1, depth_max], [x1, y0, depth_max], [x1, y1, depth_max]])
+    try:
+        world = np.linalg.solve(m[:3, :3], (cam - m[:3, 3]).T).tolist()      # [3][5]: one solve for the five points
+    except np.linalg.LinAlgError:                                   # not a rigid motion: nothing to cull by
+        return (0, 0, 0) + tuple(dims)
+    lo_hi = []
+    for k in range(3):
+        a = [(x - volume.origin[k]) / volume.voxel_size for x in world[k]]
+        lo, hi = min(a), max(a)
+        if not (math.isfinite(lo) and math.isfinite(hi)):
+            return (0, 0, 0) + tuple(dims)
+        lo = max(int(math.floor(lo)) - 1, 0)
+        hi = min(int(math.ceil(hi)) + 2, dims[k])                   # half-open: the last index + 1, + 1 for the margin
+        if lo >= hi:
+            return None
+        lo_hi.append((lo, hi))
+    return tuple(v[0] for v in lo_hi) + tuple(v[1] for v in lo_hi)
+
+
+class TSDFVolume:
+    """A dense TSDF volume on the device: `tsdf` and `weight`, fp32 [Z,Y,X]; lattice point (ix, iy, iz) lies at
+    origin + voxel_size (ix, iy, iz)."""
+
+    def __init__(self, dims, voxel_size, origin, trunc=None, w_max=64., device=None):
+        self.dims = tuple(int(n) for n in dims)
+        if len(self.dims) != 3 or min(self.dims) <= 0 or self.dims[0] * self.dims[1] * self.dims[2] > 2 ** 31:
+            raise ValueError("TSDFVolume: dims = (X, Y, Z), positive, at most 2^31 voxels; got %s" % (dims,))
+        self.voxel_size = float(voxel_size)
+        self.origin = tuple(float(o) for o in origin)
+        self.trunc = 3.0 * self.voxel_size if trunc is None else float(trunc)
+        self.w_max = float(w_max)
+        if len(self.origin) != 3 or not all(math.isfinite(o) for o in self.origin):
+            raise ValueError("TSDFVolume: origin takes three finite values, got %s" % (origin,))
+        for v, nm in ((self.voxel_size, "voxel_size"), (self.trunc, "trunc"), (self.w_max, "w_max")):
+            if not (v > 0 and math.isfinite(v)):
+                raise ValueError("TSDFVolume: %s must be positive and finite, got %s" % (nm, v))
+        X, Y, Z = self.dims
+        self._buf = torch.zeros((2, Z, Y, X), dtype=torch.float32, device=torch.device(device if device is not None else "cuda"))
+        self.device = self._buf.device                              # with its index: "cuda" names the current device
+        self.tsdf, self.weight = self._buf[0], self._buf[1]
+        self._counts = torch.zeros(2, dtype=torch.int64, device=self.device)
+        self._workspace = None
+
+    def reset(self):
+        """An empty volume again (asynchronous)."""
+        self._buf.zero_()
+
+    def integrate(self, depth, extM, intrinsics, gate=None, gate_thr=None, weight=None, depth_range=(0., float("inf")), cull=True):
+        """One depth frame: depth [H,W] (or [1,H,W]) CUDA fp32 z-depth in metres; extM: the host [4,4] world -> camera matrix
+        (VideoDepthStream.push's), used as float32(extM[:3,:4]); intrinsics: (fx, fy, cx, cy) at the map's size, or a cam_intrinsics
+        dict (intrinsics_at); gate / gate_thr: a pixel counts where gate >= gate_thr; weight: a per-pixel weight map (default 1);
+        depth_range = (d_near, d_far]; cull: launch over frustum_box alone (the same bits).  Returns False when the box is empty and
+        nothing was launched.  Allocates nothing and synchronises nothing."""
+        if depth.dim() == 3 and depth.shape[0] == 1:
+            depth = depth[0]
+            gate = gate if gate is None else gate.view(depth.shape)
+            weight = weight if weight is None else weight.view(depth.shape)
+        if depth.dim() != 2:
+            raise ValueError("TSDFVolume.integrate: depth is [H,W], got %s" % (tuple(depth.shape),))
+        H, W = depth.shape
+        if isinstance(intrinsics, dict):
+            intrinsics = intrinsics_at(intrinsics, H, W)
+        if (gate is None) != (gate_thr is None):
+            raise ValueError("TSDFVolume.integrate: gate and gate_thr come together")
+        m = _host_matrix(extM, "TSDFVolume.integrate")
+        box = None
+        if cull:
+            box = frustum_box(m, intrinsics, (H, W), float(depth_range[1]) + self.trunc, self)
+            if box is None:
+                return False
+        ops.tsdf_integrate(self.tsdf, self.weight, self.origin, self.voxel_size, depth, m, intrinsics, self.trunc, depth_range, self.w_max,
+                           gate=gate, gate_thr=0.0 if gate_thr is None else gate_thr, wmap=weight, box=box)
+        return True
+
+    def points(self, w_min=1., capacity=None):
+        """The zero crossings between lattice neighbours whose weights are >= w_min, as ([n,3] CUDA fp32 world points in ascending
+        (linear voxel index, axis) order, crossings found).  capacity=None: counts first, then writes every point; else the first
+        min(found, capacity).  Reads the count back: the one place this object synchronises (and allocates)."""
+        if self._workspace is None:
+            self._workspace = torch.empty(ops.tsdf_extract_workspace(*self.dims) // 8, dtype=torch.int64, device=self.device)
+        args = (self.tsdf, self.weight, self.origin, self.voxel_size, w_min, self._workspace)
+        if capacity is None:
+            ops.tsdf_extract_points(*args, None, self._counts)
+            capacity = int(self._counts[0].item())
+        capacity = int(capacity)
+        if capacity < 0:
+            raise ValueError("TSDFVolume.points: capacity %d" % capacity)
+        out = torch.empty((capacity, 3), dtype=torch.float32, device=self.device)
+        ops.tsdf_extract_points(*args, out if capacity else None, self._counts)
+        found, written = (int(v) for v in self._counts.cpu())
+        return out[:written], found
+
+
+class FusionVideoStream(VideoDepthStream):
+    """VideoDepthStream + a TSDFVolume: push(frame, extM) returns what VideoDepthStream.push returns, and every depth frame that comes
+    out is integrated into `volume` with the extrinsic pushed with its reference frame — one depth-regression launch and one
+    integration launch on the caller's HIP stream after the frame (eager: not part of the captured graph).
+    source: 'refined' (the R-Net volume at the network size) or 'dpv' (the K-Net volume at the plane-sweep grid);
+    conf_threshold c: only pixels with max_k logp >= float32(log c) count (evaluate.log_thresholds' gate);
+    weight: 'uniform' (1 per observation) or 'conf' (exp(max_k logp), from ops.export_depth_u16).
+    The R-Net's volume is read where it lies (its channels-last view) when the candidates fill the kernels' candidate width (64 or
+    128 candidates, 256 with if_upsample_d); another count runs zero-padded to that width, the view is then a slice of the padded
+    pixels and ops.depth_regress makes a planar copy of it first."""
+
+    def __init__(self, model, cam_intrinsics, d_candi, volume, t_win_r=2, source="refined", conf_threshold=0., weight="uniform",
+                 depth_range=None, **video_kwargs):
+        from .nets import require_volume_refiner
+        require_volume_refiner(model, "FusionVideoStream")
+        if source not in ("refined", "dpv"):
+            raise ValueError("FusionVideoStream: source is 'refined' or 'dpv', got %r" % (source,))
+        if weight not in ("uniform", "conf"):
+            raise ValueError("FusionVideoStream: weight is 'uniform' or 'conf', got %r" % (weight,))
+        c = float(conf_threshold)
+        if not 0 <= c < 1:
+            raise ValueError("FusionVideoStream: conf_threshold %s is not in [0, 1)" % (conf_threshold,))
+        self.volume = volume
+        self.source, self.weight_mode, self.conf_threshold = source, weight, c
+        self.gate_thr = None if c == 0 else float(np.log(np.float64(c)).astype(np.float32))      # the log in double, rounded once
+        self.depth_range = (0., float("inf")) if depth_range is None else (float(depth_range[0]), float(depth_range[1]))
+        self.cam, self.d_candi = cam_intrinsics, d_candi
+        self.n_slots = 2 * t_win_r + 2
+        self.ext_ring = GtRing(self.n_slots)                    # which push's extrinsic a slot holds: evaluate.GtRing's pairing
+        self._ext = [None] * self.n_slots
+        self.n_integrated = 0
+        super().__init__(model, cam_intrinsics, d_candi, t_win_r=t_win_r, **video_kwargs)
+        if _indexed(volume.device) != _indexed(self.device):
+            raise ValueError("FusionVideoStream: the volume is on %s, the stream on %s" % (volume.device, self.device))
+
+    def reset(self):
+        """New trajectory: drops the frames, the filter state and the extrinsic ring; the volume stays (volume.reset() empties it)."""
+        super().reset()
+        self.ext_ring.clear()
+        self._ext = [None] * self.n_slots
+
+    def _fuse(self, out):
+        if out is None:
+            return out
+        ref_index, refined, dpv = out
+        slot = self.ext_ring.lookup(ref_index)
+        if slot is None:                                        # a NaN pose: its windows produce no maps, so this does not happen
+            return out
+        vol = (refined if self.source == "refined" else dpv)[0]
+        D = vol.shape[0]
+        d_candi = self.d_candi
+        if D == 4 * len(d_candi):
+            d_candi = misc.d_candi_up4(d_candi)
+        elif D != len(d_candi):
+            raise ValueError("FusionVideoStream: a volume of %d planes over %d candidates" % (D, len(d_candi)))
+        d_dev = warp_homo._d_candi_dev(d_candi, vol.device)
+        cl = ops.is_channels_last_view(vol)
+        depth, logconf = ops.depth_regress(vol, d_dev, channels_last=cl)
+        wmap = ops.export_depth_u16(vol, d_dev, channels_last=cl)[1] if self.weight_mode == "conf" else None
+        gate = None if self.gate_thr is None else logconf
+        if self.volume.integrate(depth, self._ext[slot], self.cam, gate=gate, gate_thr=self.gate_thr, weight=wmap,
+                                 depth_range=self.depth_range):
+            self.n_integrated += 1
+        return out
+
+    def push(self, frame, extM):
+        """As VideoDepthStream.push; the maps that come out (of frame ref_index) are integrated before they are returned."""
+        ext = self._extrinsic(extM)
+        index = self.n_pushed
+        out = super().push(frame, extM)                         # raises before anything is counted
+        valid = bool(np.all(np.isfinite(ext)))
+        slot = self.ext_ring.store(index, valid)
+        self._ext[slot] = ext if valid else None
+        return self._fuse(out)
+
+    def flush(self):
+        """pipeline=True: the frame that is still owed, integrated like any other; None otherwise."""
+        return self._fuse(super().flush())
+
+
+def fuse_sequence(stream, frames, extMs):
+    """One trajectory through a FusionVideoStream: resets the stream's trajectory state (the volume keeps accumulating), pushes every
+    frame, flushes, and returns the number of depth frames integrated by this call."""
+    stream.reset()
+    before = stream.n_integrated
+    for frame, extM in zip(frames, extMs):
+        stream.push(frame, extM)
+    stream.flush()
+    stream.check()
+    return stream.n_integrated - before
+
+
+def save_ply(path, points):
+    """[n,3] points (a tensor on any device, or an array) as an ASCII PLY file, written on the host; %.9g round-trips fp32."""
+    if isinstance(points, torch.Tensor):
+        points = points.detach().cpu().numpy()
+    p = np.asarray(points, dtype=np.float32).reshape(-1, 3)
+    with open(path, "w") as f:
+        f.write("ply\nformat ascii 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\nend_header\n" % len(p))
+        for x, y, z in p:
+            f.write("%.9g %.9g %.9g\n" % (x, y, z))
+    return len(p)

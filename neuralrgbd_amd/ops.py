@@ -1635,3 +1635,105 @@ def dgf_refine(depth_lr, img, w1, b1, w2, b2, eps=1e-8, out=None):
                                               _stream(img))
     _lib.check(rc, "nrgbd_dgf_refine_f32")
     return out.view(n, 1, H, W)
+
+
+# ---- TSDF fusion (tsdf.hip; neuralrgbd_amd/fusion.py) ---------------------------------------------------------------------------
+
+def _tsdf_volume(tsdf, weight, who):
+    tsdf = _need(tsdf, "tsdf", strided=True)
+    if tsdf.dim() != 3 or not tsdf.is_contiguous():
+        raise ValueError("%s: tsdf must be a contiguous [Z,Y,X] tensor, got %s" % (who, tuple(tsdf.shape)))
+    weight = _need(weight, "weight", tuple(tsdf.shape), strided=True)
+    if weight.device != tsdf.device or not weight.is_contiguous():
+        raise ValueError("%s: weight must be contiguous and on %s" % (who, tsdf.device))
+    return tsdf, weight
+
+
+def _vec3(v, name):
+    v = tuple(float(x) for x in v)
+    if len(v) != 3:
+        raise ValueError("%s takes three values, got %d" % (name, len(v)))
+    return v
+
+
+def tsdf_integrate(tsdf, weight, origin, voxel_size, depth, pose, intrinsics, trunc, depth_range=(0.0, float("inf")), w_max=64.0,
+                   gate=None, gate_thr=0.0, wmap=None, box=None):
+    """One depth frame into a TSDF volume, in place, one launch (nrgbd_tsdf_integrate_f32; the per-voxel operation sequence is
+    written out in include/nrgbd.h).
+    tsdf / weight: contiguous CUDA fp32 [Z,Y,X]; origin: world position of lattice point (0,0,0); depth (and gate, wmap, or None):
+    contiguous CUDA fp32 [H,W] on the same device; pose: host [3,4] or [4,4] world -> camera, cast to float32; intrinsics =
+    (fx, fy, cx, cy) at the depth map's size; depth_range = (d_near, d_far]; box: a half-open voxel box (x0, y0, z0, x1, y1, z1) or
+    None for the whole grid.  Nothing is allocated, nothing synchronised."""
+    tsdf, weight = _tsdf_volume(tsdf, weight, "tsdf_integrate")
+    dev = tsdf.device
+    depth = _need(depth, "depth", strided=True)
+    if depth.dim() != 2:
+        raise ValueError("tsdf_integrate: depth must be [H,W], got %s" % (tuple(depth.shape),))
+    maps = []
+    for t, nm in ((depth, "depth"), (gate, "gate"), (wmap, "wmap")):
+        if t is not None:
+            t = _need(t, nm, tuple(depth.shape), strided=True)
+            if t.device != dev or not t.is_contiguous():
+                raise ValueError("tsdf_integrate: %s must be contiguous and on %s" % (nm, dev))
+        maps.append(t)
+    if isinstance(pose, torch.Tensor):
+        if pose.is_cuda:
+            raise ValueError("tsdf_integrate: pose is a host matrix (it is read at the call)")
+        pose = pose.detach().numpy()
+    pose = np.asarray(pose)
+    if pose.shape not in ((3, 4), (4, 4)):
+        raise ValueError("tsdf_integrate: pose is [3,4] or [4,4] world -> camera, got %s" % (pose.shape,))
+    pose = np.ascontiguousarray(pose[:3, :4], dtype=np.float32)
+    k = tuple(float(x) for x in intrinsics)
+    if len(k) != 4:
+        raise ValueError("tsdf_integrate: intrinsics = (fx, fy, cx, cy)")
+    o = _vec3(origin, "tsdf_integrate: origin")
+    cbox = None
+    if box is not None:
+        b = tuple(int(x) for x in box)
+        if len(b) != 6:
+            raise ValueError("tsdf_integrate: box = (x0, y0, z0, x1, y1, z1)")
+        cbox = (ctypes.c_int * 6)(*b)
+    Z, Y, X = tsdf.shape
+    H, W = depth.shape
+    with torch.cuda.device(dev):
+        rc = _lib.load().nrgbd_tsdf_integrate_f32(_p(tsdf), _p(weight), X, Y, Z, o[0], o[1], o[2], float(voxel_size), _p(maps[0]),
+                                                  _p(maps[1]), float(gate_thr), _p(maps[2]), H, W, ctypes.c_void_p(pose.ctypes.data),
+                                                  k[0], k[1], k[2], k[3], float(trunc), float(depth_range[0]), float(depth_range[1]),
+                                                  float(w_max), cbox, _stream(tsdf))
+    _lib.check(rc, "nrgbd_tsdf_integrate_f32")
+
+
+def tsdf_extract_workspace(X, Y, Z):
+    """Bytes of workspace nrgbd_tsdf_extract_points needs for an X x Y x Z grid (needs no GPU)."""
+    rc = _lib.load().nrgbd_tsdf_extract_workspace(int(X), int(Y), int(Z))
+    if rc < 0:
+        _lib.check(rc, "nrgbd_tsdf_extract_workspace")
+    return rc
+
+
+def tsdf_extract_points(tsdf, weight, origin, voxel_size, w_min, workspace, points, counts):
+    """The zero crossings of a TSDF volume as points (nrgbd_tsdf_extract_points: three launches, no atomics, ascending (linear voxel
+    index, axis) order).  workspace: a contiguous CUDA tensor of at least tsdf_extract_workspace(X, Y, Z) bytes; points: contiguous
+    CUDA fp32 [capacity,3] — the first min(found, capacity) rows are written — or None for a count alone; counts: CUDA int64 [2],
+    written (crossings found, points written).  Nothing is allocated, nothing synchronised."""
+    tsdf, weight = _tsdf_volume(tsdf, weight, "tsdf_extract_points")
+    dev = tsdf.device
+    if not isinstance(workspace, torch.Tensor) or workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError("tsdf_extract_points: workspace must be a contiguous tensor on %s" % (dev,))
+    if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int64 or counts.device != dev or not counts.is_contiguous()
+            or tuple(counts.shape) != (2,)):
+        raise ValueError("tsdf_extract_points: counts must be a contiguous int64 tensor [2] on %s" % (dev,))
+    capacity = 0
+    if points is not None:
+        points = _need(points, "points", strided=True)
+        if points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous() or points.device != dev:
+            raise ValueError("tsdf_extract_points: points must be a contiguous [capacity,3] tensor on %s" % (dev,))
+        capacity = points.shape[0]
+    o = _vec3(origin, "tsdf_extract_points: origin")
+    Z, Y, X = tsdf.shape
+    with torch.cuda.device(dev):
+        rc = _lib.load().nrgbd_tsdf_extract_points(_p(tsdf), _p(weight), X, Y, Z, o[0], o[1], o[2], float(voxel_size), float(w_min),
+                                                   _p(workspace), workspace.numel() * workspace.element_size(),
+                                                   _p(points if capacity else None), capacity, _p(counts), _stream(tsdf))
+    _lib.check(rc, "nrgbd_tsdf_extract_points")
