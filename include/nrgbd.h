@@ -62,7 +62,8 @@ extern "C" {
  * nrgbd_depth_ingest_u16 (the training stream's depth-label ingest).  0.10 also gained the on-device depth evaluation —
  * nrgbd_depth_eval_workgroups, nrgbd_depth_eval_workspace and nrgbd_depth_eval; no existing entry changed, the version string stays.
  * The same holds for nrgbd_dgf_refine_f32 (the guided-filter refinement net), and for the TSDF fusion entries
- * nrgbd_tsdf_integrate_f32, nrgbd_tsdf_extract_workspace and nrgbd_tsdf_extract_points. */
+ * nrgbd_tsdf_integrate_f32, nrgbd_tsdf_extract_workspace and nrgbd_tsdf_extract_points, and for nrgbd_tsdf_raycast_f32 (the fused
+ * volume rendered to depth and normals). */
 #define NRGBD_INTERFACE_VERSION "0.10"
 const char* nrgbd_version(void);
 const char* nrgbd_strerror(int code);
@@ -956,7 +957,7 @@ int nrgbd_dgf_refine_f32(const float* depth_lr, int n, int h, int w, const float
 /*
  * TSDF fusion (tsdf.hip; neuralrgbd_amd/fusion.py: TSDFVolume, FusionVideoStream): the depth maps of a trajectory accumulated in
  * the world frame as a dense truncated-signed-distance volume on the device, and the volume's surface as points.  None of the
- * three entries has a counterpart in the reference, which drops every map after export; the conventions are the ones written here.
+ * four entries has a counterpart in the reference, which drops every map after export; the conventions are the ones written here.
  * Everything is fp32, every operation below is ONE IEEE fp32 operation in the order written (no fused multiply-add, no reciprocal),
  * there are no atomics, and the same inputs give the same bits in every run.
  *
@@ -999,9 +1000,53 @@ int nrgbd_dgf_refine_f32(const float* depth_lr, int n, int h, int w, const float
  *   errors       NRGBD_E_NULL: a NULL pointer (points only when capacity > 0);  NRGBD_E_SHAPE: the grid as above, capacity < 0, a
  *                workspace that is too small;  NRGBD_E_ARG: voxel_size <= 0 or not finite, a NaN w_min;  NRGBD_E_ALIGN: workspace or
  *                counts.  Checked in this order, before anything touches the device.
+ * nrgbd_tsdf_raycast_f32 — no counterpart in the reference: the volume seen from a camera, one ray per pixel marched to the first
+ *   zero crossing of the trilinear interpolant; one launch, capturable, no atomics, no workspace; the volume is only read.
+ *   pose         HOST fp32 [12], read at the call: float32(extM[:3,:4]) row-major, world -> camera, as integrate takes it
+ *   centre       HOST fp32 [3], read at the call: the camera centre -R^T t in the world, formed in float64 on the host from the
+ *                float32 pose and rounded once
+ *   fx fy cx cy  the pinhole intrinsics at H x W; pixel x covers [x, x + 1)
+ *   d_near d_far the ray parameter (= z-depth: rays have z = 1) is searched in [d_near, d_far]
+ *   w_min        a sample counts where all eight corners of its cell have weight >= w_min
+ *   step         the distance between two samples along the ray, a world length in metres
+ *   depth        device fp32 [H][W], always written: z-depth of the crossing; 0 = no surface
+ *   normal       device fp32 [3][H][W] or NULL: the unit surface normal in the CAMERA frame (it points towards free space, at the
+ *                camera: its z is negative on a surface seen from the front); (0, 0, 0) where there is none
+ *   per pixel (py, px), with N = (X, Y, Z), o the origin, vs the voxel size, r the pose, a and k running over the axes x, y, z:
+ *     xn = (((float)px + 0.5) - cx) / fx;  yn = (((float)py + 0.5) - cy) / fy
+ *     d_k = (r0k * xn + r1k * yn) + r2k                       (the ray's world direction: column k of R)
+ *     len = sqrtf((dx * dx + dy * dy) + dz * dz);  dzs = step / len
+ *     go_k = (centre_k - o_k) / vs;  gd_k = d_k / vs           (voxel coordinates: the sample at ray parameter z is go + z gd)
+ *     z0 = d_near, z1 = d_far; then for k = x, y, z in turn (the slab of the interpolation domain [0, N_k - 1]):
+ *       gd_k != 0: ta = (0 - go_k) / gd_k;  tb = ((float)(N_k - 1) - go_k) / gd_k;
+ *                  z0 = fmaxf(z0, fminf(ta, tb));  z1 = fminf(z1, fmaxf(ta, tb))
+ *       gd_k == 0: a miss unless 0 <= go_k <= (float)(N_k - 1)
+ *     a miss unless z0 <= z1 (a NaN fails);  a miss when any N_k < 2 (no cell)
+ *     for k = 0, 1, ... while zk = z0 + (float)k * dzs <= z1 and k < NRGBD_TSDF_RAYCAST_MAX_STEPS (reaching it is a miss):
+ *       p_a = go_a + zk * gd_a;  the sample is INVALID unless 0 <= p_a <= (float)(N_a - 1) on every axis (a NaN fails)
+ *       i_a = min((int)floorf(p_a), N_a - 2);  f_a = p_a - (float)i_a
+ *       VALID iff the weights of the eight corners i + {0,1}^3 are all >= w_min (a NaN fails)
+ *       T = lerp(lerp(lerp(T000, T100, fx), lerp(T010, T110, fx), fy), lerp(lerp(T001, T101, fx), lerp(T011, T111, fx), fy), fz)
+ *           with lerp(a, b, f) = a + f * (b - a) and Txyz the corner i + (x, y, z)
+ *       a hit iff the previous sample (k - 1) was VALID with T_prev > 0 and this one is VALID with T <= 0:
+ *           q = T_prev / (T_prev - T);  depth = z_prev + dzs * q;  the march stops
+ *     normal, at a hit: p_a = go_a + depth * gd_a; (0, 0, 0) unless 0 <= p_a <= (float)(N_a - 1) on every axis and, with i, f as
+ *       above, the eight weights are all >= w_min; then the gradient of the trilinear interpolant,
+ *       gx = lerp(lerp(T100 - T000, T110 - T010, fy), lerp(T101 - T001, T111 - T011, fy), fz)
+ *       gy = lerp(lerp(T010 - T000, T110 - T100, fx), lerp(T011 - T001, T111 - T101, fx), fz)
+ *       gz = lerp(lerp(T001 - T000, T101 - T100, fx), lerp(T011 - T010, T111 - T110, fx), fy)
+ *       g = sqrtf((gx * gx + gy * gy) + gz * gz);  (0, 0, 0) unless g > 0 and finite;  u = (gx / g, gy / g, gz / g)
+ *       n_j = (rj0 * ux + rj1 * uy) + rj2 * uz                 (rotated into the camera frame)
+ *   A workgroup owns a NRGBD_TSDF_RAYCAST_TILE^2 pixel tile, a wave an 8 x 8 quarter of it.
+ *   errors       NRGBD_E_NULL: tsdf, weight, pose, centre or depth NULL;  NRGBD_E_SHAPE: a dimension <= 0, X Y Z > 2^31, H or W >
+ *                NRGBD_TSDF_RAYCAST_MAX_SIDE;  NRGBD_E_ARG: voxel_size, step, fx or fy <= 0 or not finite, d_near < d_far not true,
+ *                a NaN w_min, a pose or centre entry that is not finite.  Checked in this order, before anything touches the device.
  */
 #define NRGBD_TSDF_EXTRACT_VOXELS 1024
 #define NRGBD_TSDF_SCAN_PASS 1024
+#define NRGBD_TSDF_RAYCAST_MAX_STEPS 65536
+#define NRGBD_TSDF_RAYCAST_TILE 16
+#define NRGBD_TSDF_RAYCAST_MAX_SIDE 16384
 int nrgbd_tsdf_integrate_f32(float* tsdf, float* weight, int X, int Y, int Z, float ox, float oy, float oz, float voxel_size,
                              const float* depth, const float* gate, float gate_thr, const float* wmap, int H, int W,
                              const float* pose, float fx, float fy, float cx, float cy, float trunc, float d_near, float d_far,
@@ -1010,6 +1055,10 @@ long nrgbd_tsdf_extract_workspace(int X, int Y, int Z);
 int nrgbd_tsdf_extract_points(const float* tsdf, const float* weight, int X, int Y, int Z, float ox, float oy, float oz,
                               float voxel_size, float w_min, void* workspace, long workspace_bytes, float* points, long capacity,
                               long long* counts, void* stream);
+int nrgbd_tsdf_raycast_f32(const float* tsdf, const float* weight, int X, int Y, int Z, float ox, float oy, float oz,
+                           float voxel_size, const float* pose, const float* centre, float fx, float fy, float cx, float cy,
+                           int H, int W, float d_near, float d_far, float w_min, float step, float* depth, float* normal,
+                           void* stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,7 @@ Drop-in surface (reference file it replaces):
                                     digitising (mdataloader/scanNet.py:372-422) on the device
     neuralrgbd_amd.evaluate         code/test_utils/export_res.py:108-116 and the offline scoring behind it: error metrics of the depth maps
                                     against ground truth, per confidence set, as running totals on the device
-    neuralrgbd_amd.fusion           (no counterpart) TSDF fusion of the depth stream into a voxel volume on the device, surface points
+    neuralrgbd_amd.fusion           (no counterpart) TSDF fusion of the depth stream into a voxel volume on the device, surface points, ray cast
     neuralrgbd_amd.camera           the cam_intrinsics dict of code/mdataloader/scanNet.py:204-272
 The compute between the convolutions is hand-written HIP behind the C-ABI of include/nrgbd.h
 (libnrgbd_hip.so, built by `python -m neuralrgbd_amd.build`).
@@ -48,7 +48,7 @@ def __getattr__(name):
     if name in ("DepthMetrics", "EvalVideoStream", "evaluate_sequence", "metrics_from_record"):
         from . import evaluate
         return getattr(evaluate, name)
-    if name in ("TSDFVolume", "FusionVideoStream", "fuse_sequence", "frustum_box", "intrinsics_at", "save_ply"):
+    if name in ("TSDFVolume", "FusionVideoStream", "fuse_sequence", "frustum_box", "intrinsics_at", "save_ply", "shade"):
         from . import fusion
         return getattr(fusion, name)
     raise AttributeError(name)

@@ -23,6 +23,9 @@ DEPTH_EVAL_MAX_SETS = 8         # NRGBD_DEPTH_EVAL_MAX_SETS
 DGF_TILE = (16, 64)             # NRGBD_DGF_TILE_Y, NRGBD_DGF_TILE_X
 TSDF_EXTRACT_VOXELS = 1024      # NRGBD_TSDF_EXTRACT_VOXELS
 TSDF_SCAN_PASS = 1024           # NRGBD_TSDF_SCAN_PASS
+TSDF_RAYCAST_MAX_STEPS = 65536  # NRGBD_TSDF_RAYCAST_MAX_STEPS
+TSDF_RAYCAST_TILE = 16          # NRGBD_TSDF_RAYCAST_TILE
+TSDF_RAYCAST_MAX_SIDE = 16384   # NRGBD_TSDF_RAYCAST_MAX_SIDE
 
 
 class WindowSlots(ctypes.Structure):
@@ -138,6 +141,7 @@ SIGNATURES = {
     "nrgbd_tsdf_integrate_f32": (_I, [_P, _P, _I, _I, _I, _F, _F, _F, _F, _P, _P, _F, _P, _I, _I, _P, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P]),
     "nrgbd_tsdf_extract_workspace": (_L, [_I, _I, _I]),
     "nrgbd_tsdf_extract_points": (_I, [_P, _P, _I, _I, _I, _F, _F, _F, _F, _F, _P, _L, _P, _L, _P, _P]),
+    "nrgbd_tsdf_raycast_f32": (_I, [_P, _P, _I, _I, _I, _F, _F, _F, _F, _P, _P, _F, _F, _F, _F, _I, _I, _F, _F, _F, _F, _P, _P, _P]),
     "nrgbd_nhwc_stats_workgroups": (_I, [_L]),
     "nrgbd_nhwc_stats": (_I, [_P, _L, _I, _P, _P]),
     "nrgbd_nhwc_act": (_I, [_P, _P, _I, _P, _P, _I, _P, _L, _I, _I, _P]),

@@ -9,6 +9,8 @@ conventions (lattice, projection, update rule, crossings) are written out in inc
   * `frustum_box`: the voxel box a camera can touch, in float64 on the host — `integrate(cull=True)` launches over it alone;
   * `FusionVideoStream`: a video.VideoDepthStream that integrates the map of every frame that comes out, with the extrinsic that was
     pushed with that frame;
+  * `TSDFVolume.raycast` / `FusionVideoStream.render`: the volume seen from any camera — depth and normals, one launch
+    (ops.tsdf_raycast); `shade` turns the normals into a viewable image;
   * `fuse_sequence`, `save_ply`.
 """
 import math
@@ -152,6 +154,33 @@ class TSDFVolume:
         found, written = (int(v) for v in self._counts.cpu())
         return out[:written], found
 
+    def raycast(self, extM, intrinsics, size, depth_range=(0., float("inf")), w_min=1., step=None, normals=False, out=None):
+        """The volume seen from a camera at extM (host [3,4] or [4,4] world -> camera), one launch (ops.tsdf_raycast): z-depth [H,W] of
+        the surface along every pixel's ray, 0 where there is none, and with normals=True (depth, normal [3,H,W]) with the unit normals
+        in the camera frame.  intrinsics: (fx, fy, cx, cy) at size = (H, W), or a cam_intrinsics dict (intrinsics_at); depth_range: the
+        z-depths searched; w_min: a sample counts where the eight weights around it reach it; step: the sample distance along the ray
+        in metres (default voxel_size; above trunc a ray could step over the band); out: tensors to write into (then nothing is
+        allocated).  Synchronises nothing."""
+        H, W = (int(n) for n in size)
+        if isinstance(intrinsics, dict):
+            intrinsics = intrinsics_at(intrinsics, H, W)
+        m = _host_matrix(extM, "TSDFVolume.raycast")
+        if not np.isfinite(m[:3, :4]).all():
+            raise ValueError("TSDFVolume.raycast: the pose is not finite")
+        step = self.voxel_size if step is None else float(step)
+        if not 0 < step <= self.trunc:
+            raise ValueError("TSDFVolume.raycast: step %s is not in (0, trunc = %s]: a ray could step over the band" % (step, self.trunc))
+        return ops.tsdf_raycast(self.tsdf, self.weight, self.origin, self.voxel_size, m, intrinsics, (H, W), depth_range, w_min=w_min,
+                                step=step, normals=normals, out=out)
+
+
+def shade(normal):
+    """[3,H,W] camera-frame normals (TSDFVolume.raycast(normals=True)) -> a uint8 [H,W] Lambert image with the light along the view
+    direction: 255 * max(0, -n_z), 0 where there is no surface."""
+    if isinstance(normal, torch.Tensor):
+        return (-normal[2]).clamp(0., 1.).mul(255.).round().to(torch.uint8)
+    return np.rint(np.clip(-np.asarray(normal)[2], 0., 1.) * 255.).astype(np.uint8)
+
 
 class FusionVideoStream(VideoDepthStream):
     """VideoDepthStream + a TSDFVolume: push(frame, extM) returns what VideoDepthStream.push returns, and every depth frame that comes
@@ -193,6 +222,18 @@ class FusionVideoStream(VideoDepthStream):
         super().reset()
         self.ext_ring.clear()
         self._ext = [None] * self.n_slots
+        self.last_ext = None                                    # the extrinsic of the last frame integrated on this trajectory
+
+    def render(self, extM=None, size=None, normals=False, **kw):
+        """The fused model as a depth map (and normals): TSDFVolume.raycast from extM — by default the extrinsic of the last frame
+        that was integrated — at `size` (default: the network's image size) with the stream's intrinsics and, unless given, its
+        depth_range.  An eager launch on the caller's stream; the frame ring and the captured graph are not touched."""
+        if extM is None:
+            extM = self.last_ext
+            if extM is None:
+                raise ValueError("FusionVideoStream.render: no frame has been integrated yet; pass extM")
+        kw.setdefault("depth_range", self.depth_range)
+        return self.volume.raycast(extM, self.cam, (self.H, self.W) if size is None else size, normals=normals, **kw)
 
     def _fuse(self, out):
         if out is None:
@@ -216,6 +257,7 @@ class FusionVideoStream(VideoDepthStream):
         if self.volume.integrate(depth, self._ext[slot], self.cam, gate=gate, gate_thr=self.gate_thr, weight=wmap,
                                  depth_range=self.depth_range):
             self.n_integrated += 1
+            self.last_ext = self._ext[slot]
         return out
 
     def push(self, frame, extM):

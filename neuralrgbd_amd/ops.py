@@ -1737,3 +1737,60 @@ def tsdf_extract_points(tsdf, weight, origin, voxel_size, w_min, workspace, poin
                                                    _p(workspace), workspace.numel() * workspace.element_size(),
                                                    _p(points if capacity else None), capacity, _p(counts), _stream(tsdf))
     _lib.check(rc, "nrgbd_tsdf_extract_points")
+
+
+TSDF_RAYCAST_TILE = _lib.TSDF_RAYCAST_TILE      # side of the pixel tile a workgroup of nrgbd_tsdf_raycast_f32 owns (a wave: 8 x 8)
+
+
+def camera_centre(pose):
+    """The camera centre -R^T t of a world -> camera pose: float32(pose[:3,:4]) promoted to float64, the three sums formed in a
+    fixed order, rounded to float32 once (what nrgbd_tsdf_raycast_f32 takes as `centre`)."""
+    p = np.asarray(pose)[:3, :4].astype(np.float32).astype(np.float64)
+    return np.array([-((p[0, k] * p[0, 3] + p[1, k] * p[1, 3]) + p[2, k] * p[2, 3]) for k in range(3)], dtype=np.float64).astype(np.float32)
+
+
+def tsdf_raycast(tsdf, weight, origin, voxel_size, pose, intrinsics, size, depth_range, w_min=1.0, step=None, normals=False, out=None):
+    """A TSDF volume seen from a camera, one launch (nrgbd_tsdf_raycast_f32; the per-pixel operation sequence is written out in
+    include/nrgbd.h): z-depth [H,W] of the first zero crossing along every pixel's ray, 0 where there is none, and with normals=True
+    (depth, normal [3,H,W]), the unit surface normals in the camera frame ((0,0,0) where there is none).
+    tsdf / weight: contiguous CUDA fp32 [Z,Y,X]; pose: host [3,4] or [4,4] world -> camera, cast to float32; intrinsics = (fx, fy, cx,
+    cy) at size = (H, W); depth_range = [d_near, d_far]; a sample counts where the eight weights around it are >= w_min; step: the
+    sample distance along the ray in metres (None: voxel_size).  out: a contiguous CUDA fp32 [H,W] tensor, or with normals=True the
+    pair ([H,W], [3,H,W]), to write into; then nothing is allocated.  Nothing is synchronised."""
+    tsdf, weight = _tsdf_volume(tsdf, weight, "tsdf_raycast")
+    dev = tsdf.device
+    H, W = (int(n) for n in size)
+    if isinstance(pose, torch.Tensor):
+        if pose.is_cuda:
+            raise ValueError("tsdf_raycast: pose is a host matrix (it is read at the call)")
+        pose = pose.detach().numpy()
+    pose = np.asarray(pose)
+    if pose.shape not in ((3, 4), (4, 4)):
+        raise ValueError("tsdf_raycast: pose is [3,4] or [4,4] world -> camera, got %s" % (pose.shape,))
+    pose = np.ascontiguousarray(pose[:3, :4], dtype=np.float32)
+    centre = np.ascontiguousarray(camera_centre(pose))
+    k = tuple(float(x) for x in intrinsics)
+    if len(k) != 4:
+        raise ValueError("tsdf_raycast: intrinsics = (fx, fy, cx, cy)")
+    o = _vec3(origin, "tsdf_raycast: origin")
+    if out is None:
+        if H <= 0 or W <= 0:
+            raise ValueError("tsdf_raycast: size = (H, W), positive; got %s" % (size,))
+        depth = torch.empty((H, W), dtype=torch.float32, device=dev)
+        normal = torch.empty((3, H, W), dtype=torch.float32, device=dev) if normals else None
+    else:
+        if normals and (not isinstance(out, (tuple, list)) or len(out) != 2):
+            raise ValueError("tsdf_raycast: normals=True takes out=(depth, normal)")
+        depth, normal = out if normals else (out, None)
+        for t, nm, shape in ((depth, "out depth", (H, W)), (normal, "out normal", (3, H, W)))[:2 if normals else 1]:
+            t = _need(t, nm, shape, strided=True)
+            if t.device != dev or not t.is_contiguous():
+                raise ValueError("tsdf_raycast: %s must be contiguous and on %s" % (nm, dev))
+    Z, Y, X = tsdf.shape
+    with torch.cuda.device(dev):
+        rc = _lib.load().nrgbd_tsdf_raycast_f32(_p(tsdf), _p(weight), X, Y, Z, o[0], o[1], o[2], float(voxel_size),
+                                                ctypes.c_void_p(pose.ctypes.data), ctypes.c_void_p(centre.ctypes.data), k[0], k[1], k[2],
+                                                k[3], H, W, float(depth_range[0]), float(depth_range[1]), float(w_min),
+                                                float(voxel_size if step is None else step), _p(depth), _p(normal), _stream(tsdf))
+    _lib.check(rc, "nrgbd_tsdf_raycast_f32")
+    return (depth, normal) if normals else depth
