@@ -63,7 +63,8 @@ extern "C" {
  * nrgbd_depth_eval_workgroups, nrgbd_depth_eval_workspace and nrgbd_depth_eval; no existing entry changed, the version string stays.
  * The same holds for nrgbd_dgf_refine_f32 (the guided-filter refinement net), and for the TSDF fusion entries
  * nrgbd_tsdf_integrate_f32, nrgbd_tsdf_extract_workspace and nrgbd_tsdf_extract_points, and for nrgbd_tsdf_raycast_f32 (the fused
- * volume rendered to depth and normals). */
+ * volume rendered to depth and normals), and for nrgbd_tsdf_mesh_workspace and nrgbd_tsdf_extract_mesh (the fused volume as an
+ * indexed triangle mesh). */
 #define NRGBD_INTERFACE_VERSION "0.10"
 const char* nrgbd_version(void);
 const char* nrgbd_strerror(int code);
@@ -956,8 +957,8 @@ int nrgbd_dgf_refine_f32(const float* depth_lr, int n, int h, int w, const float
                          float* out, void* stream);
 /*
  * TSDF fusion (tsdf.hip; neuralrgbd_amd/fusion.py: TSDFVolume, FusionVideoStream): the depth maps of a trajectory accumulated in
- * the world frame as a dense truncated-signed-distance volume on the device, and the volume's surface as points.  None of the
- * four entries has a counterpart in the reference, which drops every map after export; the conventions are the ones written here.
+ * the world frame as a dense truncated-signed-distance volume on the device, and the volume's surface as points and as a triangle
+ * mesh.  None of the entries has a counterpart in the reference, which drops every map after export; the conventions are the ones written here.
  * Everything is fp32, every operation below is ONE IEEE fp32 operation in the order written (no fused multiply-add, no reciprocal),
  * there are no atomics, and the same inputs give the same bits in every run.
  *
@@ -1041,6 +1042,32 @@ int nrgbd_dgf_refine_f32(const float* depth_lr, int n, int h, int w, const float
  *   errors       NRGBD_E_NULL: tsdf, weight, pose, centre or depth NULL;  NRGBD_E_SHAPE: a dimension <= 0, X Y Z > 2^31, H or W >
  *                NRGBD_TSDF_RAYCAST_MAX_SIDE;  NRGBD_E_ARG: voxel_size, step, fx or fy <= 0 or not finite, d_near < d_far not true,
  *                a NaN w_min, a pose or centre entry that is not finite.  Checked in this order, before anything touches the device.
+ * nrgbd_tsdf_mesh_workspace — no counterpart in the reference: the bytes nrgbd_tsdf_extract_mesh needs for an X Y Z grid (24 per
+ *   NRGBD_TSDF_EXTRACT_VOXELS voxels and 4 per voxel; needs no GPU); NRGBD_E_SHAPE: a dimension <= 0, 3 X Y Z > 2^31 - 1.
+ * nrgbd_tsdf_extract_mesh — no counterpart in the reference: the volume's surface as an indexed triangle mesh (tsdf_mesh.hip), four
+ *   launches (per-workgroup counts of crossings and of triangles; the exclusive scan of both; the vertices and every voxel's first
+ *   vertex row; the triangles), no atomics, capturable.
+ *   vertices     device fp32 [vertex_capacity][3]: the crossings of nrgbd_tsdf_extract_points — the same predicate, the same q, the
+ *                same three operations per coordinate, the same ascending (linear voxel index, axis) order, the same device code: the
+ *                first min(found, vertex_capacity) rows, bit for bit what that entry writes; nothing behind them is written
+ *   cells        the cell of (ix, iy, iz), ix < X - 1, iy < Y - 1, iz < Z - 1, has the corners c = cx + 2 cy + 4 cz at (ix + cx, iy + cy,
+ *                iz + cz) and is VALID iff all eight have W >= w_min && fabsf(T) < 1 (a NaN fails).  Bit c of its case is T_c < 0
+ *                (0.0 and -0.0 are both outside, as for the crossings), so every sign-changing edge of a valid cell is a crossing.
+ *                A valid cell emits the triangles of its case (csrc/tsdf_mc_table.hpp, generated by tools/gen_mc_table.py from the
+ *                rule written there: at most 5, the right-hand normal towards positive T, free space — the side the ray cast's
+ *                normals point to; a closed manifold on any sign field; not MC33); an invalid cell emits none.  So a vertex at the
+ *                border of the observed region may be referenced by no triangle; and where a corner holds T = 0 exactly, q is 0,
+ *                the vertices of its edges coincide and the zero-area triangles between them are kept: the topology is the table's.
+ *   faces        device int32 [face_capacity][3]: per triangle the rows its three vertices have in the FULL vertex sequence (whatever
+ *                vertex_capacity is): the vertex on edge (voxel v, axis k) has row first(v) + popc(crossings(v) & ((1 << k) - 1)).
+ *                Ascending cell order (the linear index of the lowest corner), table order inside a cell; the first min(found,
+ *                face_capacity) triangles, nothing behind them.  Either output may be NULL when its capacity is 0.
+ *   counts       device int64 [4] = vertices found, vertices written, triangles found, triangles written
+ *   workspace    8-byte aligned, at least nrgbd_tsdf_mesh_workspace(X, Y, Z) bytes; rewritten by every call
+ *   errors       NRGBD_E_NULL: a NULL pointer (vertices / faces only when their capacity > 0);  NRGBD_E_SHAPE: a dimension <= 0,
+ *                3 X Y Z > 2^31 - 1 (a row would not fit an int32), a capacity < 0, a workspace that is too small;  NRGBD_E_ARG:
+ *                voxel_size <= 0 or not finite, a NaN w_min;  NRGBD_E_ALIGN: workspace or counts.  Checked in this order, before
+ *                anything touches the device.
  */
 #define NRGBD_TSDF_EXTRACT_VOXELS 1024
 #define NRGBD_TSDF_SCAN_PASS 1024
@@ -1059,6 +1086,10 @@ int nrgbd_tsdf_raycast_f32(const float* tsdf, const float* weight, int X, int Y,
                            float voxel_size, const float* pose, const float* centre, float fx, float fy, float cx, float cy,
                            int H, int W, float d_near, float d_far, float w_min, float step, float* depth, float* normal,
                            void* stream);
+long nrgbd_tsdf_mesh_workspace(int X, int Y, int Z);
+int nrgbd_tsdf_extract_mesh(const float* tsdf, const float* weight, int X, int Y, int Z, float ox, float oy, float oz,
+                            float voxel_size, float w_min, void* workspace, long workspace_bytes, float* vertices,
+                            long vertex_capacity, int* faces, long face_capacity, long long* counts, void* stream);
 
 #ifdef __cplusplus
 }

@@ -22,14 +22,11 @@
 //                             carried total (int64), then (crossings found, points written) into the caller's int64 [2]
 // tsdf_extract_kernel<true>   re-evaluates the crossings and writes point `offset of the workgroup + rank inside it` while that is
 //                             below the capacity: ascending (linear voxel index, axis) order, nothing behind the written rows.
-#include "common.hpp"
+// The crossing predicate, a lane's four voxels, the point writer and the scan live in tsdf_extract.hpp: tsdf_mesh.hip (the triangle
+// mesh, whose vertices are these points) runs the same device code.
+#include "tsdf_extract.hpp"      // the crossings, the lane's four voxels, the scan: shared with tsdf_mesh.hip
 
 namespace nrgbd {
-
-constexpr int kExtractVoxels = NRGBD_TSDF_EXTRACT_VOXELS;      // 1024: four consecutive voxels per lane
-constexpr int kScanPass = NRGBD_TSDF_SCAN_PASS;                // 1024: four consecutive records per lane and pass
-constexpr long kTsdfMaxVoxels = 1L << 31;
-constexpr float kFltMax = 3.402823466e+38f;
 
 struct TsdfFrame {
     float r[12];                        // float32(extM[:3,:4]) row-major: r00 r01 r02 tx | r10 r11 r12 ty | r20 r21 r22 tz
@@ -130,143 +127,29 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(float* __restrict__
 
 // ---- extraction ---------------------------------------------------------------------------------------------------------------
 
-struct TsdfGrid {
-    float ox, oy, oz, vs, w_min;
-    unsigned X, Y, Z, XY;
-    unsigned n;                         // X Y Z - 1 (the count itself may be 2^31)
-};
-
-__device__ __forceinline__ bool tsdf_side(const float* __restrict__ tsdf, const float* __restrict__ weight, size_t i, float w_min, float& T) {
-    T = tsdf[i];
-    return weight[i] >= w_min && fabsf(T) < 1.f;                 // a NaN weight or value fails
-}
-
-// The crossings of voxel i along x, y, z: bit k of the result, q[k] = T_a / (T_a - T_b).
-__device__ __forceinline__ int tsdf_crossings(const float* __restrict__ tsdf, const float* __restrict__ weight, const TsdfGrid& g, unsigned i,
-                                              unsigned ix, unsigned iy, unsigned iz, float (&q)[3]) {
-    float Ta;
-    if (!tsdf_side(tsdf, weight, i, g.w_min, Ta)) return 0;
-    const bool inside[3] = {ix + 1 < g.X, iy + 1 < g.Y, iz + 1 < g.Z};
-    const unsigned step[3] = {1u, g.X, g.XY};
-    int mask = 0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        q[k] = 0.f;
-        if (!inside[k]) continue;
-        float Tb;
-        if (!tsdf_side(tsdf, weight, (size_t)i + step[k], g.w_min, Tb)) continue;
-        if ((Ta < 0.f) == (Tb < 0.f)) continue;
-        q[k] = Ta / (Ta - Tb);
-        mask |= 1 << k;
-    }
-    return mask;
-}
-
-__device__ __forceinline__ int block_sum_256(int v, int* lds) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((lds[0] + lds[1]) + lds[2]) + lds[3];
-}
-
-// exclusive prefix of v over the 256 lanes of the workgroup in lane order (lds: 4 ints); total: the workgroup's sum
-template <typename T>
-__device__ __forceinline__ T block_exclusive_256(T v, T* lds, T& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    T inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T up = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += up;
-    }
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    T before = 0;
-    for (int k = 0; k < wave; ++k) before += lds[k];
-    total = ((lds[0] + lds[1]) + lds[2]) + lds[3];
-    return before + inc - v;
-}
-
 template <bool WRITE>
 __global__ __launch_bounds__(256) void tsdf_extract_kernel(const float* __restrict__ tsdf, const float* __restrict__ weight, const TsdfGrid g,
                                                            int* __restrict__ wg_count, const long long* __restrict__ wg_offset,
                                                            float* __restrict__ points, long long capacity) {
     __shared__ int lds[4];
-    const unsigned long long first = (unsigned long long)blockIdx.x * kExtractVoxels + 4ull * threadIdx.x;
-    int mask[4];
-    float q[4][3];
-    unsigned ixs[4], iys[4], izs[4];
-    int mine = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        mask[j] = 0;
-        if (first + j > g.n) continue;
-        const unsigned i = (unsigned)(first + j);
-        izs[j] = i / g.XY;
-        const unsigned rem = i - izs[j] * g.XY;
-        iys[j] = rem / g.X;
-        ixs[j] = rem - iys[j] * g.X;
-        mask[j] = tsdf_crossings(tsdf, weight, g, i, ixs[j], iys[j], izs[j], q[j]);
-        mine += __popc(mask[j]);
-    }
+    const unsigned long long first = tsdf_lane_first();
+    TsdfLane L;
+    tsdf_lane_crossings(tsdf, weight, g, first, L);
     if (!WRITE) {
-        const int s = block_sum_256(mine, lds);
+        const int s = block_sum_256(L.mine, lds);
         if (threadIdx.x == 0) wg_count[blockIdx.x] = s;
         return;
     }
     int total;
-    long long pos = wg_offset[blockIdx.x] + block_exclusive_256<int>(mine, lds, total);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            if (!(mask[j] & (1 << k))) continue;
-            if (pos < capacity) {
-                const float fi[3] = {(float)ixs[j], (float)iys[j], (float)izs[j]};
-                float* out = points + 3 * pos;
-                out[0] = g.ox + g.vs * (k == 0 ? fi[0] + q[j][0] : fi[0]);
-                out[1] = g.oy + g.vs * (k == 1 ? fi[1] + q[j][1] : fi[1]);
-                out[2] = g.oz + g.vs * (k == 2 ? fi[2] + q[j][2] : fi[2]);
-            }
-            ++pos;
-        }
-    }
+    const long long pos = wg_offset[blockIdx.x] + block_exclusive_256<int>(L.mine, lds, total);
+    tsdf_lane_write<false>(g, L, first, pos, points, capacity, nullptr);
 }
 
 __global__ __launch_bounds__(256) void tsdf_scan_kernel(const int* __restrict__ wg_count, long long* __restrict__ wg_offset, int nwg,
                                                         long long capacity, long long* __restrict__ counts) {
     __shared__ long long lds[4];
-    long long carry = 0;
-    for (int base = 0; base < nwg; base += kScanPass) {
-        const int r0 = base + 4 * (int)threadIdx.x;
-        long long c[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) c[j] = r0 + j < nwg ? (long long)wg_count[r0 + j] : 0;
-        long long total;
-        long long at = carry + block_exclusive_256<long long>(((c[0] + c[1]) + c[2]) + c[3], lds, total);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (r0 + j < nwg) wg_offset[r0 + j] = at;
-            at += c[j];
-        }
-        carry += total;
-        __syncthreads();                // lds is rewritten by the next pass
-    }
-    if (threadIdx.x == 0) {
-        counts[0] = carry;
-        counts[1] = carry < capacity ? carry : capacity;
-    }
+    tsdf_scan_records(wg_count, wg_offset, nwg, capacity, counts, lds);
 }
-
-static long tsdf_voxels(int X, int Y, int Z) {
-    if (X <= 0 || Y <= 0 || Z <= 0) return NRGBD_E_SHAPE;
-    const long xy = (long)X * Y;
-    if (xy > kTsdfMaxVoxels || xy * Z > kTsdfMaxVoxels) return NRGBD_E_SHAPE;
-    return xy * Z;
-}
-
-static bool tsdf_positive(float v) { return v > 0.f && v <= kFltMax; }
 
 }  // namespace nrgbd
 
@@ -327,11 +210,7 @@ extern "C" int nrgbd_tsdf_extract_points(const float* tsdf, const float* weight,
     if (workspace_bytes < nwg * 16) return NRGBD_E_SHAPE;
     if (!tsdf_positive(voxel_size) || w_min != w_min) return NRGBD_E_ARG;
     if (((uintptr_t)workspace | (uintptr_t)counts) & 7) return NRGBD_E_ALIGN;
-    TsdfGrid g;
-    g.ox = ox; g.oy = oy; g.oz = oz; g.vs = voxel_size; g.w_min = w_min;
-    g.X = (unsigned)X; g.Y = (unsigned)Y; g.Z = (unsigned)Z;
-    g.XY = (unsigned)((long)X * Y > 0x7fffffffL ? 0x80000000u : (unsigned)((long)X * Y));
-    g.n = (unsigned)(n - 1);
+    const TsdfGrid g = tsdf_grid(X, Y, Z, n, ox, oy, oz, voxel_size, w_min);
     long long* wg_offset = (long long*)workspace;
     int* wg_count = (int*)(wg_offset + nwg);
     hipStream_t st = (hipStream_t)stream;

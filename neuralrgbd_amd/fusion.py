@@ -11,6 +11,8 @@ conventions (lattice, projection, update rule, crossings) are written out in inc
     pushed with that frame;
   * `TSDFVolume.raycast` / `FusionVideoStream.render`: the volume seen from any camera — depth and normals, one launch
     (ops.tsdf_raycast); `shade` turns the normals into a viewable image;
+  * `TSDFVolume.mesh` / `FusionVideoStream.mesh`: the surface as an indexed triangle mesh (ops.tsdf_extract_mesh): the vertices are
+    `points()`'s, the triangles come from a 256-case table and wind towards free space; `save_ply` writes it (ASCII or binary);
   * `fuse_sequence`, `save_ply`.
 """
 import math
@@ -104,6 +106,7 @@ class TSDFVolume:
         self.tsdf, self.weight = self._buf[0], self._buf[1]
         self._counts = torch.zeros(2, dtype=torch.int64, device=self.device)
         self._workspace = None
+        self._mesh_counts = self._mesh_workspace = None
 
     def reset(self):
         """An empty volume again (asynchronous)."""
@@ -153,6 +156,30 @@ class TSDFVolume:
         ops.tsdf_extract_points(*args, out if capacity else None, self._counts)
         found, written = (int(v) for v in self._counts.cpu())
         return out[:written], found
+
+    def mesh(self, w_min=1., capacity=None):
+        """The surface as an indexed triangle mesh: (vertices [n,3] CUDA fp32, faces [m,3] CUDA int32, (vertices found, triangles
+        found)).  The vertices are exactly `points(w_min)` in its order; a cell whose eight corners all have weight >= w_min and
+        |T| < 1 emits the triangles of its sign case (at most 5, the normal towards free space, ascending cell order); a face holds
+        the rows of its vertices in the FULL vertex sequence, whatever the vertex capacity.  capacity=None: counts first, then
+        writes everything; capacity=(nv, nf): the first min(found, capacity) rows of either.  Reads the counts back: like `points`,
+        the one place this object synchronises (and allocates)."""
+        if self._mesh_workspace is None:
+            self._mesh_workspace = torch.empty((ops.tsdf_mesh_workspace(*self.dims) + 7) // 8, dtype=torch.int64, device=self.device)
+            self._mesh_counts = torch.zeros(4, dtype=torch.int64, device=self.device)
+        args = (self.tsdf, self.weight, self.origin, self.voxel_size, w_min, self._mesh_workspace)
+        if capacity is None:
+            ops.tsdf_extract_mesh(*args, None, None, self._mesh_counts)
+            found = self._mesh_counts.cpu()
+            capacity = (int(found[0]), int(found[2]))
+        nv, nf = (int(c) for c in capacity)
+        if nv < 0 or nf < 0:
+            raise ValueError("TSDFVolume.mesh: capacity %s" % (capacity,))
+        vertices = torch.empty((nv, 3), dtype=torch.float32, device=self.device)
+        faces = torch.empty((nf, 3), dtype=torch.int32, device=self.device)
+        ops.tsdf_extract_mesh(*args, vertices if nv else None, faces if nf else None, self._mesh_counts)
+        v_found, v_written, f_found, f_written = (int(v) for v in self._mesh_counts.cpu())
+        return vertices[:v_written], faces[:f_written], (v_found, f_found)
 
     def raycast(self, extM, intrinsics, size, depth_range=(0., float("inf")), w_min=1., step=None, normals=False, out=None):
         """The volume seen from a camera at extM (host [3,4] or [4,4] world -> camera), one launch (ops.tsdf_raycast): z-depth [H,W] of
@@ -235,6 +262,10 @@ class FusionVideoStream(VideoDepthStream):
         kw.setdefault("depth_range", self.depth_range)
         return self.volume.raycast(extM, self.cam, (self.H, self.W) if size is None else size, normals=normals, **kw)
 
+    def mesh(self, **kw):
+        """The fused model as a triangle mesh: TSDFVolume.mesh(**kw) of the stream's volume."""
+        return self.volume.mesh(**kw)
+
     def _fuse(self, out):
         if out is None:
             return out
@@ -287,13 +318,38 @@ def fuse_sequence(stream, frames, extMs):
     return stream.n_integrated - before
 
 
-def save_ply(path, points):
-    """[n,3] points (a tensor on any device, or an array) as an ASCII PLY file, written on the host; %.9g round-trips fp32."""
+def save_ply(path, points, faces=None, binary=False):
+    """[n,3] points (a tensor on any device, or an array) as a PLY file, written on the host; returns the vertex count.  faces: [m,3]
+    vertex rows (TSDFVolume.mesh's) written as an `element face` block (property list uchar int vertex_indices); binary: the
+    binary_little_endian 1.0 form, written by numpy in one piece, else ASCII, in which %.9g round-trips fp32."""
     if isinstance(points, torch.Tensor):
         points = points.detach().cpu().numpy()
     p = np.asarray(points, dtype=np.float32).reshape(-1, 3)
+    header = "ply\nformat %s 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n" % (
+        "binary_little_endian" if binary else "ascii", len(p))
+    tri = None
+    if faces is not None:
+        if isinstance(faces, torch.Tensor):
+            faces = faces.detach().cpu().numpy()
+        tri = np.asarray(faces).reshape(-1, 3)
+        if len(tri) and not (np.issubdtype(tri.dtype, np.integer) and tri.min() >= 0 and tri.max() < len(p)):
+            raise ValueError("save_ply: faces hold integer rows of the %d points" % len(p))
+        tri = tri.astype("<i4")
+        header += "element face %d\nproperty list uchar int vertex_indices\n" % len(tri)
+    header += "end_header\n"
+    if binary:
+        with open(path, "wb") as f:
+            f.write(header.encode("ascii"))
+            f.write(p.astype("<f4").tobytes())
+            if tri is not None:
+                rec = np.empty(len(tri), dtype=[("n", "u1"), ("v", "<i4", (3,))])
+                rec["n"], rec["v"] = 3, tri
+                f.write(rec.tobytes())
+        return len(p)
     with open(path, "w") as f:
-        f.write("ply\nformat ascii 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\nend_header\n" % len(p))
+        f.write(header)
         for x, y, z in p:
             f.write("%.9g %.9g %.9g\n" % (x, y, z))
+        for a, b, c in (tri if tri is not None else ()):
+            f.write("3 %d %d %d\n" % (a, b, c))
     return len(p)

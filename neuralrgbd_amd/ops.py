@@ -1739,6 +1739,49 @@ def tsdf_extract_points(tsdf, weight, origin, voxel_size, w_min, workspace, poin
     _lib.check(rc, "nrgbd_tsdf_extract_points")
 
 
+def tsdf_mesh_workspace(X, Y, Z):
+    """Bytes of workspace nrgbd_tsdf_extract_mesh needs for an X x Y x Z grid (needs no GPU)."""
+    rc = _lib.load().nrgbd_tsdf_mesh_workspace(int(X), int(Y), int(Z))
+    if rc < 0:
+        _lib.check(rc, "nrgbd_tsdf_mesh_workspace")
+    return rc
+
+
+def tsdf_extract_mesh(tsdf, weight, origin, voxel_size, w_min, workspace, vertices, faces, counts):
+    """The surface of a TSDF volume as an indexed triangle mesh (nrgbd_tsdf_extract_mesh: four launches, no atomics).  The vertices are
+    the points of tsdf_extract_points, bit for bit and in its order; a triangle holds the rows of its three vertices in the full vertex
+    sequence, its normal towards free space; triangles come in ascending cell order (include/nrgbd.h has the conventions).
+    workspace: a contiguous CUDA tensor of at least tsdf_mesh_workspace(X, Y, Z) bytes; vertices: contiguous CUDA fp32 [capacity,3] or
+    None; faces: contiguous CUDA int32 [capacity,3] or None — the first min(found, capacity) rows of either are written; counts: CUDA
+    int64 [4], written (vertices found, vertices written, triangles found, triangles written).  Nothing is allocated, nothing
+    synchronised."""
+    tsdf, weight = _tsdf_volume(tsdf, weight, "tsdf_extract_mesh")
+    dev = tsdf.device
+    if not isinstance(workspace, torch.Tensor) or workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError("tsdf_extract_mesh: workspace must be a contiguous tensor on %s" % (dev,))
+    if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int64 or counts.device != dev or not counts.is_contiguous()
+            or tuple(counts.shape) != (4,)):
+        raise ValueError("tsdf_extract_mesh: counts must be a contiguous int64 tensor [4] on %s" % (dev,))
+    caps = []
+    for t, nm, dt in ((vertices, "vertices", torch.float32), (faces, "faces", torch.int32)):
+        if t is None:
+            caps.append(0)
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise TypeError("tsdf_extract_mesh: %s must be a %s tensor" % (nm, dt))
+        if t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous() or t.device != dev:
+            raise ValueError("tsdf_extract_mesh: %s must be a contiguous [capacity,3] tensor on %s" % (nm, dev))
+        caps.append(t.shape[0])
+    o = _vec3(origin, "tsdf_extract_mesh: origin")
+    Z, Y, X = tsdf.shape
+    with torch.cuda.device(dev):
+        rc = _lib.load().nrgbd_tsdf_extract_mesh(_p(tsdf), _p(weight), X, Y, Z, o[0], o[1], o[2], float(voxel_size), float(w_min),
+                                                 _p(workspace), workspace.numel() * workspace.element_size(),
+                                                 _p(vertices if caps[0] else None), caps[0], _p(faces if caps[1] else None), caps[1],
+                                                 _p(counts), _stream(tsdf))
+    _lib.check(rc, "nrgbd_tsdf_extract_mesh")
+
+
 TSDF_RAYCAST_TILE = _lib.TSDF_RAYCAST_TILE      # side of the pixel tile a workgroup of nrgbd_tsdf_raycast_f32 owns (a wave: 8 x 8)
 
 
