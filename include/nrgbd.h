@@ -64,7 +64,8 @@ extern "C" {
  * The same holds for nrgbd_dgf_refine_f32 (the guided-filter refinement net), and for the TSDF fusion entries
  * nrgbd_tsdf_integrate_f32, nrgbd_tsdf_extract_workspace and nrgbd_tsdf_extract_points, and for nrgbd_tsdf_raycast_f32 (the fused
  * volume rendered to depth and normals), and for nrgbd_tsdf_mesh_workspace and nrgbd_tsdf_extract_mesh (the fused volume as an
- * indexed triangle mesh). */
+ * indexed triangle mesh), and for the colour entries nrgbd_tsdf_integrate_color_f32, nrgbd_tsdf_extract_points_color,
+ * nrgbd_tsdf_extract_mesh_color and nrgbd_tsdf_raycast_color_f32 (the frames' colour fused into the volume). */
 #define NRGBD_INTERFACE_VERSION "0.10"
 const char* nrgbd_version(void);
 const char* nrgbd_strerror(int code);
@@ -1042,6 +1043,47 @@ int nrgbd_dgf_refine_f32(const float* depth_lr, int n, int h, int w, const float
  *   errors       NRGBD_E_NULL: tsdf, weight, pose, centre or depth NULL;  NRGBD_E_SHAPE: a dimension <= 0, X Y Z > 2^31, H or W >
  *                NRGBD_TSDF_RAYCAST_MAX_SIDE;  NRGBD_E_ARG: voxel_size, step, fx or fy <= 0 or not finite, d_near < d_far not true,
  *                a NaN w_min, a pose or centre entry that is not finite.  Checked in this order, before anything touches the device.
+ * nrgbd_tsdf_integrate_color_f32 — no counterpart in the reference: nrgbd_tsdf_integrate_f32 with the frame's colour carried through
+ *   the volume.  The colour volume: three planar device arrays color [3][Z][Y][X] (r, g, b; X fastest) beside tsdf and weight, all zeros
+ *   when fresh.  Colour SHARES the TSDF's weight: a voxel's colour is averaged over exactly the observations that updated its distance,
+ *   with the same w (Open3D's rule); there is no fourth weight plane, so a colour volume is integrated through this entry only.
+ *   color        device fp32 [3][Z][Y][X], the volume's three planes
+ *   image        device fp32 [3][Hc][Wc], planar, at a size of its own
+ *   fxc fyc cxc cyc  the pinhole intrinsics at Hc x Wc
+ *   affine       HOST fp32 [6] = a_r a_g a_b b_r b_g b_b, read at the call: the colour of a pixel is image * a + b per channel
+ *   per voxel of the box: the chain of nrgbd_tsdf_integrate_f32 unchanged up to t, w — the same skips, the same bits of T' and W' —
+ *   and for a voxel that is updated, with xc / zc and yc / zc the quotients the projection formed and C_j its three colour values:
+ *     uc = fxc * (xc / zc) + cxc;  vc = fyc * (yc / zc) + cyc
+ *     uc = fminf(fmaxf(uc, 0), (float)(Wc - 1));  vc = fminf(fmaxf(vc, 0), (float)(Hc - 1))      (clamped: colour never vetoes a
+ *                                                                                                distance update)
+ *     icu = (int)floorf(uc);  icv = (int)floorf(vc)
+ *     c_j = image[j][icv][icu] * a_j + b_j                                                       (j = r, g, b)
+ *     c_r, c_g, c_b all finite:  C_j' = (C_j * Wt + c_j * w) / (Wt + w)      with the OLD Wt: the denominator of T'
+ *     else:                      the three colour values keep their bits (T and Wt are updated all the same)
+ *   A skipped voxel, a voxel outside the box and a lane group that updates nothing keep their colour bits (the group is neither
+ *   loaded nor stored); the image is read only for voxels that passed every test.  Four x-neighbours per lane with 16-byte loads and
+ *   stores on all five planes when X % 4 == 0 and tsdf, weight and color are 16-byte aligned, one voxel per lane otherwise: the
+ *   same bits.
+ *   errors       those of nrgbd_tsdf_integrate_f32 in its order, and with them  NRGBD_E_NULL: color, image or affine NULL;
+ *                NRGBD_E_SHAPE: Hc or Wc <= 0 (after H and W, before the box);  NRGBD_E_ARG: a colour intrinsic or an affine entry
+ *                that is not finite (after d_near < d_far).  Before anything touches the device.
+ * nrgbd_tsdf_extract_points_color, nrgbd_tsdf_extract_mesh_color — no counterpart in the reference: nrgbd_tsdf_extract_points and
+ *   nrgbd_tsdf_extract_mesh with the colour of every point / vertex: the same launches, workspaces, counts, order and capacity cut.
+ *   color        device fp32 [3][Z][Y][X], the volume's three planes
+ *   colors       device fp32 [capacity][3] (the mesh: [vertex_capacity][3]): row p belongs to row p of points / vertices; for the
+ *                crossing between a and b = a + e_k at q:   colors[p][j] = C_j(a) + q * (C_j(b) - C_j(a))      (three operations,
+ *                the q that places the point); nothing behind the written rows is written.  points / vertices / faces and counts
+ *                hold the bits the colourless entries write.
+ *   errors       those of the colourless entry in its order;  NRGBD_E_NULL also: color NULL, colors NULL when the (vertex)
+ *                capacity is > 0.
+ * nrgbd_tsdf_raycast_color_f32 — no counterpart in the reference: nrgbd_tsdf_raycast_f32 with the colour at every hit.
+ *   color        device fp32 [3][Z][Y][X], the volume's three planes
+ *   rgb          device fp32 [3][H][W], always written: at a hit, with p, i, f as for the normal, (0, 0, 0) unless 0 <= p_a <=
+ *                (float)(N_a - 1) on every axis and the eight weights are all >= w_min; then per plane the trilinear interpolant
+ *                with T's nesting, lerp(lerp(lerp(C000, C100, fx), lerp(C010, C110, fx), fy), lerp(lerp(C001, C101, fx),
+ *                lerp(C011, C111, fx), fy), fz) (the corners are requested only where the test passed).  A miss is (0, 0, 0).  The
+ *                colour does not depend on the gradient being non-zero.  depth and normal keep their bits; normal may be NULL.
+ *   errors       those of nrgbd_tsdf_raycast_f32 in its order;  NRGBD_E_NULL also: color or rgb NULL.
  * nrgbd_tsdf_mesh_workspace — no counterpart in the reference: the bytes nrgbd_tsdf_extract_mesh needs for an X Y Z grid (24 per
  *   NRGBD_TSDF_EXTRACT_VOXELS voxels and 4 per voxel; needs no GPU); NRGBD_E_SHAPE: a dimension <= 0, 3 X Y Z > 2^31 - 1.
  * nrgbd_tsdf_extract_mesh — no counterpart in the reference: the volume's surface as an indexed triangle mesh (tsdf_mesh.hip), four
@@ -1090,6 +1132,22 @@ long nrgbd_tsdf_mesh_workspace(int X, int Y, int Z);
 int nrgbd_tsdf_extract_mesh(const float* tsdf, const float* weight, int X, int Y, int Z, float ox, float oy, float oz,
                             float voxel_size, float w_min, void* workspace, long workspace_bytes, float* vertices,
                             long vertex_capacity, int* faces, long face_capacity, long long* counts, void* stream);
+int nrgbd_tsdf_integrate_color_f32(float* tsdf, float* weight, float* color, int X, int Y, int Z, float ox, float oy, float oz,
+                                   float voxel_size, const float* depth, const float* gate, float gate_thr, const float* wmap,
+                                   int H, int W, const float* pose, float fx, float fy, float cx, float cy, float trunc,
+                                   float d_near, float d_far, float w_max, const int* box, const float* image, int Hc, int Wc,
+                                   float fxc, float fyc, float cxc, float cyc, const float* affine, void* stream);
+int nrgbd_tsdf_extract_points_color(const float* tsdf, const float* weight, const float* color, int X, int Y, int Z, float ox,
+                                    float oy, float oz, float voxel_size, float w_min, void* workspace, long workspace_bytes,
+                                    float* points, float* colors, long capacity, long long* counts, void* stream);
+int nrgbd_tsdf_extract_mesh_color(const float* tsdf, const float* weight, const float* color, int X, int Y, int Z, float ox,
+                                  float oy, float oz, float voxel_size, float w_min, void* workspace, long workspace_bytes,
+                                  float* vertices, float* colors, long vertex_capacity, int* faces, long face_capacity,
+                                  long long* counts, void* stream);
+int nrgbd_tsdf_raycast_color_f32(const float* tsdf, const float* weight, const float* color, int X, int Y, int Z, float ox,
+                                 float oy, float oz, float voxel_size, const float* pose, const float* centre, float fx,
+                                 float fy, float cx, float cy, int H, int W, float d_near, float d_far, float w_min, float step,
+                                 float* depth, float* normal, float* rgb, void* stream);
 
 #ifdef __cplusplus
 }

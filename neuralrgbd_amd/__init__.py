@@ -48,7 +48,7 @@ def __getattr__(name):
     if name in ("DepthMetrics", "EvalVideoStream", "evaluate_sequence", "metrics_from_record"):
         from . import evaluate
         return getattr(evaluate, name)
-    if name in ("TSDFVolume", "FusionVideoStream", "fuse_sequence", "frustum_box", "intrinsics_at", "save_ply", "shade"):
+    if name in ("TSDFVolume", "FusionVideoStream", "fuse_sequence", "frustum_box", "intrinsics_at", "save_ply", "shade", "to_uint8"):
         from . import fusion
         return getattr(fusion, name)
     raise AttributeError(name)

@@ -144,6 +144,11 @@ SIGNATURES = {
     "nrgbd_tsdf_raycast_f32": (_I, [_P, _P, _I, _I, _I, _F, _F, _F, _F, _P, _P, _F, _F, _F, _F, _I, _I, _F, _F, _F, _F, _P, _P, _P]),
     "nrgbd_tsdf_mesh_workspace": (_L, [_I, _I, _I]),
     "nrgbd_tsdf_extract_mesh": (_I, [_P, _P, _I, _I, _I, _F, _F, _F, _F, _F, _P, _L, _P, _L, _P, _L, _P, _P]),
+    "nrgbd_tsdf_integrate_color_f32": (_I, [_P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P, _P, _F, _P, _I, _I, _P, _F, _F, _F, _F, _F, _F, _F, _F,
+                                            _P, _P, _I, _I, _F, _F, _F, _F, _P, _P]),
+    "nrgbd_tsdf_extract_points_color": (_I, [_P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _F, _P, _L, _P, _P, _L, _P, _P]),
+    "nrgbd_tsdf_extract_mesh_color": (_I, [_P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _F, _P, _L, _P, _P, _L, _P, _L, _P, _P]),
+    "nrgbd_tsdf_raycast_color_f32": (_I, [_P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P, _P, _F, _F, _F, _F, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P]),
     "nrgbd_nhwc_stats_workgroups": (_I, [_L]),
     "nrgbd_nhwc_stats": (_I, [_P, _L, _I, _P, _P]),
     "nrgbd_nhwc_act": (_I, [_P, _P, _I, _P, _P, _I, _P, _L, _I, _I, _P]),

@@ -17,6 +17,17 @@
 //                             Resources (kernel-resource-usage remarks, gfx950, -O3): VEC 56 VGPRs, element form 28, 8 waves per
 //                             SIMD, no scratch, no LDS (the extraction kernels: 18 / 46 / 42 VGPRs, no scratch); two IEEE
 //                             divisions for the projection, one for t and one for the average per updated voxel.
+// tsdf_integrate_kernel<VEC, TsdfColour>  the same kernel with the colour arguments (nrgbd_tsdf_integrate_color_f32): for a voxel that
+//                             is updated, the pixel of the colour image it projects to (the quotients xc / zc, yc / zc of the depth
+//                             projection, the image's own intrinsics, clamped into the image) goes through the affine and, when its
+//                             three values are finite, into the running average of the three colour planes with the OLD weight; the
+//                             image is read only for voxels that passed every test, a group that updates nothing touches no plane, and
+//                             a group with an update loads and stores five planes (5 x 16 bytes per lane in the VEC form, which also
+//                             needs the colour planes 16-byte aligned).  The colour arguments are an optional parameter pack: without
+//                             them (Colour... empty) COLOR is false and the kernel is the instruction stream it was before colour.
+//                             Resources (kernel-resource-usage remarks, gfx950, -O3): VEC 94 VGPRs (5 waves per SIMD), element form
+//                             53 (7 waves); ScratchSize 0, no LDS; three more IEEE divisions per updated voxel.  The coloured point
+//                             writer: 50 VGPRs, no scratch.
 // tsdf_extract_kernel<false>  surface crossings per workgroup of kExtractVoxels consecutive voxels (linear index order)
 // tsdf_scan_kernel            one workgroup: exclusive prefix of those counts in index order, kScanPass records per pass with a
 //                             carried total (int64), then (crossings found, points written) into the caller's int64 [2]
@@ -52,16 +63,32 @@ __device__ __forceinline__ TsdfRow tsdf_row(const TsdfFrame& f, int iy, int iz) 
     return r;
 }
 
-// The chain of include/nrgbd.h up to t and w for lattice column ix of a row; false: the voxel is skipped.
+// The colour image of nrgbd_tsdf_integrate_color_f32: its size and intrinsics, the affine c = image * a + b per channel.
+struct TsdfImage {
+    float fx, fy, cx, cy;
+    float a[3], b[3];
+    int H, W;
+    size_t volume;                      // X Y Z: the distance between two colour planes
+};
+
+// The chain of include/nrgbd.h up to t and w for lattice column ix of a row; false: the voxel is skipped.  COLOR: the two quotients of
+// the projection as well (xq = xc / zc, yq = yc / zc: the colour image is projected with the same ones).
+template <bool COLOR>
 __device__ __forceinline__ bool tsdf_observe(const TsdfFrame& f, const TsdfRow& row, int ix, const float* __restrict__ depth,
-                                             const float* __restrict__ gate, const float* __restrict__ wmap, float& t, float& w) {
+                                             const float* __restrict__ gate, const float* __restrict__ wmap, float& t, float& w,
+                                             float& xq, float& yq) {
     const float xw = f.ox + f.vs * (float)ix;
     const float xc = ((f.r[0] * xw + row.bx) + row.cx) + f.r[3];
     const float yc = ((f.r[4] * xw + row.by) + row.cy) + f.r[7];
     const float zc = ((f.r[8] * xw + row.bz) + row.cz) + f.r[11];
     if (!(zc > 0.f)) return false;
-    const float u = f.fx * (xc / zc) + f.cx;
-    const float v = f.fy * (yc / zc) + f.cy;
+    const float xz = xc / zc, yz = yc / zc;
+    const float u = f.fx * xz + f.cx;
+    const float v = f.fy * yz + f.cy;
+    if (COLOR) {
+        xq = xz;
+        yq = yz;
+    }
     if (!(u >= 0.f && u < (float)f.W && v >= 0.f && v < (float)f.H)) return false;       // a NaN fails
     const int iu = (int)floorf(u), iv = (int)floorf(v);                                  // 0 <= iu < W, 0 <= iv < H
     const size_t p = (size_t)iv * (size_t)f.W + (size_t)iu;
@@ -81,11 +108,44 @@ __device__ __forceinline__ void tsdf_average(float& T, float& Wt, float t, float
     Wt = fminf(Wt + w, w_max);
 }
 
+// The pixel of the colour image a voxel sees (clamped into the image: colour never vetoes a distance update), through the affine.
+// false: one of the three values is not finite and the voxel's colour keeps its bits.
+__device__ __forceinline__ bool tsdf_colour(const TsdfImage& m, const float* __restrict__ image, float xq, float yq, float (&c)[3]) {
+    float uc = m.fx * xq + m.cx;
+    float vc = m.fy * yq + m.cy;
+    uc = fminf(fmaxf(uc, 0.f), (float)(m.W - 1));
+    vc = fminf(fmaxf(vc, 0.f), (float)(m.H - 1));
+    const int icu = (int)floorf(uc), icv = (int)floorf(vc);
+    const size_t plane = (size_t)m.H * (size_t)m.W;
+    const float* px = image + ((size_t)icv * (size_t)m.W + (size_t)icu);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) c[j] = px[j * plane] * m.a[j] + m.b[j];
+    return fabsf(c[0]) <= kFltMax && fabsf(c[1]) <= kFltMax && fabsf(c[2]) <= kFltMax;                // a NaN fails
+}
+
+// C' = (C * Wt + c * w) / (Wt + w) with the OLD Wt: the denominator of T'
+__device__ __forceinline__ float tsdf_blend(float C, float Wt, float c, float w) { return (C * Wt + c * w) / (Wt + w); }
+
+// The coloured form's further kernel arguments; the colourless form has none (an empty pack: the kernel it was before colour).
+struct TsdfColour {
+    float* color;                       // [3][Z][Y][X]
+    const float* image;                 // [3][Hc][Wc]
+    TsdfImage m;
+};
+
+__device__ __forceinline__ TsdfColour tsdf_colour_args() { return TsdfColour(); }
+__device__ __forceinline__ const TsdfColour& tsdf_colour_args(const TsdfColour& k) { return k; }
+
 // block (64, 4): threadIdx.x walks x (groups of four voxels, or voxels), threadIdx.y rows; blockIdx.y / .z stride over rows and slices
-template <bool VEC>
+template <bool VEC, class... Colour>
 __global__ __launch_bounds__(256) void tsdf_integrate_kernel(float* __restrict__ tsdf, float* __restrict__ weight,
                                                              const float* __restrict__ depth, const float* __restrict__ gate,
-                                                             const float* __restrict__ wmap, const TsdfFrame f) {
+                                                             const float* __restrict__ wmap, const TsdfFrame f, const Colour... colour) {
+    constexpr bool COLOR = sizeof...(Colour) != 0;
+    const TsdfColour k = tsdf_colour_args(colour...);
+    float* __restrict__ const color = k.color;
+    const float* __restrict__ const image = k.image;
+    const TsdfImage& m = k.m;
     const long at = (long)(VEC ? (f.x0 >> 2) : f.x0) + (long)(blockIdx.x * 64 + threadIdx.x);
     if (at >= (VEC ? (long)((f.x1 + 3) >> 2) : (long)f.x1)) return;
     const int unit = (int)at;
@@ -94,19 +154,41 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(float* __restrict__
             const TsdfRow row = tsdf_row(f, iy, iz);
             const size_t base = ((size_t)iz * (size_t)f.Y + (size_t)iy) * (size_t)f.X;
             if (VEC) {
-                float t[4], w[4];
+                float t[4], w[4], xq[4], yq[4];
                 bool ok[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int ix = 4 * unit + j;
                     t[j] = 0.f;
                     w[j] = 0.f;
-                    ok[j] = ix >= f.x0 && ix < f.x1 && tsdf_observe(f, row, ix, depth, gate, wmap, t[j], w[j]);
+                    xq[j] = yq[j] = 0.f;
+                    ok[j] = ix >= f.x0 && ix < f.x1 && tsdf_observe<COLOR>(f, row, ix, depth, gate, wmap, t[j], w[j], xq[j], yq[j]);
                 }
                 if (!(ok[0] || ok[1] || ok[2] || ok[3])) continue;
                 float4* pt = reinterpret_cast<float4*>(tsdf + base) + unit;
                 float4* pw = reinterpret_cast<float4*>(weight + base) + unit;
                 float4 T = *pt, Wt = *pw;
+                if (COLOR) {                                        // with the old weights, before the average replaces them
+                    float c[4][3];
+                    bool fin[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        c[j][0] = c[j][1] = c[j][2] = 0.f;
+                        fin[j] = ok[j] && tsdf_colour(m, image, xq[j], yq[j], c[j]);
+                    }
+                    if (fin[0] || fin[1] || fin[2] || fin[3]) {
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) {
+                            float4* pc = reinterpret_cast<float4*>(color + k * m.volume + base) + unit;
+                            float4 C = *pc;
+                            if (fin[0]) C.x = tsdf_blend(C.x, Wt.x, c[0][k], w[0]);
+                            if (fin[1]) C.y = tsdf_blend(C.y, Wt.y, c[1][k], w[1]);
+                            if (fin[2]) C.z = tsdf_blend(C.z, Wt.z, c[2][k], w[2]);
+                            if (fin[3]) C.w = tsdf_blend(C.w, Wt.w, c[3][k], w[3]);
+                            *pc = C;
+                        }
+                    }
+                }
                 if (ok[0]) tsdf_average(T.x, Wt.x, t[0], w[0], f.w_max);
                 if (ok[1]) tsdf_average(T.y, Wt.y, t[1], w[1], f.w_max);
                 if (ok[2]) tsdf_average(T.z, Wt.z, t[2], w[2], f.w_max);
@@ -114,9 +196,19 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(float* __restrict__
                 *pt = T;
                 *pw = Wt;
             } else {
-                float t, w;
-                if (!tsdf_observe(f, row, unit, depth, gate, wmap, t, w)) continue;
+                float t, w, xq = 0.f, yq = 0.f;
+                if (!tsdf_observe<COLOR>(f, row, unit, depth, gate, wmap, t, w, xq, yq)) continue;
                 float T = tsdf[base + unit], Wt = weight[base + unit];
+                if (COLOR) {
+                    float c[3];
+                    if (tsdf_colour(m, image, xq, yq, c)) {
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) {
+                            float* pc = color + k * m.volume + base + unit;
+                            *pc = tsdf_blend(*pc, Wt, c[k], w);
+                        }
+                    }
+                }
                 tsdf_average(T, Wt, t, w, f.w_max);
                 tsdf[base + unit] = T;
                 weight[base + unit] = Wt;
@@ -127,10 +219,13 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(float* __restrict__
 
 // ---- extraction ---------------------------------------------------------------------------------------------------------------
 
-template <bool WRITE>
+// Colour...: nothing, or one TsdfPointColour (the third launch of nrgbd_tsdf_extract_points_color: the points and their colours)
+template <bool WRITE, class... Colour>
 __global__ __launch_bounds__(256) void tsdf_extract_kernel(const float* __restrict__ tsdf, const float* __restrict__ weight, const TsdfGrid g,
                                                            int* __restrict__ wg_count, const long long* __restrict__ wg_offset,
-                                                           float* __restrict__ points, long long capacity) {
+                                                           float* __restrict__ points, long long capacity, const Colour... colour) {
+    constexpr bool COLOR = sizeof...(Colour) != 0;
+    const TsdfPointColour k = tsdf_point_colour(colour...);
     __shared__ int lds[4];
     const unsigned long long first = tsdf_lane_first();
     TsdfLane L;
@@ -142,13 +237,55 @@ __global__ __launch_bounds__(256) void tsdf_extract_kernel(const float* __restri
     }
     int total;
     const long long pos = wg_offset[blockIdx.x] + block_exclusive_256<int>(L.mine, lds, total);
-    tsdf_lane_write<false>(g, L, first, pos, points, capacity, nullptr);
+    tsdf_lane_write<false, COLOR>(g, L, first, pos, points, capacity, nullptr, k.color, k.colors);
 }
 
 __global__ __launch_bounds__(256) void tsdf_scan_kernel(const int* __restrict__ wg_count, long long* __restrict__ wg_offset, int nwg,
                                                         long long capacity, long long* __restrict__ counts) {
     __shared__ long long lds[4];
     tsdf_scan_records(wg_count, wg_offset, nwg, capacity, counts, lds);
+}
+
+}  // namespace nrgbd
+
+namespace nrgbd {
+
+// The checks the two integrations share, in the documented order (m: the colour entry's image, else NULL), and the frame.
+static int tsdf_frame(TsdfFrame& f, int X, int Y, int Z, float ox, float oy, float oz, float voxel_size, int H, int W, const float* pose,
+                      float fx, float fy, float cx, float cy, float trunc, float d_near, float d_far, float w_max, float gate_thr,
+                      const int* box, const TsdfImage* m) {
+    const long n = tsdf_voxels(X, Y, Z);
+    if (n < 0) return (int)n;
+    if (H <= 0 || W <= 0) return NRGBD_E_SHAPE;
+    if (m && (m->H <= 0 || m->W <= 0)) return NRGBD_E_SHAPE;
+    f.x0 = f.y0 = f.z0 = 0;
+    f.x1 = X; f.y1 = Y; f.z1 = Z;
+    if (box) {
+        f.x0 = box[0]; f.y0 = box[1]; f.z0 = box[2];
+        f.x1 = box[3]; f.y1 = box[4]; f.z1 = box[5];
+        if (f.x0 < 0 || f.y0 < 0 || f.z0 < 0 || f.x1 > X || f.y1 > Y || f.z1 > Z) return NRGBD_E_SHAPE;
+        if (f.x0 >= f.x1 || f.y0 >= f.y1 || f.z0 >= f.z1) return NRGBD_E_SHAPE;
+    }
+    if (!tsdf_positive(voxel_size) || !tsdf_positive(trunc) || !tsdf_positive(w_max)) return NRGBD_E_ARG;
+    if (!(d_near < d_far)) return NRGBD_E_ARG;                   // a NaN bound included
+    if (m) {
+        const float k[10] = {m->fx, m->fy, m->cx, m->cy, m->a[0], m->a[1], m->a[2], m->b[0], m->b[1], m->b[2]};
+        for (int i = 0; i < 10; ++i)
+            if (!(fabsf(k[i]) <= kFltMax)) return NRGBD_E_ARG;   // a NaN fails
+    }
+    for (int i = 0; i < 12; ++i) f.r[i] = pose[i];
+    f.ox = ox; f.oy = oy; f.oz = oz; f.vs = voxel_size;
+    f.fx = fx; f.fy = fy; f.cx = cx; f.cy = cy;
+    f.trunc = trunc; f.d_near = d_near; f.d_far = d_far; f.w_max = w_max; f.gate_thr = gate_thr;
+    f.X = X; f.Y = Y; f.H = H; f.W = W;
+    return NRGBD_OK;
+}
+
+static dim3 tsdf_integrate_grid(const TsdfFrame& f, bool vec) {
+    const int units = vec ? (f.x1 + 3) / 4 - f.x0 / 4 : f.x1 - f.x0;
+    const int rows = f.y1 - f.y0, slices = f.z1 - f.z0;
+    return dim3((unsigned)ceil_div(units, 64), (unsigned)(ceil_div(rows, 4) < 65535 ? ceil_div(rows, 4) : 65535),
+                (unsigned)(slices < 65535 ? slices : 65535));
 }
 
 }  // namespace nrgbd
@@ -160,34 +297,47 @@ extern "C" int nrgbd_tsdf_integrate_f32(float* tsdf, float* weight, int X, int Y
                                         float w_max, const int* box, void* stream) {
     using namespace nrgbd;
     if (!tsdf || !weight || !depth || !pose) return NRGBD_E_NULL;
-    const long n = tsdf_voxels(X, Y, Z);
-    if (n < 0) return (int)n;
-    if (H <= 0 || W <= 0) return NRGBD_E_SHAPE;
     TsdfFrame f;
-    f.x0 = f.y0 = f.z0 = 0;
-    f.x1 = X; f.y1 = Y; f.z1 = Z;
-    if (box) {
-        f.x0 = box[0]; f.y0 = box[1]; f.z0 = box[2];
-        f.x1 = box[3]; f.y1 = box[4]; f.z1 = box[5];
-        if (f.x0 < 0 || f.y0 < 0 || f.z0 < 0 || f.x1 > X || f.y1 > Y || f.z1 > Z) return NRGBD_E_SHAPE;
-        if (f.x0 >= f.x1 || f.y0 >= f.y1 || f.z0 >= f.z1) return NRGBD_E_SHAPE;
-    }
-    if (!tsdf_positive(voxel_size) || !tsdf_positive(trunc) || !tsdf_positive(w_max)) return NRGBD_E_ARG;
-    if (!(d_near < d_far)) return NRGBD_E_ARG;                   // a NaN bound included
-    for (int i = 0; i < 12; ++i) f.r[i] = pose[i];
-    f.ox = ox; f.oy = oy; f.oz = oz; f.vs = voxel_size;
-    f.fx = fx; f.fy = fy; f.cx = cx; f.cy = cy;
-    f.trunc = trunc; f.d_near = d_near; f.d_far = d_far; f.w_max = w_max; f.gate_thr = gate_thr;
-    f.X = X; f.Y = Y; f.H = H; f.W = W;
+    const int rc = tsdf_frame(f, X, Y, Z, ox, oy, oz, voxel_size, H, W, pose, fx, fy, cx, cy, trunc, d_near, d_far, w_max, gate_thr, box, nullptr);
+    if (rc != NRGBD_OK) return rc;
     const bool vec = X % 4 == 0 && (((uintptr_t)tsdf | (uintptr_t)weight) & 15) == 0;
-    const int units = vec ? (f.x1 + 3) / 4 - f.x0 / 4 : f.x1 - f.x0;
-    const int rows = f.y1 - f.y0, slices = f.z1 - f.z0;
-    const dim3 grid((unsigned)ceil_div(units, 64), (unsigned)(ceil_div(rows, 4) < 65535 ? ceil_div(rows, 4) : 65535),
-                    (unsigned)(slices < 65535 ? slices : 65535));
+    const dim3 grid = tsdf_integrate_grid(f, vec);
     if (vec)
         hipLaunchKernelGGL(tsdf_integrate_kernel<true>, grid, dim3(64, 4), 0, (hipStream_t)stream, tsdf, weight, depth, gate, wmap, f);
     else
         hipLaunchKernelGGL(tsdf_integrate_kernel<false>, grid, dim3(64, 4), 0, (hipStream_t)stream, tsdf, weight, depth, gate, wmap, f);
+    NRGBD_CHECK_LAUNCH();
+    return NRGBD_OK;
+}
+
+// no counterpart in the reference: the same launch with the frame's colour averaged into three more planes
+extern "C" int nrgbd_tsdf_integrate_color_f32(float* tsdf, float* weight, float* color, int X, int Y, int Z, float ox, float oy, float oz,
+                                              float voxel_size, const float* depth, const float* gate, float gate_thr, const float* wmap,
+                                              int H, int W, const float* pose, float fx, float fy, float cx, float cy, float trunc,
+                                              float d_near, float d_far, float w_max, const int* box, const float* image, int Hc, int Wc,
+                                              float fxc, float fyc, float cxc, float cyc, const float* affine, void* stream) {
+    using namespace nrgbd;
+    if (!tsdf || !weight || !depth || !pose || !color || !image || !affine) return NRGBD_E_NULL;
+    TsdfImage m;
+    m.fx = fxc; m.fy = fyc; m.cx = cxc; m.cy = cyc;
+    for (int j = 0; j < 3; ++j) {
+        m.a[j] = affine[j];
+        m.b[j] = affine[3 + j];
+    }
+    m.H = Hc; m.W = Wc;
+    m.volume = (size_t)(X > 0 ? X : 0) * (size_t)(Y > 0 ? Y : 0) * (size_t)(Z > 0 ? Z : 0);
+    TsdfFrame f;
+    const int rc = tsdf_frame(f, X, Y, Z, ox, oy, oz, voxel_size, H, W, pose, fx, fy, cx, cy, trunc, d_near, d_far, w_max, gate_thr, box, &m);
+    if (rc != NRGBD_OK) return rc;
+    const bool vec = X % 4 == 0 && (((uintptr_t)tsdf | (uintptr_t)weight | (uintptr_t)color) & 15) == 0;      // X % 4 == 0: every plane
+    const dim3 grid = tsdf_integrate_grid(f, vec);
+    const TsdfColour k = {color, image, m};
+    if (vec)
+        hipLaunchKernelGGL((tsdf_integrate_kernel<true, TsdfColour>), grid, dim3(64, 4), 0, (hipStream_t)stream, tsdf, weight, depth, gate,
+                           wmap, f, k);
+    else
+        hipLaunchKernelGGL((tsdf_integrate_kernel<false, TsdfColour>), grid, dim3(64, 4), 0, (hipStream_t)stream, tsdf, weight, depth, gate,
+                           wmap, f, k);
     NRGBD_CHECK_LAUNCH();
     return NRGBD_OK;
 }
@@ -198,11 +348,12 @@ extern "C" long nrgbd_tsdf_extract_workspace(int X, int Y, int Z) {
     return (n + nrgbd::kExtractVoxels - 1) / nrgbd::kExtractVoxels * 16;      // an int64 offset and an int32 count per workgroup
 }
 
-extern "C" int nrgbd_tsdf_extract_points(const float* tsdf, const float* weight, int X, int Y, int Z, float ox, float oy, float oz,
-                                         float voxel_size, float w_min, void* workspace, long workspace_bytes, float* points,
-                                         long capacity, long long* counts, void* stream) {
-    using namespace nrgbd;
-    if (!tsdf || !weight || !workspace || !counts || (!points && capacity > 0)) return NRGBD_E_NULL;
+namespace nrgbd {
+
+// nrgbd_tsdf_extract_points and its coloured form: the same checks, launches, workspace and counts (color NULL: the points alone)
+static int tsdf_extract_launch(const float* tsdf, const float* weight, const float* color, int X, int Y, int Z, float ox, float oy, float oz,
+                               float voxel_size, float w_min, void* workspace, long workspace_bytes, float* points, float* colors,
+                               long capacity, long long* counts, void* stream) {
     const long n = tsdf_voxels(X, Y, Z);
     if (n < 0) return (int)n;
     if (capacity < 0) return NRGBD_E_SHAPE;
@@ -220,9 +371,31 @@ extern "C" int nrgbd_tsdf_extract_points(const float* tsdf, const float* weight,
     hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), dim3(256), 0, st, (const int*)wg_count, wg_offset, (int)nwg, (long long)capacity, counts);
     NRGBD_CHECK_LAUNCH();
     if (capacity > 0) {
-        hipLaunchKernelGGL(tsdf_extract_kernel<true>, dim3((unsigned)nwg), dim3(256), 0, st, tsdf, weight, g, wg_count,
-                           (const long long*)wg_offset, points, (long long)capacity);
+        if (color)
+            hipLaunchKernelGGL((tsdf_extract_kernel<true, TsdfPointColour>), dim3((unsigned)nwg), dim3(256), 0, st, tsdf, weight, g, wg_count,
+                               (const long long*)wg_offset, points, (long long)capacity, TsdfPointColour{color, colors});
+        else
+            hipLaunchKernelGGL(tsdf_extract_kernel<true>, dim3((unsigned)nwg), dim3(256), 0, st, tsdf, weight, g, wg_count,
+                               (const long long*)wg_offset, points, (long long)capacity);
         NRGBD_CHECK_LAUNCH();
     }
     return NRGBD_OK;
+}
+
+}  // namespace nrgbd
+
+extern "C" int nrgbd_tsdf_extract_points(const float* tsdf, const float* weight, int X, int Y, int Z, float ox, float oy, float oz,
+                                         float voxel_size, float w_min, void* workspace, long workspace_bytes, float* points,
+                                         long capacity, long long* counts, void* stream) {
+    if (!tsdf || !weight || !workspace || !counts || (!points && capacity > 0)) return NRGBD_E_NULL;
+    return nrgbd::tsdf_extract_launch(tsdf, weight, nullptr, X, Y, Z, ox, oy, oz, voxel_size, w_min, workspace, workspace_bytes, points,
+                                      nullptr, capacity, counts, stream);
+}
+
+extern "C" int nrgbd_tsdf_extract_points_color(const float* tsdf, const float* weight, const float* color, int X, int Y, int Z, float ox,
+                                               float oy, float oz, float voxel_size, float w_min, void* workspace, long workspace_bytes,
+                                               float* points, float* colors, long capacity, long long* counts, void* stream) {
+    if (!tsdf || !weight || !color || !workspace || !counts || ((!points || !colors) && capacity > 0)) return NRGBD_E_NULL;
+    return nrgbd::tsdf_extract_launch(tsdf, weight, color, X, Y, Z, ox, oy, oz, voxel_size, w_min, workspace, workspace_bytes, points,
+                                      colors, capacity, counts, stream);
 }

@@ -99,10 +99,12 @@ __device__ __forceinline__ void tsdf_lane_crossings(const float* __restrict__ ts
 }
 
 // Writes the lane's crossings as points from row `pos` on while the row is below the capacity.  ROWS: also the row of every voxel's
-// first crossing (whether written or not, and whether the voxel has one or not) into first_row[linear voxel index].
-template <bool ROWS>
+// first crossing (whether written or not, and whether the voxel has one or not) into first_row[linear voxel index].  COLOR: also row
+// `pos` of colors, per plane j of color [3][Z][Y][X]: C_j(a) + q * (C_j(b) - C_j(a)) with the q that places the point.
+template <bool ROWS, bool COLOR = false>
 __device__ __forceinline__ void tsdf_lane_write(const TsdfGrid& g, const TsdfLane& L, unsigned long long first, long long pos,
-                                                float* __restrict__ points, long long capacity, int* __restrict__ first_row) {
+                                                float* __restrict__ points, long long capacity, int* __restrict__ first_row,
+                                                const float* __restrict__ color = nullptr, float* __restrict__ colors = nullptr) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         if (ROWS && first + j <= g.n) first_row[first + j] = (int)pos;
@@ -115,11 +117,29 @@ __device__ __forceinline__ void tsdf_lane_write(const TsdfGrid& g, const TsdfLan
                 out[0] = g.ox + g.vs * (k == 0 ? fi[0] + L.q[j][0] : fi[0]);
                 out[1] = g.oy + g.vs * (k == 1 ? fi[1] + L.q[j][1] : fi[1]);
                 out[2] = g.oz + g.vs * (k == 2 ? fi[2] + L.q[j][2] : fi[2]);
+                if (COLOR) {
+                    const size_t a = (size_t)(first + j), b = a + (k == 0 ? 1u : k == 1 ? g.X : g.XY);
+                    const size_t plane = (size_t)g.n + 1;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const float Ca = color[c * plane + a], Cb = color[c * plane + b];
+                        colors[3 * pos + c] = Ca + L.q[j][k] * (Cb - Ca);
+                    }
+                }
             }
             ++pos;
         }
     }
 }
+
+// The coloured writers' further kernel arguments; the colourless kernels take none (an empty pack: the kernels they were before colour).
+struct TsdfPointColour {
+    const float* color;                 // the volume's planes [3][Z][Y][X]
+    float* colors;                      // [capacity][3]
+};
+
+__device__ __forceinline__ TsdfPointColour tsdf_point_colour() { return TsdfPointColour(); }
+__device__ __forceinline__ const TsdfPointColour& tsdf_point_colour(const TsdfPointColour& k) { return k; }
 
 // One workgroup: the exclusive prefix of nwg count records in index order, kScanPass records per pass with a carried total (int64),
 // then (found, written = min(found, capacity)) into counts[0..1].

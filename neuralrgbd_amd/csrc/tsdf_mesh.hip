@@ -9,7 +9,8 @@
 // tsdf_mesh_count_kernel   crossings and triangles per workgroup
 // tsdf_mesh_scan_kernel    two workgroups: the exclusive prefix of either count sequence (tsdf_scan_records), then
 //                          (vertices found, written, triangles found, written) into the caller's int64 [4]
-// tsdf_mesh_vertex_kernel  the points, and for EVERY voxel the row of its first crossing into first_row[voxel] (int32, workspace)
+// tsdf_mesh_vertex_kernel  the points, and for EVERY voxel the row of its first crossing into first_row[voxel] (int32, workspace);
+//                          <TsdfPointColour>: the vertices' colours as well (nrgbd_tsdf_extract_mesh_color; 52 VGPRs, no scratch)
 // tsdf_mesh_face_kernel    per valid cell the case's triangles at `offset of the workgroup + rank inside it`; the row of the vertex on
 //                          edge (voxel v, axis k) is first_row[v] + popc(crossings(v) & ((1 << k) - 1)) with the crossings of v
 //                          re-evaluated by tsdf_crossings.  A lane forms the rows of a cell's sign-changing edges into its own
@@ -99,16 +100,20 @@ __global__ __launch_bounds__(256) void tsdf_mesh_scan_kernel(const int* __restri
     tsdf_scan_records(wg_count + s * nwg, wg_offset + s * nwg, nwg, s ? face_capacity : vertex_capacity, counts + 2 * s, lds);
 }
 
+// Colour...: nothing, or one TsdfPointColour (nrgbd_tsdf_extract_mesh_color: the vertices' colours as well)
+template <class... Colour>
 __global__ __launch_bounds__(256) void tsdf_mesh_vertex_kernel(const float* __restrict__ tsdf, const float* __restrict__ weight, const TsdfGrid g,
                                                                const long long* __restrict__ wg_offset, float* __restrict__ points,
-                                                               long long capacity, int* __restrict__ first_row) {
+                                                               long long capacity, int* __restrict__ first_row, const Colour... colour) {
+    constexpr bool COLOR = sizeof...(Colour) != 0;
+    const TsdfPointColour k = tsdf_point_colour(colour...);
     __shared__ int lds[4];
     const unsigned long long first = tsdf_lane_first();
     TsdfLane L;
     tsdf_lane_crossings(tsdf, weight, g, first, L);
     int total;
     const long long pos = wg_offset[blockIdx.x] + block_exclusive_256<int>(L.mine, lds, total);
-    tsdf_lane_write<true>(g, L, first, pos, points, capacity, first_row);
+    tsdf_lane_write<true, COLOR>(g, L, first, pos, points, capacity, first_row, k.color, k.colors);
 }
 
 __global__ __launch_bounds__(256) void tsdf_mesh_face_kernel(const float* __restrict__ tsdf, const float* __restrict__ weight, const TsdfGrid g,
@@ -202,12 +207,12 @@ extern "C" long nrgbd_tsdf_mesh_workspace(int X, int Y, int Z) {
     return nrgbd::mesh_workspace_bytes(n);
 }
 
-// no counterpart in the reference: see the header of this file and include/nrgbd.h
-extern "C" int nrgbd_tsdf_extract_mesh(const float* tsdf, const float* weight, int X, int Y, int Z, float ox, float oy, float oz,
-                                       float voxel_size, float w_min, void* workspace, long workspace_bytes, float* vertices,
-                                       long vertex_capacity, int* faces, long face_capacity, long long* counts, void* stream) {
-    using namespace nrgbd;
-    if (!tsdf || !weight || !workspace || !counts || (!vertices && vertex_capacity > 0) || (!faces && face_capacity > 0)) return NRGBD_E_NULL;
+namespace nrgbd {
+
+// nrgbd_tsdf_extract_mesh and its coloured form: the same checks, launches, workspace and counts (color NULL: no colours)
+static int tsdf_mesh_launch(const float* tsdf, const float* weight, const float* color, int X, int Y, int Z, float ox, float oy, float oz,
+                            float voxel_size, float w_min, void* workspace, long workspace_bytes, float* vertices, float* colors,
+                            long vertex_capacity, int* faces, long face_capacity, long long* counts, void* stream) {
     const long n = mesh_voxels(X, Y, Z);
     if (n < 0) return (int)n;
     if (vertex_capacity < 0 || face_capacity < 0) return NRGBD_E_SHAPE;
@@ -226,8 +231,12 @@ extern "C" int nrgbd_tsdf_extract_mesh(const float* tsdf, const float* weight, i
                        (long long)face_capacity, counts);
     NRGBD_CHECK_LAUNCH();
     if (vertex_capacity > 0 || face_capacity > 0) {            // the triangles need every voxel's first row, written or not
-        hipLaunchKernelGGL(tsdf_mesh_vertex_kernel, dim3((unsigned)nwg), dim3(256), 0, st, tsdf, weight, g, (const long long*)wg_offset,
-                           vertices, (long long)vertex_capacity, first_row);
+        if (color)                                              // capacity 0: no row is below it, neither output is touched
+            hipLaunchKernelGGL(tsdf_mesh_vertex_kernel<TsdfPointColour>, dim3((unsigned)nwg), dim3(256), 0, st, tsdf, weight, g,
+                               (const long long*)wg_offset, vertices, (long long)vertex_capacity, first_row, TsdfPointColour{color, colors});
+        else
+            hipLaunchKernelGGL(tsdf_mesh_vertex_kernel<>, dim3((unsigned)nwg), dim3(256), 0, st, tsdf, weight, g, (const long long*)wg_offset,
+                               vertices, (long long)vertex_capacity, first_row);
         NRGBD_CHECK_LAUNCH();
     }
     if (face_capacity > 0) {
@@ -236,4 +245,26 @@ extern "C" int nrgbd_tsdf_extract_mesh(const float* tsdf, const float* weight, i
         NRGBD_CHECK_LAUNCH();
     }
     return NRGBD_OK;
+}
+
+}  // namespace nrgbd
+
+// no counterpart in the reference: see the header of this file and include/nrgbd.h
+extern "C" int nrgbd_tsdf_extract_mesh(const float* tsdf, const float* weight, int X, int Y, int Z, float ox, float oy, float oz,
+                                       float voxel_size, float w_min, void* workspace, long workspace_bytes, float* vertices,
+                                       long vertex_capacity, int* faces, long face_capacity, long long* counts, void* stream) {
+    if (!tsdf || !weight || !workspace || !counts || (!vertices && vertex_capacity > 0) || (!faces && face_capacity > 0)) return NRGBD_E_NULL;
+    return nrgbd::tsdf_mesh_launch(tsdf, weight, nullptr, X, Y, Z, ox, oy, oz, voxel_size, w_min, workspace, workspace_bytes, vertices, nullptr,
+                                   vertex_capacity, faces, face_capacity, counts, stream);
+}
+
+extern "C" int nrgbd_tsdf_extract_mesh_color(const float* tsdf, const float* weight, const float* color, int X, int Y, int Z, float ox,
+                                             float oy, float oz, float voxel_size, float w_min, void* workspace, long workspace_bytes,
+                                             float* vertices, float* colors, long vertex_capacity, int* faces, long face_capacity,
+                                             long long* counts, void* stream) {
+    if (!tsdf || !weight || !color || !workspace || !counts || ((!vertices || !colors) && vertex_capacity > 0) ||
+        (!faces && face_capacity > 0))
+        return NRGBD_E_NULL;
+    return nrgbd::tsdf_mesh_launch(tsdf, weight, color, X, Y, Z, ox, oy, oz, voxel_size, w_min, workspace, workspace_bytes, vertices, colors,
+                                   vertex_capacity, faces, face_capacity, counts, stream);
 }

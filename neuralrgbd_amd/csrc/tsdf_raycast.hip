@@ -13,6 +13,10 @@
 //                              and the wave leaves the loop when none of its lanes has a sample left (hit, past z1, or k at the cap).
 //                              Bound by the latency of two dependent groups of gathered loads per sample, not by bytes: no LDS, no
 //                              scratch (kernel-resource-usage, gfx950, -O3: 42 VGPRs with and without normals).
+// tsdf_raycast_kernel<NORMAL, TsdfRayColour>  the same march, and at a hit whose cell passes the weight test (the normal's rule) the
+//                              trilinear interpolant of the three colour planes, 24 more gathered loads; (0, 0, 0) elsewhere.  The
+//                              colour arguments are an optional parameter pack: without them the kernel is the instruction stream it
+//                              was before colour.  44 VGPRs with normals, 46 without, no scratch.
 #include "common.hpp"
 
 namespace nrgbd {
@@ -77,9 +81,30 @@ __device__ __forceinline__ bool ray_slab(float go, float gd, int n, float& z0, f
     return go >= 0.f && go <= last;
 }
 
-template <bool NORMAL>
+// The trilinear interpolant of eight corners, the nesting T uses: x, then y, then z.
+__device__ __forceinline__ float ray_trilinear(const float (&t)[8], const TsdfCell& c) {
+    const float c00 = ray_lerp(t[0], t[1], c.fx), c10 = ray_lerp(t[2], t[3], c.fx);
+    const float c01 = ray_lerp(t[4], t[5], c.fx), c11 = ray_lerp(t[6], t[7], c.fx);
+    return ray_lerp(ray_lerp(c00, c10, c.fy), ray_lerp(c01, c11, c.fy), c.fz);
+}
+
+// The coloured form's further kernel arguments; the colourless form has none (an empty pack: the kernel it was before colour).
+struct TsdfRayColour {
+    const float* color;                 // the volume's planes [3][Z][Y][X]
+    float* rgb;                         // [3][H][W]
+};
+
+__device__ __forceinline__ TsdfRayColour ray_colour() { return TsdfRayColour(); }
+__device__ __forceinline__ const TsdfRayColour& ray_colour(const TsdfRayColour& k) { return k; }
+
+template <bool NORMAL, class... Colour>
 __global__ __launch_bounds__(256) void tsdf_raycast_kernel(const float* __restrict__ tsdf, const float* __restrict__ weight,
-                                                           float* __restrict__ depth, float* __restrict__ normal, const TsdfView v) {
+                                                           float* __restrict__ depth, float* __restrict__ normal, const TsdfView v,
+                                                           const Colour... colour) {
+    constexpr bool COLOR = sizeof...(Colour) != 0;
+    const TsdfRayColour k = ray_colour(colour...);
+    const float* __restrict__ const color = k.color;
+    float* __restrict__ const rgb = k.rgb;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int px = (int)blockIdx.x * kRaycastTile + (wave & 1) * 8 + (lane & 7);
     const int py = (int)blockIdx.y * kRaycastTile + (wave >> 1) * 8 + (lane >> 3);
@@ -140,8 +165,9 @@ __global__ __launch_bounds__(256) void tsdf_raycast_kernel(const float* __restri
     if (!pixel) return;
     const size_t at = (size_t)py * (size_t)v.W + (size_t)px;
     depth[at] = hit;                                                // 0: no surface
-    if (!NORMAL) return;
+    if (!NORMAL && !COLOR) return;
     float nx = 0.f, ny = 0.f, nz = 0.f;
+    float col[3] = {0.f, 0.f, 0.f};
     if (found) {
         const float hx = gox + hit * gdx, hy = goy + hit * gdy, hz = goz + hit * gdz;
         if (ray_inside(v, hx, hy, hz)) {
@@ -149,25 +175,43 @@ __global__ __launch_bounds__(256) void tsdf_raycast_kernel(const float* __restri
             float w[8];
             ray_corners(weight, c.base, sy, sz, w);
             if (ray_observed(w, v.w_min)) {
-                float t[8];
-                ray_corners(tsdf, c.base, sy, sz, t);
-                const float gx = ray_lerp(ray_lerp(t[1] - t[0], t[3] - t[2], c.fy), ray_lerp(t[5] - t[4], t[7] - t[6], c.fy), c.fz);
-                const float gy = ray_lerp(ray_lerp(t[2] - t[0], t[3] - t[1], c.fx), ray_lerp(t[6] - t[4], t[7] - t[5], c.fx), c.fz);
-                const float gz = ray_lerp(ray_lerp(t[4] - t[0], t[5] - t[1], c.fx), ray_lerp(t[6] - t[2], t[7] - t[3], c.fx), c.fy);
-                const float g = sqrtf((gx * gx + gy * gy) + gz * gz);
-                if (g > 0.f && g <= kRayFltMax) {                    // a NaN fails
-                    const float ux = gx / g, uy = gy / g, uz = gz / g;
-                    nx = (v.r[0] * ux + v.r[1] * uy) + v.r[2] * uz;
-                    ny = (v.r[4] * ux + v.r[5] * uy) + v.r[6] * uz;
-                    nz = (v.r[8] * ux + v.r[9] * uy) + v.r[10] * uz;
+                if (NORMAL) {
+                    float t[8];
+                    ray_corners(tsdf, c.base, sy, sz, t);
+                    const float gx = ray_lerp(ray_lerp(t[1] - t[0], t[3] - t[2], c.fy), ray_lerp(t[5] - t[4], t[7] - t[6], c.fy), c.fz);
+                    const float gy = ray_lerp(ray_lerp(t[2] - t[0], t[3] - t[1], c.fx), ray_lerp(t[6] - t[4], t[7] - t[5], c.fx), c.fz);
+                    const float gz = ray_lerp(ray_lerp(t[4] - t[0], t[5] - t[1], c.fx), ray_lerp(t[6] - t[2], t[7] - t[3], c.fx), c.fy);
+                    const float g = sqrtf((gx * gx + gy * gy) + gz * gz);
+                    if (g > 0.f && g <= kRayFltMax) {                    // a NaN fails
+                        const float ux = gx / g, uy = gy / g, uz = gz / g;
+                        nx = (v.r[0] * ux + v.r[1] * uy) + v.r[2] * uz;
+                        ny = (v.r[4] * ux + v.r[5] * uy) + v.r[6] * uz;
+                        nz = (v.r[8] * ux + v.r[9] * uy) + v.r[10] * uz;
+                    }
+                }
+                if (COLOR) {                                         // whatever the gradient is
+                    const size_t volume = sz * (size_t)v.Z;
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) {
+                        float t[8];
+                        ray_corners(color + j * volume, c.base, sy, sz, t);
+                        col[j] = ray_trilinear(t, c);
+                    }
                 }
             }
         }
     }
     const size_t plane = (size_t)v.H * (size_t)v.W;
-    normal[at] = nx;
-    normal[plane + at] = ny;
-    normal[2 * plane + at] = nz;
+    if (NORMAL) {
+        normal[at] = nx;
+        normal[plane + at] = ny;
+        normal[2 * plane + at] = nz;
+    }
+    if (COLOR) {
+        rgb[at] = col[0];
+        rgb[plane + at] = col[1];
+        rgb[2 * plane + at] = col[2];
+    }
 }
 
 static bool ray_finite(float x) { return x >= -kRayFltMax && x <= kRayFltMax; }
@@ -175,19 +219,16 @@ static bool ray_positive(float x) { return x > 0.f && x <= kRayFltMax; }
 
 }  // namespace nrgbd
 
-// no counterpart in the reference: see the header of this file and include/nrgbd.h
-extern "C" int nrgbd_tsdf_raycast_f32(const float* tsdf, const float* weight, int X, int Y, int Z, float ox, float oy, float oz,
-                                      float voxel_size, const float* pose, const float* centre, float fx, float fy, float cx, float cy,
-                                      int H, int W, float d_near, float d_far, float w_min, float step, float* depth, float* normal,
-                                      void* stream) {
-    using namespace nrgbd;
-    if (!tsdf || !weight || !pose || !centre || !depth) return NRGBD_E_NULL;
+namespace nrgbd {
+
+// The checks nrgbd_tsdf_raycast_f32 and its coloured form share, in the documented order, and the view.
+static int ray_view(TsdfView& v, int X, int Y, int Z, float ox, float oy, float oz, float voxel_size, const float* pose, const float* centre,
+                    float fx, float fy, float cx, float cy, int H, int W, float d_near, float d_far, float w_min, float step) {
     if (X <= 0 || Y <= 0 || Z <= 0 || H <= 0 || W <= 0) return NRGBD_E_SHAPE;
     if ((long)X * Y > kRaycastMaxVoxels || (long)X * Y * Z > kRaycastMaxVoxels) return NRGBD_E_SHAPE;
     if (H > NRGBD_TSDF_RAYCAST_MAX_SIDE || W > NRGBD_TSDF_RAYCAST_MAX_SIDE) return NRGBD_E_SHAPE;
     if (!ray_positive(voxel_size) || !ray_positive(step) || !ray_positive(fx) || !ray_positive(fy)) return NRGBD_E_ARG;
     if (!(d_near < d_far) || w_min != w_min) return NRGBD_E_ARG;    // a NaN bound included
-    TsdfView v;
     for (int i = 0; i < 12; ++i) {
         if (!ray_finite(pose[i])) return NRGBD_E_ARG;
         v.r[i] = pose[i];
@@ -200,11 +241,47 @@ extern "C" int nrgbd_tsdf_raycast_f32(const float* tsdf, const float* weight, in
     v.fx = fx; v.fy = fy; v.cx = cx; v.cy = cy;
     v.d_near = d_near; v.d_far = d_far; v.w_min = w_min; v.step = step;
     v.X = X; v.Y = Y; v.Z = Z; v.H = H; v.W = W;
+    return NRGBD_OK;
+}
+
+}  // namespace nrgbd
+
+// no counterpart in the reference: see the header of this file and include/nrgbd.h
+extern "C" int nrgbd_tsdf_raycast_f32(const float* tsdf, const float* weight, int X, int Y, int Z, float ox, float oy, float oz,
+                                      float voxel_size, const float* pose, const float* centre, float fx, float fy, float cx, float cy,
+                                      int H, int W, float d_near, float d_far, float w_min, float step, float* depth, float* normal,
+                                      void* stream) {
+    using namespace nrgbd;
+    if (!tsdf || !weight || !pose || !centre || !depth) return NRGBD_E_NULL;
+    TsdfView v;
+    const int rc = ray_view(v, X, Y, Z, ox, oy, oz, voxel_size, pose, centre, fx, fy, cx, cy, H, W, d_near, d_far, w_min, step);
+    if (rc != NRGBD_OK) return rc;
     const dim3 grid((unsigned)ceil_div(W, kRaycastTile), (unsigned)ceil_div(H, kRaycastTile));
     if (normal)
         hipLaunchKernelGGL(tsdf_raycast_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, tsdf, weight, depth, normal, v);
     else
         hipLaunchKernelGGL(tsdf_raycast_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, tsdf, weight, depth, normal, v);
+    NRGBD_CHECK_LAUNCH();
+    return NRGBD_OK;
+}
+
+// no counterpart in the reference: the same march, and the trilinear colour at the hit
+extern "C" int nrgbd_tsdf_raycast_color_f32(const float* tsdf, const float* weight, const float* color, int X, int Y, int Z, float ox,
+                                            float oy, float oz, float voxel_size, const float* pose, const float* centre, float fx,
+                                            float fy, float cx, float cy, int H, int W, float d_near, float d_far, float w_min, float step,
+                                            float* depth, float* normal, float* rgb, void* stream) {
+    using namespace nrgbd;
+    if (!tsdf || !weight || !pose || !centre || !depth || !color || !rgb) return NRGBD_E_NULL;
+    TsdfView v;
+    const int rc = ray_view(v, X, Y, Z, ox, oy, oz, voxel_size, pose, centre, fx, fy, cx, cy, H, W, d_near, d_far, w_min, step);
+    if (rc != NRGBD_OK) return rc;
+    const dim3 grid((unsigned)ceil_div(W, kRaycastTile), (unsigned)ceil_div(H, kRaycastTile));
+    if (normal)
+        hipLaunchKernelGGL((tsdf_raycast_kernel<true, TsdfRayColour>), grid, dim3(256), 0, (hipStream_t)stream, tsdf, weight, depth, normal, v,
+                           TsdfRayColour{color, rgb});
+    else
+        hipLaunchKernelGGL((tsdf_raycast_kernel<false, TsdfRayColour>), grid, dim3(256), 0, (hipStream_t)stream, tsdf, weight, depth, normal, v,
+                           TsdfRayColour{color, rgb});
     NRGBD_CHECK_LAUNCH();
     return NRGBD_OK;
 }

@@ -13,6 +13,10 @@ conventions (lattice, projection, update rule, crossings) are written out in inc
     (ops.tsdf_raycast); `shade` turns the normals into a viewable image;
   * `TSDFVolume.mesh` / `FusionVideoStream.mesh`: the surface as an indexed triangle mesh (ops.tsdf_extract_mesh): the vertices are
     `points()`'s, the triangles come from a 256-case table and wind towards free space; `save_ply` writes it (ASCII or binary);
+  * colour: `TSDFVolume(color=True)` carries three colour planes that share the TSDF's weight; `integrate(color=image)` averages the
+    frame's pixels into them in the same launch (ops.tsdf_integrate_color), `points(colors=True)`, `mesh(colors=True)` and
+    `raycast(color=True)` read them out, and `FusionVideoStream(color=True)` fuses every frame's own picture from its ring slot;
+    `to_uint8` and `save_ply(colors=...)` write them;
   * `fuse_sequence`, `save_ply`.
 """
 import math
@@ -85,9 +89,10 @@ def frustum_box(extM, intrinsics, size, depth_max, volume):
 
 class TSDFVolume:
     """A dense TSDF volume on the device: `tsdf` and `weight`, fp32 [Z,Y,X]; lattice point (ix, iy, iz) lies at
-    origin + voxel_size (ix, iy, iz)."""
+    origin + voxel_size (ix, iy, iz).  color=True: also `color`, fp32 [3,Z,Y,X] (r, g, b), the running average of the colours of
+    exactly the observations that updated a voxel's distance, with the same weights (one buffer [5,Z,Y,X] holds all of it)."""
 
-    def __init__(self, dims, voxel_size, origin, trunc=None, w_max=64., device=None):
+    def __init__(self, dims, voxel_size, origin, trunc=None, w_max=64., device=None, color=False):
         self.dims = tuple(int(n) for n in dims)
         if len(self.dims) != 3 or min(self.dims) <= 0 or self.dims[0] * self.dims[1] * self.dims[2] > 2 ** 31:
             raise ValueError("TSDFVolume: dims = (X, Y, Z), positive, at most 2^31 voxels; got %s" % (dims,))
@@ -101,9 +106,11 @@ class TSDFVolume:
             if not (v > 0 and math.isfinite(v)):
                 raise ValueError("TSDFVolume: %s must be positive and finite, got %s" % (nm, v))
         X, Y, Z = self.dims
-        self._buf = torch.zeros((2, Z, Y, X), dtype=torch.float32, device=torch.device(device if device is not None else "cuda"))
+        self._buf = torch.zeros((5 if color else 2, Z, Y, X), dtype=torch.float32,
+                                device=torch.device(device if device is not None else "cuda"))
         self.device = self._buf.device                              # with its index: "cuda" names the current device
         self.tsdf, self.weight = self._buf[0], self._buf[1]
+        self.color = self._buf[2:5] if color else None
         self._counts = torch.zeros(2, dtype=torch.int64, device=self.device)
         self._workspace = None
         self._mesh_counts = self._mesh_workspace = None
@@ -112,12 +119,29 @@ class TSDFVolume:
         """An empty volume again (asynchronous)."""
         self._buf.zero_()
 
-    def integrate(self, depth, extM, intrinsics, gate=None, gate_thr=None, weight=None, depth_range=(0., float("inf")), cull=True):
+    def integrate(self, depth, extM, intrinsics, gate=None, gate_thr=None, weight=None, depth_range=(0., float("inf")), cull=True,
+                  color=None, color_intrinsics=None, color_affine=None):
         """One depth frame: depth [H,W] (or [1,H,W]) CUDA fp32 z-depth in metres; extM: the host [4,4] world -> camera matrix
         (VideoDepthStream.push's), used as float32(extM[:3,:4]); intrinsics: (fx, fy, cx, cy) at the map's size, or a cam_intrinsics
         dict (intrinsics_at); gate / gate_thr: a pixel counts where gate >= gate_thr; weight: a per-pixel weight map (default 1);
         depth_range = (d_near, d_far]; cull: launch over frustum_box alone (the same bits).  Returns False when the box is empty and
-        nothing was launched.  Allocates nothing and synchronises nothing."""
+        nothing was launched.  Allocates nothing and synchronises nothing.
+        A colour volume takes color: the frame's picture, CUDA fp32 [3,Hc,Wc] at any size (a volume without colour refuses one; a
+        colour volume refuses a frame without: the shared weight would go out of step with the colour); color_intrinsics:
+        (fx, fy, cx, cy) at that size — by default intrinsics_at when `intrinsics` is a dict, or the depth map's when the sizes are
+        equal; color_affine = (a [3], b [3]): a pixel's colour is image * a + b per channel (default a = 1, b = 0)."""
+        if (color is None) != (self.color is None):
+            raise ValueError("TSDFVolume.integrate: a colour volume is integrated with a colour image (the weight is shared), a volume "
+                             "without colour without one")
+        if color is None and (color_intrinsics is not None or color_affine is not None):
+            raise ValueError("TSDFVolume.integrate: color_intrinsics / color_affine come with color")
+        if color is not None:
+            if not isinstance(color, torch.Tensor) or color.dtype != torch.float32:
+                raise TypeError("TSDFVolume.integrate: color is an fp32 tensor [3,Hc,Wc]")
+            if color.dim() != 3 or color.shape[0] != 3 or color.shape[1] < 1 or color.shape[2] < 1:
+                raise ValueError("TSDFVolume.integrate: color is [3,Hc,Wc], got %s" % (tuple(color.shape),))
+            if color.device != self.device or not color.is_contiguous():
+                raise ValueError("TSDFVolume.integrate: color must be contiguous and on %s" % (self.device,))
         if depth.dim() == 3 and depth.shape[0] == 1:
             depth = depth[0]
             gate = gate if gate is None else gate.view(depth.shape)
@@ -125,8 +149,18 @@ class TSDFVolume:
         if depth.dim() != 2:
             raise ValueError("TSDFVolume.integrate: depth is [H,W], got %s" % (tuple(depth.shape),))
         H, W = depth.shape
+        if color is not None and color_intrinsics is None:
+            if isinstance(intrinsics, dict):
+                color_intrinsics = intrinsics_at(intrinsics, color.shape[1], color.shape[2])
+            elif tuple(color.shape[1:]) != (H, W):
+                raise ValueError("TSDFVolume.integrate: a %d x %d colour image beside a %d x %d depth map needs color_intrinsics"
+                                 % (color.shape[1], color.shape[2], H, W))
+        if isinstance(color_intrinsics, dict):
+            color_intrinsics = intrinsics_at(color_intrinsics, color.shape[1], color.shape[2])
         if isinstance(intrinsics, dict):
             intrinsics = intrinsics_at(intrinsics, H, W)
+        if color is not None and color_intrinsics is None:
+            color_intrinsics = intrinsics
         if (gate is None) != (gate_thr is None):
             raise ValueError("TSDFVolume.integrate: gate and gate_thr come together")
         m = _host_matrix(extM, "TSDFVolume.integrate")
@@ -135,14 +169,27 @@ class TSDFVolume:
             box = frustum_box(m, intrinsics, (H, W), float(depth_range[1]) + self.trunc, self)
             if box is None:
                 return False
+        if color is not None:
+            ops.tsdf_integrate_color(self.tsdf, self.weight, self.color, self.origin, self.voxel_size, depth, m, intrinsics, self.trunc, color,
+                                     color_intrinsics, color_affine, depth_range, self.w_max, gate=gate,
+                                     gate_thr=0.0 if gate_thr is None else gate_thr, wmap=weight, box=box)
+            return True
         ops.tsdf_integrate(self.tsdf, self.weight, self.origin, self.voxel_size, depth, m, intrinsics, self.trunc, depth_range, self.w_max,
                            gate=gate, gate_thr=0.0 if gate_thr is None else gate_thr, wmap=weight, box=box)
         return True
 
-    def points(self, w_min=1., capacity=None):
+    def _need_color(self, who):
+        if self.color is None:
+            raise ValueError("TSDFVolume.%s: the volume has no colour (TSDFVolume(..., color=True))" % who)
+        return self.color
+
+    def points(self, w_min=1., capacity=None, colors=False):
         """The zero crossings between lattice neighbours whose weights are >= w_min, as ([n,3] CUDA fp32 world points in ascending
         (linear voxel index, axis) order, crossings found).  capacity=None: counts first, then writes every point; else the first
-        min(found, capacity).  Reads the count back: the one place this object synchronises (and allocates)."""
+        min(found, capacity).  colors=True (a colour volume): (points, colors [n,3] CUDA fp32 — row p the colour of point p, the
+        two voxels' colours interpolated at the crossing —, found).  Reads the count back: the one place this object synchronises
+        (and allocates)."""
+        color = self._need_color("points") if colors else None
         if self._workspace is None:
             self._workspace = torch.empty(ops.tsdf_extract_workspace(*self.dims) // 8, dtype=torch.int64, device=self.device)
         args = (self.tsdf, self.weight, self.origin, self.voxel_size, w_min, self._workspace)
@@ -153,17 +200,24 @@ class TSDFVolume:
         if capacity < 0:
             raise ValueError("TSDFVolume.points: capacity %d" % capacity)
         out = torch.empty((capacity, 3), dtype=torch.float32, device=self.device)
+        if colors:
+            rgb = torch.empty((capacity, 3), dtype=torch.float32, device=self.device)
+            ops.tsdf_extract_points(*args, out if capacity else None, self._counts, color=color, colors=rgb if capacity else None)
+            found, written = (int(v) for v in self._counts.cpu())
+            return out[:written], rgb[:written], found
         ops.tsdf_extract_points(*args, out if capacity else None, self._counts)
         found, written = (int(v) for v in self._counts.cpu())
         return out[:written], found
 
-    def mesh(self, w_min=1., capacity=None):
+    def mesh(self, w_min=1., capacity=None, colors=False):
         """The surface as an indexed triangle mesh: (vertices [n,3] CUDA fp32, faces [m,3] CUDA int32, (vertices found, triangles
         found)).  The vertices are exactly `points(w_min)` in its order; a cell whose eight corners all have weight >= w_min and
         |T| < 1 emits the triangles of its sign case (at most 5, the normal towards free space, ascending cell order); a face holds
         the rows of its vertices in the FULL vertex sequence, whatever the vertex capacity.  capacity=None: counts first, then
-        writes everything; capacity=(nv, nf): the first min(found, capacity) rows of either.  Reads the counts back: like `points`,
-        the one place this object synchronises (and allocates)."""
+        writes everything; capacity=(nv, nf): the first min(found, capacity) rows of either.  colors=True (a colour volume):
+        (vertices, faces, colors [n,3] CUDA fp32 — row p the colour of vertex p —, (vertices found, triangles found)).  Reads the
+        counts back: like `points`, the one place this object synchronises (and allocates)."""
+        color = self._need_color("mesh") if colors else None
         if self._mesh_workspace is None:
             self._mesh_workspace = torch.empty((ops.tsdf_mesh_workspace(*self.dims) + 7) // 8, dtype=torch.int64, device=self.device)
             self._mesh_counts = torch.zeros(4, dtype=torch.int64, device=self.device)
@@ -177,17 +231,26 @@ class TSDFVolume:
             raise ValueError("TSDFVolume.mesh: capacity %s" % (capacity,))
         vertices = torch.empty((nv, 3), dtype=torch.float32, device=self.device)
         faces = torch.empty((nf, 3), dtype=torch.int32, device=self.device)
+        if colors:
+            rgb = torch.empty((nv, 3), dtype=torch.float32, device=self.device)
+            ops.tsdf_extract_mesh(*args, vertices if nv else None, faces if nf else None, self._mesh_counts, color=color,
+                                  colors=rgb if nv else None)
+            v_found, v_written, f_found, f_written = (int(v) for v in self._mesh_counts.cpu())
+            return vertices[:v_written], faces[:f_written], rgb[:v_written], (v_found, f_found)
         ops.tsdf_extract_mesh(*args, vertices if nv else None, faces if nf else None, self._mesh_counts)
         v_found, v_written, f_found, f_written = (int(v) for v in self._mesh_counts.cpu())
         return vertices[:v_written], faces[:f_written], (v_found, f_found)
 
-    def raycast(self, extM, intrinsics, size, depth_range=(0., float("inf")), w_min=1., step=None, normals=False, out=None):
+    def raycast(self, extM, intrinsics, size, depth_range=(0., float("inf")), w_min=1., step=None, normals=False, out=None, color=False):
         """The volume seen from a camera at extM (host [3,4] or [4,4] world -> camera), one launch (ops.tsdf_raycast): z-depth [H,W] of
         the surface along every pixel's ray, 0 where there is none, and with normals=True (depth, normal [3,H,W]) with the unit normals
         in the camera frame.  intrinsics: (fx, fy, cx, cy) at size = (H, W), or a cam_intrinsics dict (intrinsics_at); depth_range: the
         z-depths searched; w_min: a sample counts where the eight weights around it reach it; step: the sample distance along the ray
         in metres (default voxel_size; above trunc a ray could step over the band); out: tensors to write into (then nothing is
-        allocated).  Synchronises nothing."""
+        allocated).  color=True (a colour volume): rgb [3,H,W], the trilinear colour at every hit and (0, 0, 0) where there is none,
+        as one more element of the result: (depth, rgb) or (depth, normal, rgb); `out` then takes the same tuple.  Synchronises
+        nothing."""
+        planes = self._need_color("raycast") if color else None
         H, W = (int(n) for n in size)
         if isinstance(intrinsics, dict):
             intrinsics = intrinsics_at(intrinsics, H, W)
@@ -198,7 +261,16 @@ class TSDFVolume:
         if not 0 < step <= self.trunc:
             raise ValueError("TSDFVolume.raycast: step %s is not in (0, trunc = %s]: a ray could step over the band" % (step, self.trunc))
         return ops.tsdf_raycast(self.tsdf, self.weight, self.origin, self.voxel_size, m, intrinsics, (H, W), depth_range, w_min=w_min,
-                                step=step, normals=normals, out=out)
+                                step=step, normals=normals, out=out, color=planes, rgb=bool(color))
+
+
+def to_uint8(rgb):
+    """fp32 colours in [0, 1] (a tensor on any device, or an array) -> uint8 of the same shape and kind: rint(clip(c, 0, 1) * 255),
+    ties to even; a NaN becomes 0."""
+    if isinstance(rgb, torch.Tensor):
+        return torch.nan_to_num(rgb, nan=0.0).clamp(0., 1.).mul(255.).round().to(torch.uint8)
+    c = np.asarray(rgb, dtype=np.float32)
+    return np.rint(np.clip(np.where(np.isnan(c), np.float32(0), c), 0., 1.) * np.float32(255.)).astype(np.uint8)
 
 
 def shade(normal):
@@ -216,12 +288,15 @@ class FusionVideoStream(VideoDepthStream):
     source: 'refined' (the R-Net volume at the network size) or 'dpv' (the K-Net volume at the plane-sweep grid);
     conf_threshold c: only pixels with max_k logp >= float32(log c) count (evaluate.log_thresholds' gate);
     weight: 'uniform' (1 per observation) or 'conf' (exp(max_k logp), from ops.export_depth_u16).
+    color=True (a colour volume): the frame's own picture is fused with its depth map — read straight from the slot of the frame ring
+    the reference frame still occupies, at the network size with intrinsics_at(cam, H, W) (also when source='dpv' puts the depth map at
+    the plane-sweep grid), through the affine a = std, b = mean, which undoes the ingest's normalisation: colours in [0, 1].
     The R-Net's volume is read where it lies (its channels-last view) when the candidates fill the kernels' candidate width (64 or
     128 candidates, 256 with if_upsample_d); another count runs zero-padded to that width, the view is then a slice of the padded
     pixels and ops.depth_regress makes a planar copy of it first."""
 
     def __init__(self, model, cam_intrinsics, d_candi, volume, t_win_r=2, source="refined", conf_threshold=0., weight="uniform",
-                 depth_range=None, **video_kwargs):
+                 depth_range=None, color=False, **video_kwargs):
         from .nets import require_volume_refiner
         require_volume_refiner(model, "FusionVideoStream")
         if source not in ("refined", "dpv"):
@@ -231,6 +306,10 @@ class FusionVideoStream(VideoDepthStream):
         c = float(conf_threshold)
         if not 0 <= c < 1:
             raise ValueError("FusionVideoStream: conf_threshold %s is not in [0, 1)" % (conf_threshold,))
+        if bool(color) != (getattr(volume, "color", None) is not None):
+            raise ValueError("FusionVideoStream: color=%s takes a volume %s colour (TSDFVolume(..., color=%s))"
+                             % (bool(color), "with" if color else "without", bool(color)))
+        self.color = bool(color)
         self.volume = volume
         self.source, self.weight_mode, self.conf_threshold = source, weight, c
         self.gate_thr = None if c == 0 else float(np.log(np.float64(c)).astype(np.float32))      # the log in double, rounded once
@@ -251,8 +330,8 @@ class FusionVideoStream(VideoDepthStream):
         self._ext = [None] * self.n_slots
         self.last_ext = None                                    # the extrinsic of the last frame integrated on this trajectory
 
-    def render(self, extM=None, size=None, normals=False, **kw):
-        """The fused model as a depth map (and normals): TSDFVolume.raycast from extM — by default the extrinsic of the last frame
+    def render(self, extM=None, size=None, normals=False, color=False, **kw):
+        """The fused model as a depth map (and normals, and with color=True its colours): TSDFVolume.raycast from extM — by default the extrinsic of the last frame
         that was integrated — at `size` (default: the network's image size) with the stream's intrinsics and, unless given, its
         depth_range.  An eager launch on the caller's stream; the frame ring and the captured graph are not touched."""
         if extM is None:
@@ -260,10 +339,12 @@ class FusionVideoStream(VideoDepthStream):
             if extM is None:
                 raise ValueError("FusionVideoStream.render: no frame has been integrated yet; pass extM")
         kw.setdefault("depth_range", self.depth_range)
+        if color:
+            kw["color"] = True
         return self.volume.raycast(extM, self.cam, (self.H, self.W) if size is None else size, normals=normals, **kw)
 
     def mesh(self, **kw):
-        """The fused model as a triangle mesh: TSDFVolume.mesh(**kw) of the stream's volume."""
+        """The fused model as a triangle mesh: TSDFVolume.mesh(**kw) of the stream's volume (colors=True: with vertex colours)."""
         return self.volume.mesh(**kw)
 
     def _fuse(self, out):
@@ -285,8 +366,14 @@ class FusionVideoStream(VideoDepthStream):
         depth, logconf = ops.depth_regress(vol, d_dev, channels_last=cl)
         wmap = ops.export_depth_u16(vol, d_dev, channels_last=cl)[1] if self.weight_mode == "conf" else None
         gate = None if self.gate_thr is None else logconf
+        kw = {}
+        if self.color:
+            # frame ref_index is at most t_win_r + 1 pushes behind the newest (pipeline=True; flush() included) and the ring holds the
+            # last 2 t_win_r + 1 >= t_win_r + 2: its slot still holds its picture, written by an ingest enqueued on this stream
+            kw = dict(color=self.ring[ref_index % self.R], color_intrinsics=intrinsics_at(self.cam, self.H, self.W),
+                      color_affine=(self.std, self.mean))
         if self.volume.integrate(depth, self._ext[slot], self.cam, gate=gate, gate_thr=self.gate_thr, weight=wmap,
-                                 depth_range=self.depth_range):
+                                 depth_range=self.depth_range, **kw):
             self.n_integrated += 1
             self.last_ext = self._ext[slot]
         return out
@@ -318,15 +405,29 @@ def fuse_sequence(stream, frames, extMs):
     return stream.n_integrated - before
 
 
-def save_ply(path, points, faces=None, binary=False):
+def save_ply(path, points, faces=None, binary=False, colors=None):
     """[n,3] points (a tensor on any device, or an array) as a PLY file, written on the host; returns the vertex count.  faces: [m,3]
     vertex rows (TSDFVolume.mesh's) written as an `element face` block (property list uchar int vertex_indices); binary: the
-    binary_little_endian 1.0 form, written by numpy in one piece, else ASCII, in which %.9g round-trips fp32."""
+    binary_little_endian 1.0 form, written by numpy in one piece, else ASCII, in which %.9g round-trips fp32.  colors: [n,3] colours of
+    the points, written as `property uchar red / green / blue` after z — fp32 in [0, 1] through to_uint8, or uint8 as given."""
     if isinstance(points, torch.Tensor):
         points = points.detach().cpu().numpy()
     p = np.asarray(points, dtype=np.float32).reshape(-1, 3)
     header = "ply\nformat %s 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n" % (
         "binary_little_endian" if binary else "ascii", len(p))
+    rgb = None
+    if colors is not None:
+        if isinstance(colors, torch.Tensor):
+            colors = colors.detach().cpu().numpy()
+        rgb = np.asarray(colors)
+        if rgb.dtype != np.uint8:
+            if not np.issubdtype(rgb.dtype, np.floating):
+                raise ValueError("save_ply: colors are fp32 in [0, 1] or uint8, got %s" % rgb.dtype)
+            rgb = to_uint8(rgb)
+        rgb = rgb.reshape(-1, 3)
+        if len(rgb) != len(p):
+            raise ValueError("save_ply: %d colours for %d points" % (len(rgb), len(p)))
+        header += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
     tri = None
     if faces is not None:
         if isinstance(faces, torch.Tensor):
@@ -340,7 +441,12 @@ def save_ply(path, points, faces=None, binary=False):
     if binary:
         with open(path, "wb") as f:
             f.write(header.encode("ascii"))
-            f.write(p.astype("<f4").tobytes())
+            if rgb is None:
+                f.write(p.astype("<f4").tobytes())
+            else:
+                vert = np.empty(len(p), dtype=[("p", "<f4", (3,)), ("c", "u1", (3,))])
+                vert["p"], vert["c"] = p, rgb
+                f.write(vert.tobytes())
             if tri is not None:
                 rec = np.empty(len(tri), dtype=[("n", "u1"), ("v", "<i4", (3,))])
                 rec["n"], rec["v"] = 3, tri
@@ -348,8 +454,12 @@ def save_ply(path, points, faces=None, binary=False):
         return len(p)
     with open(path, "w") as f:
         f.write(header)
-        for x, y, z in p:
-            f.write("%.9g %.9g %.9g\n" % (x, y, z))
+        if rgb is None:
+            for x, y, z in p:
+                f.write("%.9g %.9g %.9g\n" % (x, y, z))
+        else:
+            for (x, y, z), (r, g, b) in zip(p, rgb):
+                f.write("%.9g %.9g %.9g %d %d %d\n" % (x, y, z, r, g, b))
         for a, b, c in (tri if tri is not None else ()):
             f.write("3 %d %d %d\n" % (a, b, c))
     return len(p)

@@ -1656,6 +1656,42 @@ def _vec3(v, name):
     return v
 
 
+def _tsdf_frame(who, tsdf, weight, origin, depth, gate, wmap, pose, intrinsics, box):
+    """What the two integrations check and prepare alike: -> (tsdf, weight, [depth, gate, wmap], float32 pose [3,4], (fx, fy, cx, cy),
+    origin, the box as a C array or None)."""
+    tsdf, weight = _tsdf_volume(tsdf, weight, who)
+    dev = tsdf.device
+    depth = _need(depth, "depth", strided=True)
+    if depth.dim() != 2:
+        raise ValueError("%s: depth must be [H,W], got %s" % (who, tuple(depth.shape)))
+    maps = []
+    for t, nm in ((depth, "depth"), (gate, "gate"), (wmap, "wmap")):
+        if t is not None:
+            t = _need(t, nm, tuple(depth.shape), strided=True)
+            if t.device != dev or not t.is_contiguous():
+                raise ValueError("%s: %s must be contiguous and on %s" % (who, nm, dev))
+        maps.append(t)
+    if isinstance(pose, torch.Tensor):
+        if pose.is_cuda:
+            raise ValueError("%s: pose is a host matrix (it is read at the call)" % who)
+        pose = pose.detach().numpy()
+    pose = np.asarray(pose)
+    if pose.shape not in ((3, 4), (4, 4)):
+        raise ValueError("%s: pose is [3,4] or [4,4] world -> camera, got %s" % (who, pose.shape))
+    pose = np.ascontiguousarray(pose[:3, :4], dtype=np.float32)
+    k = tuple(float(x) for x in intrinsics)
+    if len(k) != 4:
+        raise ValueError("%s: intrinsics = (fx, fy, cx, cy)" % who)
+    o = _vec3(origin, "%s: origin" % who)
+    cbox = None
+    if box is not None:
+        b = tuple(int(x) for x in box)
+        if len(b) != 6:
+            raise ValueError("%s: box = (x0, y0, z0, x1, y1, z1)" % who)
+        cbox = (ctypes.c_int * 6)(*b)
+    return tsdf, weight, maps, pose, k, o, cbox
+
+
 def tsdf_integrate(tsdf, weight, origin, voxel_size, depth, pose, intrinsics, trunc, depth_range=(0.0, float("inf")), w_max=64.0,
                    gate=None, gate_thr=0.0, wmap=None, box=None):
     """One depth frame into a TSDF volume, in place, one launch (nrgbd_tsdf_integrate_f32; the per-voxel operation sequence is
@@ -1664,44 +1700,60 @@ def tsdf_integrate(tsdf, weight, origin, voxel_size, depth, pose, intrinsics, tr
     contiguous CUDA fp32 [H,W] on the same device; pose: host [3,4] or [4,4] world -> camera, cast to float32; intrinsics =
     (fx, fy, cx, cy) at the depth map's size; depth_range = (d_near, d_far]; box: a half-open voxel box (x0, y0, z0, x1, y1, z1) or
     None for the whole grid.  Nothing is allocated, nothing synchronised."""
-    tsdf, weight = _tsdf_volume(tsdf, weight, "tsdf_integrate")
+    tsdf, weight, maps, pose, k, o, cbox = _tsdf_frame("tsdf_integrate", tsdf, weight, origin, depth, gate, wmap, pose, intrinsics, box)
     dev = tsdf.device
-    depth = _need(depth, "depth", strided=True)
-    if depth.dim() != 2:
-        raise ValueError("tsdf_integrate: depth must be [H,W], got %s" % (tuple(depth.shape),))
-    maps = []
-    for t, nm in ((depth, "depth"), (gate, "gate"), (wmap, "wmap")):
-        if t is not None:
-            t = _need(t, nm, tuple(depth.shape), strided=True)
-            if t.device != dev or not t.is_contiguous():
-                raise ValueError("tsdf_integrate: %s must be contiguous and on %s" % (nm, dev))
-        maps.append(t)
-    if isinstance(pose, torch.Tensor):
-        if pose.is_cuda:
-            raise ValueError("tsdf_integrate: pose is a host matrix (it is read at the call)")
-        pose = pose.detach().numpy()
-    pose = np.asarray(pose)
-    if pose.shape not in ((3, 4), (4, 4)):
-        raise ValueError("tsdf_integrate: pose is [3,4] or [4,4] world -> camera, got %s" % (pose.shape,))
-    pose = np.ascontiguousarray(pose[:3, :4], dtype=np.float32)
-    k = tuple(float(x) for x in intrinsics)
-    if len(k) != 4:
-        raise ValueError("tsdf_integrate: intrinsics = (fx, fy, cx, cy)")
-    o = _vec3(origin, "tsdf_integrate: origin")
-    cbox = None
-    if box is not None:
-        b = tuple(int(x) for x in box)
-        if len(b) != 6:
-            raise ValueError("tsdf_integrate: box = (x0, y0, z0, x1, y1, z1)")
-        cbox = (ctypes.c_int * 6)(*b)
     Z, Y, X = tsdf.shape
-    H, W = depth.shape
+    H, W = maps[0].shape
     with torch.cuda.device(dev):
         rc = _lib.load().nrgbd_tsdf_integrate_f32(_p(tsdf), _p(weight), X, Y, Z, o[0], o[1], o[2], float(voxel_size), _p(maps[0]),
                                                   _p(maps[1]), float(gate_thr), _p(maps[2]), H, W, ctypes.c_void_p(pose.ctypes.data),
                                                   k[0], k[1], k[2], k[3], float(trunc), float(depth_range[0]), float(depth_range[1]),
                                                   float(w_max), cbox, _stream(tsdf))
     _lib.check(rc, "nrgbd_tsdf_integrate_f32")
+
+
+def _tsdf_color(color, tsdf, who):
+    """The colour planes [3,Z,Y,X] of a volume: fp32, contiguous, on the volume's device."""
+    color = _need(color, "color", (3,) + tuple(tsdf.shape), strided=True)
+    if color.device != tsdf.device or not color.is_contiguous():
+        raise ValueError("%s: color must be a contiguous [3,Z,Y,X] tensor on %s" % (who, tsdf.device))
+    return color
+
+
+def tsdf_integrate_color(tsdf, weight, color, origin, voxel_size, depth, pose, intrinsics, trunc, image, color_intrinsics,
+                         color_affine=None, depth_range=(0.0, float("inf")), w_max=64.0, gate=None, gate_thr=0.0, wmap=None, box=None):
+    """tsdf_integrate with the frame's colour averaged into the volume's colour planes, one launch (nrgbd_tsdf_integrate_color_f32;
+    the operation sequence is written out in include/nrgbd.h): tsdf and weight get the bits tsdf_integrate gives them, and every
+    voxel that is updated averages the pixel of `image` it projects to — clamped into the image — into `color` with the same weight.
+    color: contiguous CUDA fp32 [3,Z,Y,X]; image: contiguous CUDA fp32 [3,Hc,Wc] on the same device, at a size of its own;
+    color_intrinsics = (fx, fy, cx, cy) at that size; color_affine = (a [3], b [3]): the colour of a pixel is image * a + b per
+    channel (None: a = 1, b = 0).  Everything else as tsdf_integrate.  Nothing is allocated, nothing synchronised."""
+    tsdf, weight, maps, pose, k, o, cbox = _tsdf_frame("tsdf_integrate_color", tsdf, weight, origin, depth, gate, wmap, pose, intrinsics, box)
+    color = _tsdf_color(color, tsdf, "tsdf_integrate_color")
+    dev = tsdf.device
+    image = _need(image, "image", strided=True)
+    if image.dim() != 3 or image.shape[0] != 3 or image.shape[1] < 1 or image.shape[2] < 1:
+        raise ValueError("tsdf_integrate_color: image must be [3,Hc,Wc], got %s" % (tuple(image.shape),))
+    if image.device != dev or not image.is_contiguous():
+        raise ValueError("tsdf_integrate_color: image must be contiguous and on %s" % (dev,))
+    kc = tuple(float(x) for x in color_intrinsics)
+    if len(kc) != 4:
+        raise ValueError("tsdf_integrate_color: color_intrinsics = (fx, fy, cx, cy)")
+    if color_affine is None:
+        color_affine = ((1.0, 1.0, 1.0), (0.0, 0.0, 0.0))
+    affine = np.ascontiguousarray(np.concatenate([np.asarray(v, dtype=np.float32).reshape(-1) for v in color_affine]))
+    if affine.shape != (6,):
+        raise ValueError("tsdf_integrate_color: color_affine = (a [3], b [3])")
+    Z, Y, X = tsdf.shape
+    H, W = maps[0].shape
+    with torch.cuda.device(dev):
+        rc = _lib.load().nrgbd_tsdf_integrate_color_f32(_p(tsdf), _p(weight), _p(color), X, Y, Z, o[0], o[1], o[2], float(voxel_size),
+                                                        _p(maps[0]), _p(maps[1]), float(gate_thr), _p(maps[2]), H, W,
+                                                        ctypes.c_void_p(pose.ctypes.data), k[0], k[1], k[2], k[3], float(trunc),
+                                                        float(depth_range[0]), float(depth_range[1]), float(w_max), cbox, _p(image),
+                                                        image.shape[1], image.shape[2], kc[0], kc[1], kc[2], kc[3],
+                                                        ctypes.c_void_p(affine.ctypes.data), _stream(tsdf))
+    _lib.check(rc, "nrgbd_tsdf_integrate_color_f32")
 
 
 def tsdf_extract_workspace(X, Y, Z):
@@ -1712,13 +1764,33 @@ def tsdf_extract_workspace(X, Y, Z):
     return rc
 
 
-def tsdf_extract_points(tsdf, weight, origin, voxel_size, w_min, workspace, points, counts):
+def _tsdf_colors(colors, rows, color, dev, who):
+    """The [capacity,3] colour rows that go with a coloured extraction's points (None with None)."""
+    if color is None:
+        if colors is not None:
+            raise ValueError("%s: colors needs the volume's color planes" % who)
+        return None
+    if rows is None:
+        if colors is not None:
+            raise ValueError("%s: colors without the rows they belong to" % who)
+        return None
+    colors = _need(colors, "colors", tuple(rows.shape), strided=True)
+    if not colors.is_contiguous() or colors.device != dev:
+        raise ValueError("%s: colors must be a contiguous [capacity,3] tensor on %s" % (who, dev))
+    return colors
+
+
+def tsdf_extract_points(tsdf, weight, origin, voxel_size, w_min, workspace, points, counts, color=None, colors=None):
     """The zero crossings of a TSDF volume as points (nrgbd_tsdf_extract_points: three launches, no atomics, ascending (linear voxel
     index, axis) order).  workspace: a contiguous CUDA tensor of at least tsdf_extract_workspace(X, Y, Z) bytes; points: contiguous
     CUDA fp32 [capacity,3] — the first min(found, capacity) rows are written — or None for a count alone; counts: CUDA int64 [2],
-    written (crossings found, points written).  Nothing is allocated, nothing synchronised."""
+    written (crossings found, points written).  color: the volume's colour planes [3,Z,Y,X] and colors: contiguous CUDA fp32
+    [capacity,3] — row p gets the colour of point p (nrgbd_tsdf_extract_points_color: the same launches, the same points); without
+    them the colourless entry runs.  Nothing is allocated, nothing synchronised."""
     tsdf, weight = _tsdf_volume(tsdf, weight, "tsdf_extract_points")
     dev = tsdf.device
+    if color is not None:
+        color = _tsdf_color(color, tsdf, "tsdf_extract_points")
     if not isinstance(workspace, torch.Tensor) or workspace.device != dev or not workspace.is_contiguous():
         raise ValueError("tsdf_extract_points: workspace must be a contiguous tensor on %s" % (dev,))
     if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int64 or counts.device != dev or not counts.is_contiguous()
@@ -1730,8 +1802,17 @@ def tsdf_extract_points(tsdf, weight, origin, voxel_size, w_min, workspace, poin
         if points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous() or points.device != dev:
             raise ValueError("tsdf_extract_points: points must be a contiguous [capacity,3] tensor on %s" % (dev,))
         capacity = points.shape[0]
+    colors = _tsdf_colors(colors, points, color, dev, "tsdf_extract_points")
     o = _vec3(origin, "tsdf_extract_points: origin")
     Z, Y, X = tsdf.shape
+    if color is not None:
+        with torch.cuda.device(dev):
+            rc = _lib.load().nrgbd_tsdf_extract_points_color(_p(tsdf), _p(weight), _p(color), X, Y, Z, o[0], o[1], o[2], float(voxel_size),
+                                                             float(w_min), _p(workspace), workspace.numel() * workspace.element_size(),
+                                                             _p(points if capacity else None), _p(colors if capacity else None),
+                                                             capacity, _p(counts), _stream(tsdf))
+        _lib.check(rc, "nrgbd_tsdf_extract_points_color")
+        return
     with torch.cuda.device(dev):
         rc = _lib.load().nrgbd_tsdf_extract_points(_p(tsdf), _p(weight), X, Y, Z, o[0], o[1], o[2], float(voxel_size), float(w_min),
                                                    _p(workspace), workspace.numel() * workspace.element_size(),
@@ -1747,16 +1828,19 @@ def tsdf_mesh_workspace(X, Y, Z):
     return rc
 
 
-def tsdf_extract_mesh(tsdf, weight, origin, voxel_size, w_min, workspace, vertices, faces, counts):
+def tsdf_extract_mesh(tsdf, weight, origin, voxel_size, w_min, workspace, vertices, faces, counts, color=None, colors=None):
     """The surface of a TSDF volume as an indexed triangle mesh (nrgbd_tsdf_extract_mesh: four launches, no atomics).  The vertices are
     the points of tsdf_extract_points, bit for bit and in its order; a triangle holds the rows of its three vertices in the full vertex
     sequence, its normal towards free space; triangles come in ascending cell order (include/nrgbd.h has the conventions).
     workspace: a contiguous CUDA tensor of at least tsdf_mesh_workspace(X, Y, Z) bytes; vertices: contiguous CUDA fp32 [capacity,3] or
     None; faces: contiguous CUDA int32 [capacity,3] or None — the first min(found, capacity) rows of either are written; counts: CUDA
-    int64 [4], written (vertices found, vertices written, triangles found, triangles written).  Nothing is allocated, nothing
-    synchronised."""
+    int64 [4], written (vertices found, vertices written, triangles found, triangles written).  color: the volume's colour planes
+    [3,Z,Y,X] and colors: contiguous CUDA fp32 [capacity,3] — row p gets the colour of vertex p (nrgbd_tsdf_extract_mesh_color: the
+    same launches, vertices and faces); without them the colourless entry runs.  Nothing is allocated, nothing synchronised."""
     tsdf, weight = _tsdf_volume(tsdf, weight, "tsdf_extract_mesh")
     dev = tsdf.device
+    if color is not None:
+        color = _tsdf_color(color, tsdf, "tsdf_extract_mesh")
     if not isinstance(workspace, torch.Tensor) or workspace.device != dev or not workspace.is_contiguous():
         raise ValueError("tsdf_extract_mesh: workspace must be a contiguous tensor on %s" % (dev,))
     if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int64 or counts.device != dev or not counts.is_contiguous()
@@ -1772,8 +1856,17 @@ def tsdf_extract_mesh(tsdf, weight, origin, voxel_size, w_min, workspace, vertic
         if t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous() or t.device != dev:
             raise ValueError("tsdf_extract_mesh: %s must be a contiguous [capacity,3] tensor on %s" % (nm, dev))
         caps.append(t.shape[0])
+    colors = _tsdf_colors(colors, vertices, color, dev, "tsdf_extract_mesh")
     o = _vec3(origin, "tsdf_extract_mesh: origin")
     Z, Y, X = tsdf.shape
+    if color is not None:
+        with torch.cuda.device(dev):
+            rc = _lib.load().nrgbd_tsdf_extract_mesh_color(_p(tsdf), _p(weight), _p(color), X, Y, Z, o[0], o[1], o[2], float(voxel_size),
+                                                           float(w_min), _p(workspace), workspace.numel() * workspace.element_size(),
+                                                           _p(vertices if caps[0] else None), _p(colors if caps[0] else None), caps[0],
+                                                           _p(faces if caps[1] else None), caps[1], _p(counts), _stream(tsdf))
+        _lib.check(rc, "nrgbd_tsdf_extract_mesh_color")
+        return
     with torch.cuda.device(dev):
         rc = _lib.load().nrgbd_tsdf_extract_mesh(_p(tsdf), _p(weight), X, Y, Z, o[0], o[1], o[2], float(voxel_size), float(w_min),
                                                  _p(workspace), workspace.numel() * workspace.element_size(),
@@ -1792,16 +1885,24 @@ def camera_centre(pose):
     return np.array([-((p[0, k] * p[0, 3] + p[1, k] * p[1, 3]) + p[2, k] * p[2, 3]) for k in range(3)], dtype=np.float64).astype(np.float32)
 
 
-def tsdf_raycast(tsdf, weight, origin, voxel_size, pose, intrinsics, size, depth_range, w_min=1.0, step=None, normals=False, out=None):
+def tsdf_raycast(tsdf, weight, origin, voxel_size, pose, intrinsics, size, depth_range, w_min=1.0, step=None, normals=False, out=None,
+                 color=None, rgb=False):
     """A TSDF volume seen from a camera, one launch (nrgbd_tsdf_raycast_f32; the per-pixel operation sequence is written out in
     include/nrgbd.h): z-depth [H,W] of the first zero crossing along every pixel's ray, 0 where there is none, and with normals=True
     (depth, normal [3,H,W]), the unit surface normals in the camera frame ((0,0,0) where there is none).
     tsdf / weight: contiguous CUDA fp32 [Z,Y,X]; pose: host [3,4] or [4,4] world -> camera, cast to float32; intrinsics = (fx, fy, cx,
     cy) at size = (H, W); depth_range = [d_near, d_far]; a sample counts where the eight weights around it are >= w_min; step: the
     sample distance along the ray in metres (None: voxel_size).  out: a contiguous CUDA fp32 [H,W] tensor, or with normals=True the
-    pair ([H,W], [3,H,W]), to write into; then nothing is allocated.  Nothing is synchronised."""
+    pair ([H,W], [3,H,W]), to write into; then nothing is allocated.  rgb=True with color, the volume's colour planes [3,Z,Y,X]
+    (nrgbd_tsdf_raycast_color_f32: the same depth and normals): the trilinear colour at every hit [3,H,W], (0,0,0) where there is
+    none, as one more element of the result — (depth, rgb) or (depth, normal, rgb), and `out` takes the same tuple.  Nothing is
+    synchronised."""
+    if rgb and color is None:
+        raise ValueError("tsdf_raycast: rgb=True needs the volume's color planes")
     tsdf, weight = _tsdf_volume(tsdf, weight, "tsdf_raycast")
     dev = tsdf.device
+    if rgb:
+        color = _tsdf_color(color, tsdf, "tsdf_raycast")
     H, W = (int(n) for n in size)
     if isinstance(pose, torch.Tensor):
         if pose.is_cuda:
@@ -1816,20 +1917,24 @@ def tsdf_raycast(tsdf, weight, origin, voxel_size, pose, intrinsics, size, depth
     if len(k) != 4:
         raise ValueError("tsdf_raycast: intrinsics = (fx, fy, cx, cy)")
     o = _vec3(origin, "tsdf_raycast: origin")
+    wanted = [("out depth", (H, W)), ("out normal", (3, H, W))][:2 if normals else 1] + ([("out rgb", (3, H, W))] if rgb else [])
     if out is None:
         if H <= 0 or W <= 0:
             raise ValueError("tsdf_raycast: size = (H, W), positive; got %s" % (size,))
-        depth = torch.empty((H, W), dtype=torch.float32, device=dev)
-        normal = torch.empty((3, H, W), dtype=torch.float32, device=dev) if normals else None
+        outs = [torch.empty(shape, dtype=torch.float32, device=dev) for _, shape in wanted]
     else:
-        if normals and (not isinstance(out, (tuple, list)) or len(out) != 2):
-            raise ValueError("tsdf_raycast: normals=True takes out=(depth, normal)")
-        depth, normal = out if normals else (out, None)
-        for t, nm, shape in ((depth, "out depth", (H, W)), (normal, "out normal", (3, H, W)))[:2 if normals else 1]:
+        if len(wanted) > 1 and (not isinstance(out, (tuple, list)) or len(out) != len(wanted)):
+            raise ValueError("tsdf_raycast: out=(%s)" % ", ".join(nm[4:] for nm, _ in wanted) if rgb else
+                             "tsdf_raycast: normals=True takes out=(depth, normal)")
+        outs = list(out) if len(wanted) > 1 else [out]
+        for t, (nm, shape) in zip(outs, wanted):
             t = _need(t, nm, shape, strided=True)
             if t.device != dev or not t.is_contiguous():
                 raise ValueError("tsdf_raycast: %s must be contiguous and on %s" % (nm, dev))
+    depth, normal = outs[0], (outs[1] if normals else None)
     Z, Y, X = tsdf.shape
+    if rgb:
+        return _tsdf_raycast_color(tsdf, weight, color, X, Y, Z, o, voxel_size, pose, centre, k, H, W, depth_range, w_min, step, outs, normal)
     with torch.cuda.device(dev):
         rc = _lib.load().nrgbd_tsdf_raycast_f32(_p(tsdf), _p(weight), X, Y, Z, o[0], o[1], o[2], float(voxel_size),
                                                 ctypes.c_void_p(pose.ctypes.data), ctypes.c_void_p(centre.ctypes.data), k[0], k[1], k[2],
@@ -1837,3 +1942,14 @@ def tsdf_raycast(tsdf, weight, origin, voxel_size, pose, intrinsics, size, depth
                                                 float(voxel_size if step is None else step), _p(depth), _p(normal), _stream(tsdf))
     _lib.check(rc, "nrgbd_tsdf_raycast_f32")
     return (depth, normal) if normals else depth
+
+
+def _tsdf_raycast_color(tsdf, weight, color, X, Y, Z, o, voxel_size, pose, centre, k, H, W, depth_range, w_min, step, outs, normal):
+    with torch.cuda.device(tsdf.device):
+        rc = _lib.load().nrgbd_tsdf_raycast_color_f32(_p(tsdf), _p(weight), _p(color), X, Y, Z, o[0], o[1], o[2], float(voxel_size),
+                                                      ctypes.c_void_p(pose.ctypes.data), ctypes.c_void_p(centre.ctypes.data), k[0], k[1],
+                                                      k[2], k[3], H, W, float(depth_range[0]), float(depth_range[1]), float(w_min),
+                                                      float(voxel_size if step is None else step), _p(outs[0]), _p(normal), _p(outs[-1]),
+                                                      _stream(tsdf))
+    _lib.check(rc, "nrgbd_tsdf_raycast_color_f32")
+    return tuple(outs)
