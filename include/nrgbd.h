@@ -65,7 +65,9 @@ extern "C" {
  * nrgbd_tsdf_integrate_f32, nrgbd_tsdf_extract_workspace and nrgbd_tsdf_extract_points, and for nrgbd_tsdf_raycast_f32 (the fused
  * volume rendered to depth and normals), and for nrgbd_tsdf_mesh_workspace and nrgbd_tsdf_extract_mesh (the fused volume as an
  * indexed triangle mesh), and for the colour entries nrgbd_tsdf_integrate_color_f32, nrgbd_tsdf_extract_points_color,
- * nrgbd_tsdf_extract_mesh_color and nrgbd_tsdf_raycast_color_f32 (the frames' colour fused into the volume). */
+ * nrgbd_tsdf_extract_mesh_color and nrgbd_tsdf_raycast_color_f32 (the frames' colour fused into the volume), and for the tracking
+ * entries nrgbd_icp_workgroups, nrgbd_icp_workspace, nrgbd_icp_terms_f32 and nrgbd_icp_update (a depth frame registered against the
+ * fused volume). */
 #define NRGBD_INTERFACE_VERSION "0.10"
 const char* nrgbd_version(void);
 const char* nrgbd_strerror(int code);
@@ -1148,6 +1150,115 @@ int nrgbd_tsdf_raycast_color_f32(const float* tsdf, const float* weight, const f
                                  float oy, float oz, float voxel_size, const float* pose, const float* centre, float fx,
                                  float fy, float cx, float cy, int H, int W, float d_near, float d_far, float w_min, float step,
                                  float* depth, float* normal, float* rgb, void* stream);
+/*
+ * Frame-to-model tracking (icp.hip; neuralrgbd_amd/tracking.py: FrameTracker; fusion.py: TSDFVolume.track, FusionVideoStream(track=
+ * True)): a depth frame registered against the maps nrgbd_tsdf_raycast_f32 writes, by point-to-plane ICP with projective data
+ * association (KinectFusion's frame-to-model tracking).  None of the entries has a counterpart in the reference, which takes its poses
+ * from an external odometry; the conventions are the ones written here.  Per pixel everything is fp32, from the normal equations on
+ * everything is double; every operation below is ONE IEEE operation of its type in the order written (no fused multiply-add, no
+ * reciprocal, no library function), there are no atomics, and the same inputs give the same bits in every run.  One Gauss-Newton
+ * iteration is two launches on the caller's stream (nrgbd_icp_terms_f32, nrgbd_icp_update); nothing is read back between iterations
+ * and the schedule is capturable.
+ *
+ * state: device memory, NRGBD_ICP_STATE_BYTES, 8-byte aligned:
+ *     double T[12]    the motion dT = (R | t), [3][4] row-major, frame camera -> model camera (the camera the model maps were cast from)
+ *     float  Tf[12]   the same, each entry rounded once: what nrgbd_icp_terms_f32 reads
+ *     int32  flag     0, or the NRGBD_ICP_* reason the iteration stopped for (sticky)
+ *     int32  iterations   the steps that updated T since step 0
+ * partial: nwg = nrgbd_icp_workgroups(Hs, Ws) records of NRGBD_ICP_RECORD_BYTES (240): double[28] = A_ij for i <= j in row-major
+ *   order (A_00, A_01 .. A_05, A_11 ..: 21), g_0 .. g_5, E; then an int64 count; then 8 bytes of padding (written as 0).
+ *
+ * nrgbd_icp_workgroups — no counterpart in the reference: min(ceil(Hs Ws / 256), NRGBD_ICP_MAX_WG); a fixed cap, larger maps are
+ *   covered by a grid-stride loop.  NRGBD_E_SHAPE: Hs or Ws <= 0 or > 32768.  Needs no GPU.
+ * nrgbd_icp_workspace — no counterpart in the reference: the bytes of `partial` for an Hs x Ws visit (needs no GPU); NRGBD_E_SHAPE alike.
+ * nrgbd_icp_terms_f32 — no counterpart in the reference: association, residuals and the partial normal equations, one launch.
+ *   depth        device fp32 [H][W]: the frame's z-depth in metres
+ *   gate         device fp32 [H][W] or NULL: a pixel counts where gate >= gate_thr (a NaN fails), as nrgbd_tsdf_integrate_f32 takes it
+ *   d_near d_far a pixel counts where d is finite, d > d_near and d <= d_far
+ *   fx fy cx cy  the frame's pinhole intrinsics at H x W; pixel x covers [x, x + 1)
+ *   sub          >= 1: the pixels visited are (y, x) = (sub j + sub / 2, sub i + sub / 2), j < Hs = H / sub, i < Ws = W / sub
+ *                (integer divisions)
+ *   mdepth       device fp32 [Hm][Wm]: the model's z-depth, 0 = no surface      } what nrgbd_tsdf_raycast_f32 writes
+ *   mnormal      device fp32 [3][Hm][Wm]: camera-frame unit normals, (0,0,0) = none }
+ *   fxm .. cym   the model maps' intrinsics at Hm x Wm
+ *   state        read: Tf = (R | t)
+ *   per visited pixel, fp32:
+ *     d = depth[y][x];  skip unless d > d_near, d <= d_far and d finite (a NaN fails);  skip unless gate[y][x] >= gate_thr (when given)
+ *     xn = (((float)x + 0.5) - cx) / fx;  yn = (((float)y + 0.5) - cy) / fy;  p = (xn * d, yn * d, d)
+ *     q_j = ((R_j0 * p_x + R_j1 * p_y) + R_j2 * p_z) + t_j                      (j = x, y, z: the point in the model camera)
+ *     skip unless q_z > 0
+ *     u = fxm * (q_x / q_z) + cxm;  v = fym * (q_y / q_z) + cym
+ *     skip unless u >= 0 && u < (float)Wm && v >= 0 && v < (float)Hm            (a NaN fails)
+ *     iu = (int)floorf(u);  iv = (int)floorf(v);  dm = mdepth[iv][iu];  n = mnormal[:][iv][iu]
+ *     skip unless dm > 0 (a NaN fails);  skip if n == (0, 0, 0) or a component of n is not finite
+ *     m = (((((float)iu + 0.5) - cxm) / fxm) * dm,  ((((float)iv + 0.5) - cym) / fym) * dm,  dm)
+ *     e = q - m;  skip unless (e_x * e_x + e_y * e_y) + e_z * e_z <= dist_thr * dist_thr      (a NaN fails)
+ *     r = (n_x * e_x + n_y * e_y) + n_z * e_z
+ *     c = q x n:  c_x = q_y * n_z - q_z * n_y;  c_y = q_z * n_x - q_x * n_z;  c_z = q_x * n_y - q_y * n_x
+ *     J = (n_x, n_y, n_z, c_x, c_y, c_z)          (d r / d(v, omega) of the left perturbation q -> q + v + omega x q)
+ *     w = fabsf(r) <= huber ? 1 : huber / fabsf(r)
+ *   and for a pixel that was not skipped, in double from the promoted fp32 values (the product of two promoted floats is exact):
+ *     A_ij += (double)w * ((double)J_i * (double)J_j)   (i <= j);   g_i += (double)w * ((double)J_i * (double)r);
+ *     E += (double)w * ((double)r * (double)r);   count += 1
+ *   A lane adds its pixels in visiting order (pixel p = j Ws + i of lane l of workgroup b: p = 256 b + l, + 256 nwg, ...), then the
+ *   workgroup folds its lanes in a fixed order (a wave64 shuffle tree, then the 4 waves in wave order) and writes record b.
+ *   resid        device fp32 [H][W] or NULL: r at the visited pixels that were not skipped, a quiet NaN at every other pixel of the
+ *                map (the pixels that are not visited included): an alignment-error map
+ *   errors       NRGBD_E_NULL: depth, mdepth, mnormal, state or partial NULL;  NRGBD_E_SHAPE: H, W, Hm or Wm <= 0 or > 32768,
+ *                sub < 1, Hs or Ws 0, partial_bytes < nrgbd_icp_workspace(Hs, Ws);  NRGBD_E_ARG: fx, fy, fxm or fym <= 0 or not
+ *                finite, cx, cy, cxm or cym not finite, dist_thr or huber <= 0 or not finite, d_near < d_far not true (a NaN bound
+ *                included), a NaN gate_thr beside a gate;  NRGBD_E_ALIGN: state or partial not 8-byte aligned.  Checked in this
+ *                order, before anything touches the device.
+ * nrgbd_icp_update — no counterpart in the reference: the solve and the pose update, one workgroup, one launch.
+ *   init         HOST double [12] or NULL (= the identity), read at the call when step == 0
+ *   step == 0:   T = init; Tf = (float)T (rounded once); flag = 0; iterations = 0.  partial and log are not touched (may be NULL).
+ *   step >= 1:   S = the nwg records added in index order, ((rec_0 + rec_1) + rec_2) + ..., per value, in double / int64;
+ *     flag' = flag.  If flag == 0, in this order:
+ *       count < min_pairs                          -> flag' = NRGBD_ICP_FEW
+ *       a value of S (28 doubles) not finite       -> flag' = NRGBD_ICP_NONFINITE
+ *       the factorisation A = L D L^T of the symmetric A (A_ij = A_ji), amax = fmax(.. fmax(A_00, A_11) .., A_55):
+ *         for j = 0 .. 5:  D_j = A_jj, then for k = 0 .. j - 1 in turn: D_j = D_j - (L_jk * L_jk) * D_k
+ *                          for i = j + 1 .. 5:  s = A_ij, then for k = 0 .. j - 1: s = s - (L_ik * L_jk) * D_k;   L_ij = s / D_j
+ *         a pivot with D_j > min_pivot * amax not true (a NaN included) -> flag' = NRGBD_ICP_DEGENERATE
+ *       the solve A xi = -g:  for i = 0 .. 5: y_i = -g_i, then for k = 0 .. i - 1: y_i = y_i - L_ik * y_k
+ *                             z_i = y_i / D_i
+ *                             for i = 5 .. 0: xi_i = z_i, then for k = i + 1 .. 5: xi_i = xi_i - L_ki * xi_k
+ *       |xi|^2 = ((((xi_0 xi_0 + xi_1 xi_1) + xi_2 xi_2) + xi_3 xi_3) + xi_4 xi_4) + xi_5 xi_5
+ *       xi = (v, omega);  xx = o_x * o_x, yy, zz alike;  theta2 = (xx + yy) + zz
+ *       theta2 <= NRGBD_ICP_MAX_THETA2 (0.25: half a radian) not true -> flag' = NRGBD_ICP_LARGE
+ *       a = sin(theta) / theta and b = (1 - cos(theta)) / theta^2 as the Taylor polynomials of degree 8 in theta2, Horner form:
+ *         a = ca_8, then for k = 7 .. 0: a = a * theta2 + ca_k,  ca_k = (-1)^k / (2k + 1)!   (one division; the factorial is exact)
+ *         b = cb_8, then for k = 7 .. 0: b = b * theta2 + cb_k,  cb_k = (-1)^k / (2k + 2)!
+ *         (the truncation error is below 1e-22 for theta <= 0.5)
+ *       xy = o_x * o_y, xz, yz alike;  Rw = I + a [omega]x + b [omega]x^2 entry by entry:
+ *         Rw_00 = 1 - b * (yy + zz)    Rw_01 = b * xy - a * o_z    Rw_02 = b * xz + a * o_y
+ *         Rw_10 = b * xy + a * o_z     Rw_11 = 1 - b * (xx + zz)   Rw_12 = b * yz - a * o_x
+ *         Rw_20 = b * xz - a * o_y     Rw_21 = b * yz + a * o_x    Rw_22 = 1 - b * (xx + yy)
+ *       T'_ij = (Rw_i0 * T_0j + Rw_i1 * T_1j) + Rw_i2 * T_2j  for j = 0 .. 3, then T'_i3 = T'_i3 + v_i    (dR <- Rw dR, dt <- Rw dt + v)
+ *       Tf = (float)T' (rounded once);  iterations += 1
+ *     A step that sets a flag, or finds one set, leaves T, Tf and iterations alone: their bits stay.
+ *     log[4 (step - 1) ..] = ((double)count, E, |xi|^2, (double)flag'), always written; |xi|^2 is 0 where no solve was completed.
+ *   errors       NRGBD_E_NULL: state NULL; for step >= 1 partial or log NULL;  NRGBD_E_SHAPE: step < 0; for step >= 1 nwg < 1 or
+ *                nwg > NRGBD_ICP_MAX_WG;  NRGBD_E_ARG: step == 0: an init entry that is not finite; step >= 1: min_pivot <= 0 or
+ *                not finite, min_pairs < 6;  NRGBD_E_ALIGN: state, and for step >= 1 partial or log, not 8-byte aligned.  Checked in
+ *                this order, before anything touches the device.
+ */
+#define NRGBD_ICP_MAX_WG 256
+#define NRGBD_ICP_RECORD_BYTES 240
+#define NRGBD_ICP_STATE_BYTES 152
+#define NRGBD_ICP_FEW 1
+#define NRGBD_ICP_NONFINITE 2
+#define NRGBD_ICP_DEGENERATE 3
+#define NRGBD_ICP_LARGE 4
+#define NRGBD_ICP_MAX_THETA2 0.25
+int nrgbd_icp_workgroups(int Hs, int Ws);
+long nrgbd_icp_workspace(int Hs, int Ws);
+int nrgbd_icp_terms_f32(const float* depth, const float* gate, float gate_thr, int H, int W, float d_near, float d_far,
+                        float fx, float fy, float cx, float cy, int sub, const float* mdepth, const float* mnormal, int Hm,
+                        int Wm, float fxm, float fym, float cxm, float cym, const void* state, float dist_thr, float huber,
+                        void* partial, long partial_bytes, float* resid, void* stream);
+int nrgbd_icp_update(void* state, const double* init, int step, const void* partial, int nwg, long long min_pairs,
+                     double min_pivot, double* log, void* stream);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,11 @@ TSDF_SCAN_PASS = 1024           # NRGBD_TSDF_SCAN_PASS
 TSDF_RAYCAST_MAX_STEPS = 65536  # NRGBD_TSDF_RAYCAST_MAX_STEPS
 TSDF_RAYCAST_TILE = 16          # NRGBD_TSDF_RAYCAST_TILE
 TSDF_RAYCAST_MAX_SIDE = 16384   # NRGBD_TSDF_RAYCAST_MAX_SIDE
+ICP_MAX_WG = 256                # NRGBD_ICP_MAX_WG
+ICP_RECORD_BYTES = 240          # NRGBD_ICP_RECORD_BYTES
+ICP_STATE_BYTES = 152           # NRGBD_ICP_STATE_BYTES
+ICP_FEW, ICP_NONFINITE, ICP_DEGENERATE, ICP_LARGE = 1, 2, 3, 4     # NRGBD_ICP_*: why an iteration stopped
+ICP_MAX_THETA2 = 0.25           # NRGBD_ICP_MAX_THETA2
 
 
 class WindowSlots(ctypes.Structure):
@@ -149,6 +154,11 @@ SIGNATURES = {
     "nrgbd_tsdf_extract_points_color": (_I, [_P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _F, _P, _L, _P, _P, _L, _P, _P]),
     "nrgbd_tsdf_extract_mesh_color": (_I, [_P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _F, _P, _L, _P, _P, _L, _P, _L, _P, _P]),
     "nrgbd_tsdf_raycast_color_f32": (_I, [_P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P, _P, _F, _F, _F, _F, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P]),
+    "nrgbd_icp_workgroups": (_I, [_I, _I]),
+    "nrgbd_icp_workspace": (_L, [_I, _I]),
+    "nrgbd_icp_terms_f32": (_I, [_P, _P, _F, _I, _I, _F, _F, _F, _F, _F, _F, _I, _P, _P, _I, _I, _F, _F, _F, _F, _P, _F, _F, _P, _L, _P,
+                                 _P]),
+    "nrgbd_icp_update": (_I, [_P, _P, _I, _P, _I, _c.c_longlong, _D, _P, _P]),
     "nrgbd_nhwc_stats_workgroups": (_I, [_L]),
     "nrgbd_nhwc_stats": (_I, [_P, _L, _I, _P, _P]),
     "nrgbd_nhwc_act": (_I, [_P, _P, _I, _P, _P, _I, _P, _L, _I, _I, _P]),

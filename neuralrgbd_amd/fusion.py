@@ -17,6 +17,9 @@ conventions (lattice, projection, update rule, crossings) are written out in inc
     frame's pixels into them in the same launch (ops.tsdf_integrate_color), `points(colors=True)`, `mesh(colors=True)` and
     `raycast(color=True)` read them out, and `FusionVideoStream(color=True)` fuses every frame's own picture from its ring slot;
     `to_uint8` and `save_ply(colors=...)` write them;
+  * tracking: `TSDFVolume.track` registers a depth frame against the volume from a pose guess (tracking.FrameTracker: ray casts and
+    point-to-plane Gauss-Newton iterations on the device, ops.icp_terms / ops.icp_update), and `FusionVideoStream(track=True)`
+    integrates every map at its tracked pose instead of the pushed one;
   * `fuse_sequence`, `save_ply`.
 """
 import math
@@ -114,6 +117,7 @@ class TSDFVolume:
         self._counts = torch.zeros(2, dtype=torch.int64, device=self.device)
         self._workspace = None
         self._mesh_counts = self._mesh_workspace = None
+        self._trackers = {}
 
     def reset(self):
         """An empty volume again (asynchronous)."""
@@ -263,6 +267,20 @@ class TSDFVolume:
         return ops.tsdf_raycast(self.tsdf, self.weight, self.origin, self.voxel_size, m, intrinsics, (H, W), depth_range, w_min=w_min,
                                 step=step, normals=normals, out=out, color=planes, rgb=bool(color))
 
+    def track(self, depth, extM_guess, intrinsics, levels=None, **kw):
+        """The pose of a depth frame registered against the volume, from a guess: tracking.FrameTracker(self, depth's size,
+        intrinsics, levels).track(depth, extM_guess, **kw), the tracker built once per (size, intrinsics, levels) and kept — the
+        second call with a size allocates nothing.  Returns a tracking.TrackResult (extM, ok, flag, log, delta).  Synchronises once,
+        at the end."""
+        from .tracking import DEFAULT_LEVELS, FrameTracker
+        levels = DEFAULT_LEVELS if levels is None else tuple((int(s), int(n)) for s, n in levels)
+        size = tuple(int(n) for n in depth.shape[-2:])
+        K = intrinsics_at(intrinsics, *size) if isinstance(intrinsics, dict) else tuple(float(k) for k in intrinsics)
+        key = (size, K, levels)
+        if key not in self._trackers:
+            self._trackers[key] = FrameTracker(self, size, intrinsics, levels)
+        return self._trackers[key].track(depth, extM_guess, **kw)
+
 
 def to_uint8(rgb):
     """fp32 colours in [0, 1] (a tensor on any device, or an array) -> uint8 of the same shape and kind: rint(clip(c, 0, 1) * 255),
@@ -293,10 +311,18 @@ class FusionVideoStream(VideoDepthStream):
     the plane-sweep grid), through the affine a = std, b = mean, which undoes the ingest's normalisation: colours in [0, 1].
     The R-Net's volume is read where it lies (its channels-last view) when the candidates fill the kernels' candidate width (64 or
     128 candidates, 256 with if_upsample_d); another count runs zero-padded to that width, the view is then a slice of the padded
-    pixels and ops.depth_regress makes a planar copy of it first."""
+    pixels and ops.depth_regress makes a planar copy of it first.
+    track=True: frame-to-model tracking (tracking.FrameTracker; track_kwargs go to TSDFVolume.track).  The first depth frame of a
+    trajectory is integrated at its pushed pose.  For every later one, with E the pushed extrinsics and T the poses that were
+    integrated, the guess is E_i E_prev^-1 T_prev — the pushed relative motion on top of the last integrated pose —, the frame's
+    regressed depth map is tracked against the volume from it with the stream's own gate and depth range, and the map is integrated
+    at the tracked pose; where the track is lost it is integrated at the guess and `n_track_lost` counts it.  `last_ext` is the pose
+    that was integrated (what render() uses), `tracked_poses` keeps (ref_index, extM, ok).  A tracked push synchronises once per depth
+    frame (the tracker reads its result back).  The network's own cost volume keeps using the pushed poses: tracking touches only
+    where the map is integrated.  With track=False nothing of this is constructed or launched."""
 
     def __init__(self, model, cam_intrinsics, d_candi, volume, t_win_r=2, source="refined", conf_threshold=0., weight="uniform",
-                 depth_range=None, color=False, **video_kwargs):
+                 depth_range=None, color=False, track=False, track_kwargs=None, **video_kwargs):
         from .nets import require_volume_refiner
         require_volume_refiner(model, "FusionVideoStream")
         if source not in ("refined", "dpv"):
@@ -319,6 +345,13 @@ class FusionVideoStream(VideoDepthStream):
         self.ext_ring = GtRing(self.n_slots)                    # which push's extrinsic a slot holds: evaluate.GtRing's pairing
         self._ext = [None] * self.n_slots
         self.n_integrated = 0
+        self.track = bool(track)
+        if track_kwargs is not None and not self.track:
+            raise ValueError("FusionVideoStream: track_kwargs come with track=True")
+        self.track_kwargs = dict(track_kwargs or {})
+        self.n_track_lost = 0
+        self.tracked_poses = []
+        self._prev = None                                       # (pushed extrinsic, integrated pose) of the last frame integrated
         super().__init__(model, cam_intrinsics, d_candi, t_win_r=t_win_r, **video_kwargs)
         if _indexed(volume.device) != _indexed(self.device):
             raise ValueError("FusionVideoStream: the volume is on %s, the stream on %s" % (volume.device, self.device))
@@ -329,6 +362,8 @@ class FusionVideoStream(VideoDepthStream):
         self.ext_ring.clear()
         self._ext = [None] * self.n_slots
         self.last_ext = None                                    # the extrinsic of the last frame integrated on this trajectory
+        self._prev = None
+        self.tracked_poses = []
 
     def render(self, extM=None, size=None, normals=False, color=False, **kw):
         """The fused model as a depth map (and normals, and with color=True its colours): TSDFVolume.raycast from extM — by default the extrinsic of the last frame
@@ -372,10 +407,20 @@ class FusionVideoStream(VideoDepthStream):
             # last 2 t_win_r + 1 >= t_win_r + 2: its slot still holds its picture, written by an ingest enqueued on this stream
             kw = dict(color=self.ring[ref_index % self.R], color_intrinsics=intrinsics_at(self.cam, self.H, self.W),
                       color_affine=(self.std, self.mean))
-        if self.volume.integrate(depth, self._ext[slot], self.cam, gate=gate, gate_thr=self.gate_thr, weight=wmap,
+        pose = self._ext[slot]
+        if self.track and self._prev is not None:
+            guess = pose @ np.linalg.solve(self._prev[0], self._prev[1])       # E_i E_prev^-1 T_prev, float64 on the host
+            res = self.volume.track(depth, guess, self.cam, gate=gate, gate_thr=self.gate_thr, depth_range=self.depth_range,
+                                    **self.track_kwargs)
+            self.n_track_lost += 0 if res.ok else 1
+            self.tracked_poses.append((ref_index, res.extM, res.ok))
+            pose = res.extM                                     # lost: the guess (as the ray casts used it, float32-rounded)
+        if self.volume.integrate(depth, pose, self.cam, gate=gate, gate_thr=self.gate_thr, weight=wmap,
                                  depth_range=self.depth_range, **kw):
             self.n_integrated += 1
-            self.last_ext = self._ext[slot]
+            self.last_ext = pose
+            if self.track:
+                self._prev = (np.asarray(self._ext[slot], dtype=np.float64), np.asarray(pose, dtype=np.float64))
         return out
 
     def push(self, frame, extM):

@@ -1953,3 +1953,95 @@ def _tsdf_raycast_color(tsdf, weight, color, X, Y, Z, o, voxel_size, pose, centr
                                                       _stream(tsdf))
     _lib.check(rc, "nrgbd_tsdf_raycast_color_f32")
     return tuple(outs)
+
+
+# ---- frame-to-model tracking (icp.hip; neuralrgbd_amd/tracking.py) --------------------------------------------------------------
+
+ICP_STATE_WORDS = _lib.ICP_STATE_BYTES // 8         # the state as float64 words: T [12], then Tf [12] fp32, flag and iterations int32
+ICP_RECORD_WORDS = _lib.ICP_RECORD_BYTES // 8       # a partial record as float64 words: 28 sums, the int64 count, padding
+
+
+def icp_workgroups(Hs, Ws):
+    """Partial records nrgbd_icp_terms_f32 writes for an Hs x Ws visit (needs no GPU)."""
+    rc = _lib.load().nrgbd_icp_workgroups(int(Hs), int(Ws))
+    if rc < 0:
+        _lib.check(rc, "nrgbd_icp_workgroups")
+    return rc
+
+
+def icp_workspace(Hs, Ws):
+    """Bytes of `partial` nrgbd_icp_terms_f32 needs for an Hs x Ws visit (needs no GPU)."""
+    rc = _lib.load().nrgbd_icp_workspace(int(Hs), int(Ws))
+    if rc < 0:
+        _lib.check(rc, "nrgbd_icp_workspace")
+    return rc
+
+
+def _icp_words(t, name, words, dev, who):
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() < words
+            or (dev is not None and t.device != dev) or not t.is_cuda):
+        raise ValueError("%s: %s must be a contiguous CUDA float64 tensor of at least %d elements%s"
+                         % (who, name, words, "" if dev is None else " on %s" % (dev,)))
+    return t
+
+
+def icp_terms(depth, intrinsics, sub, mdepth, mnormal, model_intrinsics, state, partial, dist_thr, huber, depth_range=(0.0, float("inf")),
+              gate=None, gate_thr=0.0, resid=None):
+    """Association, point-to-plane residuals and the partial normal equations of one Gauss-Newton iteration, one launch
+    (nrgbd_icp_terms_f32; the per-pixel operation sequence is written out in include/nrgbd.h).
+    depth (and gate, resid, or None): contiguous CUDA fp32 [H,W]; intrinsics = (fx, fy, cx, cy) at H x W; sub: every sub-th pixel
+    is visited; mdepth [Hm,Wm] / mnormal [3,Hm,Wm]: the model maps of tsdf_raycast with model_intrinsics at their size; state: float64
+    [ICP_STATE_WORDS] (icp_update's); partial: float64, at least icp_workspace(H // sub, W // sub) bytes; depth_range = (d_near,
+    d_far].  Returns the number of records written.  Nothing is allocated, nothing synchronised."""
+    depth = _need(depth, "depth", strided=True)
+    if depth.dim() != 2:
+        raise ValueError("icp_terms: depth must be [H,W], got %s" % (tuple(depth.shape),))
+    dev = depth.device
+    H, W = depth.shape
+    mdepth = _need(mdepth, "mdepth", strided=True)
+    if mdepth.dim() != 2:
+        raise ValueError("icp_terms: mdepth must be [Hm,Wm], got %s" % (tuple(mdepth.shape),))
+    Hm, Wm = mdepth.shape
+    for t, nm, shape in ((depth, "depth", (H, W)), (gate, "gate", (H, W)), (resid, "resid", (H, W)), (mdepth, "mdepth", (Hm, Wm)),
+                         (mnormal, "mnormal", (3, Hm, Wm))):
+        if t is None and nm in ("gate", "resid"):
+            continue
+        t = _need(t, nm, shape, strided=True)
+        if t.device != dev or not t.is_contiguous():
+            raise ValueError("icp_terms: %s must be contiguous and on %s" % (nm, dev))
+    k, km = tuple(float(x) for x in intrinsics), tuple(float(x) for x in model_intrinsics)
+    if len(k) != 4 or len(km) != 4:
+        raise ValueError("icp_terms: intrinsics = (fx, fy, cx, cy)")
+    sub = int(sub)
+    state = _icp_words(state, "state", ICP_STATE_WORDS, dev, "icp_terms")
+    partial = _icp_words(partial, "partial", 0, dev, "icp_terms")
+    with torch.cuda.device(dev):
+        rc = _lib.load().nrgbd_icp_terms_f32(_p(depth), _p(gate), float(gate_thr), H, W, float(depth_range[0]), float(depth_range[1]),
+                                             k[0], k[1], k[2], k[3], sub, _p(mdepth), _p(mnormal), Hm, Wm, km[0], km[1], km[2], km[3],
+                                             _p(state), float(dist_thr), float(huber), _p(partial), partial.numel() * 8, _p(resid),
+                                             _stream(depth))
+    _lib.check(rc, "nrgbd_icp_terms_f32")
+    return icp_workgroups(H // sub, W // sub)
+
+
+def icp_update(state, step, partial=None, nwg=0, min_pairs=6, min_pivot=1e-6, log=None, init=None):
+    """The solve and the pose update of one Gauss-Newton iteration, one launch of one workgroup (nrgbd_icp_update; every operation is
+    written out in include/nrgbd.h).  step == 0: the state from `init` (a host [3,4] or [4,4] float64 motion; None: the identity).
+    step >= 1: the `nwg` records of `partial` added in index order, the tests, the L D L^T solve, T <- exp(xi) T; row step - 1 of
+    log (float64 [rows,4]) = (count, E, |xi|^2, flag).  Nothing is allocated, nothing synchronised."""
+    state = _icp_words(state, "state", ICP_STATE_WORDS, None, "icp_update")
+    dev = state.device
+    step = int(step)
+    cinit = None
+    if init is not None:
+        m = np.asarray(init, dtype=np.float64)
+        if m.shape not in ((3, 4), (4, 4)):
+            raise ValueError("icp_update: init is a [3,4] or [4,4] motion, got %s" % (m.shape,))
+        cinit = (ctypes.c_double * 12)(*m[:3, :4].reshape(-1).tolist())
+    if step > 0:
+        partial = _icp_words(partial, "partial", int(nwg) * ICP_RECORD_WORDS, dev, "icp_update")
+        log = _icp_words(log, "log", 4 * step, dev, "icp_update")
+    with torch.cuda.device(dev):
+        rc = _lib.load().nrgbd_icp_update(_p(state), cinit, step, _p(partial if step > 0 else None), int(nwg), int(min_pairs),
+                                          float(min_pivot), _p(log if step > 0 else None), _stream(state))
+    _lib.check(rc, "nrgbd_icp_update")

@@ -1,0 +1,150 @@
+"""Frame-to-model tracking: a depth frame registered against the fused TSDF volume before it is integrated (KinectFusion's
+tracking half; csrc/icp.hip, include/nrgbd.h spells out every operation).
+
+The reference takes its poses from an external odometry, and FusionVideoStream integrates each map at exactly the pose pushed with
+it; a drifting pose smears the volume.  `FrameTracker` corrects a pose guess: the volume is ray cast from the guess
+(TSDFVolume.raycast: depth and camera-frame normals), the frame's depth map is associated with it projectively, and a few
+Gauss-Newton iterations on the point-to-plane residuals — two launches each, ops.icp_terms and ops.icp_update, coarse to fine —
+find the motion dT between the frame's camera and the guess.  Nothing is read back between iterations; one device-to-host copy at
+the end fetches the state and the iteration log.
+
+Deliberately not built: frame normals and a normal-angle gate, photometric terms, relocalisation after a loss, re-integration of the
+volume after a pose correction."""
+import math
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+
+FLAGS = {0: "ok", _lib.ICP_FEW: "too few pairs", _lib.ICP_NONFINITE: "a sum is not finite", _lib.ICP_DEGENERATE: "degenerate geometry",
+         _lib.ICP_LARGE: "a step past half a radian"}
+DEFAULT_LEVELS = ((4, 10), (2, 5), (1, 4))
+
+
+class TrackResult:
+    """extM [4,4] float64: the frame's world -> camera pose (the guess when the track was lost); ok: flag == 0; flag: 0 or the
+    NRGBD_ICP_* reason (tracking.FLAGS); log [iterations,4] float64 = (pairs, weighted squared error, |xi|^2, flag) per iteration;
+    delta [4,4] float64: the motion frame camera -> guess camera that was found."""
+
+    def __init__(self, extM, flag, log, delta):
+        self.extM, self.flag, self.log, self.delta = extM, int(flag), log, delta
+        self.ok = self.flag == 0
+
+    def __repr__(self):
+        return "TrackResult(ok=%s, flag=%d (%s), iterations=%d)" % (self.ok, self.flag, FLAGS.get(self.flag, "?"), len(self.log))
+
+
+def _levels(levels):
+    out = tuple((int(s), int(n)) for s, n in levels)
+    if not out or any(s < 1 or n < 1 for s, n in out):
+        raise ValueError("FrameTracker: levels = ((sub, iterations), ...), both >= 1; got %s" % (levels,))
+    return out
+
+
+class FrameTracker:
+    """Tracks H x W depth frames against `volume`.  size = (H, W); intrinsics: (fx, fy, cx, cy) at that size or a cam_intrinsics
+    dict; levels: (sub, iterations) coarse to fine — a level visits every sub-th pixel of the frame and ray casts the model at
+    (H // sub, W // sub).  Owns every buffer (the levels' model maps, the state, the partial records, the log, a residual map):
+    after construction `track` allocates nothing on the device."""
+
+    def __init__(self, volume, size, intrinsics, levels=DEFAULT_LEVELS):
+        from .fusion import intrinsics_at
+        self.volume = volume
+        self.H, self.W = (int(n) for n in size)
+        self.levels = _levels(levels)
+        dev = volume.device
+        self._levels = []
+        words = 0
+        for sub, iters in self.levels:
+            Hs, Ws = self.H // sub, self.W // sub
+            if Hs < 1 or Ws < 1:
+                raise ValueError("FrameTracker: a %d x %d frame has no pixel at sub = %d" % (self.H, self.W, sub))
+            if isinstance(intrinsics, dict):
+                K = intrinsics_at(intrinsics, Hs, Ws)
+            else:
+                K = tuple(float(k) / sub for k in intrinsics)
+            maps = (torch.empty((Hs, Ws), dtype=torch.float32, device=dev), torch.empty((3, Hs, Ws), dtype=torch.float32, device=dev))
+            self._levels.append((sub, iters, (Hs, Ws), K, maps))
+            words = max(words, ops.icp_workspace(Hs, Ws) // 8)
+        self.K = intrinsics_at(intrinsics, self.H, self.W) if isinstance(intrinsics, dict) else tuple(float(k) for k in intrinsics)
+        if len(self.K) != 4:
+            raise ValueError("FrameTracker: intrinsics = (fx, fy, cx, cy)")
+        self.iterations = sum(n for _, n in self.levels)
+        # the state and the log in one buffer: one copy fetches both
+        self._result = torch.zeros(ops.ICP_STATE_WORDS + 4 * self.iterations, dtype=torch.float64, device=dev)
+        self._state, self._log = self._result[:ops.ICP_STATE_WORDS], self._result[ops.ICP_STATE_WORDS:]
+        self._partial = torch.zeros(words, dtype=torch.float64, device=dev)
+        self._resid = torch.empty((self.H, self.W), dtype=torch.float32, device=dev)
+
+    def _params(self, dist_thr, huber):
+        dist_thr = 2.0 * self.volume.trunc if dist_thr is None else float(dist_thr)
+        huber = self.volume.voxel_size if huber is None else float(huber)
+        return dist_thr, huber
+
+    def _depth(self, depth, gate):
+        if depth.dim() == 3 and depth.shape[0] == 1:
+            depth = depth[0]
+            gate = gate if gate is None else gate.view(depth.shape)
+        if tuple(depth.shape) != (self.H, self.W):
+            raise ValueError("FrameTracker: depth is [%d,%d], got %s" % (self.H, self.W, tuple(depth.shape)))
+        return depth, gate
+
+    def track(self, depth, extM_guess, gate=None, gate_thr=None, depth_range=(0., float("inf")), w_min=1., dist_thr=None, huber=None,
+              min_frac=0.1, min_pivot=1e-6):
+        """depth [H,W] (or [1,H,W]) CUDA fp32 against the volume seen from extM_guess (host [3,4] or [4,4] world -> camera; the ray
+        casts use float32(extM_guess[:3,:4])).  gate / gate_thr and depth_range = (d_near, d_far] as TSDFVolume.integrate takes them;
+        w_min: the ray cast's weight threshold; dist_thr: a pair is dropped beyond this distance (default 2 trunc); huber: residuals
+        beyond it are down-weighted (default voxel_size) — parameters, not measurements; min_frac: a level needs
+        max(6, ceil(min_frac Hs Ws)) pairs; min_pivot: the relative pivot below which the geometry counts as degenerate.
+        Per level one ray cast and its iterations of two launches each; dT carries over between the levels.  Returns a TrackResult:
+        extM = dT^-1 T_g in float64 on the host, T_g the float32-rounded guess promoted — the guess itself when the track was lost.
+        Reads the state and the log back at the end: the one place this object synchronises (as TSDFVolume.points does)."""
+        from .fusion import _host_matrix
+        if (gate is None) != (gate_thr is None):
+            raise ValueError("FrameTracker.track: gate and gate_thr come together")
+        depth, gate = self._depth(depth, gate)
+        g = _host_matrix(extM_guess, "FrameTracker.track")
+        Tg = np.eye(4)
+        Tg[:3, :4] = g[:3, :4].astype(np.float32).astype(np.float64)
+        dist_thr, huber = self._params(dist_thr, huber)
+        ops.icp_update(self._state, 0)
+        step = 0
+        for sub, iters, (Hs, Ws), K, maps in self._levels:
+            self.volume.raycast(Tg, K, (Hs, Ws), depth_range=depth_range, w_min=w_min, normals=True, out=maps)
+            min_pairs = max(6, int(math.ceil(min_frac * Hs * Ws)))
+            for _ in range(iters):
+                step += 1
+                nwg = ops.icp_terms(depth, self.K, sub, maps[0], maps[1], K, self._state, self._partial, dist_thr, huber,
+                                    depth_range=depth_range, gate=gate, gate_thr=0.0 if gate_thr is None else gate_thr)
+                ops.icp_update(self._state, step, self._partial, nwg, min_pairs=min_pairs, min_pivot=min_pivot, log=self._log)
+        host = self._result.cpu().numpy()                           # the single synchronisation
+        delta = np.eye(4)
+        delta[:3, :4] = host[:12].reshape(3, 4)
+        flag = int(host[ops.ICP_STATE_WORDS - 1:ops.ICP_STATE_WORDS].view(np.int32)[0])
+        log = host[ops.ICP_STATE_WORDS:].reshape(-1, 4).copy()
+        extM = np.linalg.solve(delta, Tg) if flag == 0 else Tg
+        return TrackResult(extM, flag, log, delta)
+
+    def residual_map(self, depth, extM, extM_model=None, gate=None, gate_thr=None, depth_range=(0., float("inf")), w_min=1.,
+                     dist_thr=None, huber=None):
+        """The point-to-plane residual of every pixel of `depth` seen from extM against the volume ray cast at full size from
+        extM_model (default: extM itself, the final pose of a track): [H,W] CUDA fp32, NaN where a pixel has no pair — one more
+        icp_terms call (owned buffer: overwritten by the next call).  Synchronises nothing."""
+        from .fusion import _host_matrix
+        if (gate is None) != (gate_thr is None):
+            raise ValueError("FrameTracker.residual_map: gate and gate_thr come together")
+        depth, gate = self._depth(depth, gate)
+        Tf = np.eye(4)
+        Tf[:3, :4] = _host_matrix(extM, "FrameTracker.residual_map")[:3, :4]
+        Tm = Tf
+        if extM_model is not None:
+            Tm = np.eye(4)
+            Tm[:3, :4] = _host_matrix(extM_model, "FrameTracker.residual_map")[:3, :4].astype(np.float32).astype(np.float64)
+        sub, _, size, K, maps = min(self._levels, key=lambda l: l[0])
+        dist_thr, huber = self._params(dist_thr, huber)
+        self.volume.raycast(Tm, K, size, depth_range=depth_range, w_min=w_min, normals=True, out=maps)
+        ops.icp_update(self._state, 0, init=Tm @ np.linalg.inv(Tf))
+        ops.icp_terms(depth, self.K, sub, maps[0], maps[1], K, self._state, self._partial, dist_thr, huber, depth_range=depth_range,
+                      gate=gate, gate_thr=0.0 if gate_thr is None else gate_thr, resid=self._resid)
+        return self._resid
