@@ -334,6 +334,7 @@ int nrgbd_logsoftmax_d(const float* a, const float* b, float scale, float* out,
  * Replaces: mutils/misc.py:532-548 depth_val_regression (BV_log=True; a Python loop over
  * D) and the max_d of test_utils/export_res.py:58-59.
  *   logp [D][n]; d_candi [D]; depth [n] or NULL; conf [n] or NULL (max_k logp)
+ *   A column that holds a NaN has depth NaN AND conf NaN (torch.max keeps a NaN; the first NaN of the column is returned).
  */
 int nrgbd_depth_regress(const float* logp, const float* d_candi,
                         float* depth, float* conf, int D, long n, void* stream);
@@ -345,6 +346,7 @@ int nrgbd_depth_regress(const float* logp, const float* d_candi,
  *   logp [D][n]; d_candi [D]
  *   depth [n] or NULL   sum_k exp(logp_k) d_k          conf [n] or NULL   exp(max_k logp_k)
  *   depth_u16, conf_u16 [n] or NULL   (map * scale) truncated toward zero (numpy astype), clamped to [0, 65535]
+ *   A column that holds a NaN has depth NaN and conf NaN, as nrgbd_depth_regress; a NaN map value is written as 0 in the uint16 maps.
  */
 int nrgbd_export_depth_u16(const float* logp, const float* d_candi, float depth_scale, float conf_scale,
                            float* depth, float* conf, unsigned short* depth_u16, unsigned short* conf_u16,

@@ -5,6 +5,11 @@
 
 namespace nrgbd {
 
+// (v - m) - ls with ONE rounding.  In fp32 both subtractions round at the magnitude |v - m|: on a peaked column (|log p| of 100 and
+// more) that is twice the half ulp of the result, and at small D nothing else in the error budget is as large (tests/softmax_ref.py).
+// v - m is exact in double, the second subtraction rounds at 2^-53, the conversion rounds once; IEEE classes are what they were
+__device__ __forceinline__ float logp_of(float v, float m, float ls) { return (float)(((double)v - (double)m) - (double)ls); }
+
 // out = log_softmax_k(scale * a + b)   (models/basic.py:299-300, models/KVNET.py:172-173)
 template <int DREG>  // DREG > 0: D <= DREG, column cached in registers; 0: three passes over memory
 __global__ __launch_bounds__(256) void logsoftmax_d_kernel(const float* __restrict__ a,
@@ -32,18 +37,29 @@ __global__ __launch_bounds__(256) void logsoftmax_d_kernel(const float* __restri
         const float ls = logf(s);
 #pragma unroll
         for (int k = 0; k < DREG; ++k)
-            if (k < D) out[(size_t)k * n + p] = (col[k] - m) - ls;
+            if (k < D) out[(size_t)k * n + p] = logp_of(col[k], m, ls);
     } else {
         float m = -INFINITY;
         for (int k = 0; k < D; ++k) m = fmaxf(m, load(k));
         float s = 0.f;
         for (int k = 0; k < D; ++k) s += expf(load(k) - m);
         const float ls = logf(s);
-        for (int k = 0; k < D; ++k) out[(size_t)k * n + p] = (load(k) - m) - ls;
+        for (int k = 0; k < D; ++k) out[(size_t)k * n + p] = logp_of(load(k), m, ls);
     }
 }
 
-// depth = sum_k exp(logp_k) * d_k, conf = max_k logp_k   (mutils/misc.py:532-548)
+// The confidence of a column that holds a NaN: torch.max keeps a NaN, fmaxf drops it (such a column came out with a NaN depth and a
+// finite confidence).  A NaN entry always makes the depth sum NaN, so only a pixel whose sum IS NaN walks its column again and takes
+// the first NaN it finds; every other pixel pays one comparison after its loop and keeps the bits fmaxf gave it
+__device__ __forceinline__ float first_nan(const float* __restrict__ col, size_t stride, int D, float m) {
+    for (int k = 0; k < D; ++k) {
+        const float v = col[(size_t)k * stride];
+        if (v != v) return v;
+    }
+    return m;
+}
+
+// depth = sum_k exp(logp_k) * d_k, conf = max_k logp_k (NaN when the column holds one)   (mutils/misc.py:532-548)
 __global__ __launch_bounds__(256) void depth_regress_kernel(const float* __restrict__ logp,
                                                             const float* __restrict__ d_candi,
                                                             float* __restrict__ depth,
@@ -56,6 +72,7 @@ __global__ __launch_bounds__(256) void depth_regress_kernel(const float* __restr
         acc = acc + expf(v) * d_candi[k];
         m = fmaxf(m, v);
     }
+    if (__builtin_expect(acc != acc, 0)) m = first_nan(logp + p, n, D, m);
     if (depth) depth[p] = acc;
     if (conf) conf[p] = m;
 }
@@ -101,7 +118,7 @@ __global__ __launch_bounds__(256) void logsoftmax_d4_kernel(const float* __restr
 #pragma unroll
         for (int t = 0; t < KMAX; ++t) {
             const int k = part + 4 * t;
-            if (k < D) out[(size_t)k * n + p] = (col[t] - m) - ls;
+            if (k < D) out[(size_t)k * n + p] = logp_of(col[t], m, ls);
         }
     }
 }
@@ -141,6 +158,7 @@ __global__ __launch_bounds__(256) void export_depth_u16_kernel(const float* __re
         acc = acc + exp_rn(v) * d_candi[k];
         m = fmaxf(m, v);
     }
+    if (__builtin_expect(acc != acc, 0)) m = first_nan(logp + p, n, D, m);
     const float c = exp_rn(m);
     if (depth) depth[p] = acc;
     if (conf) conf[p] = c;
@@ -184,6 +202,7 @@ __global__ __launch_bounds__(256) void depth_rows_kernel(const float* __restrict
         __syncthreads();
     }
     if (tid >= ROWS_PX || p >= n) return;
+    if (__builtin_expect(acc != acc, 0)) m = first_nan(logp + p * (size_t)D, 1, D, m);
     if constexpr (EXPORT) {
         const float c = exp_rn(m);
         if (depth) depth[p] = acc;

@@ -342,7 +342,7 @@ int oracle_depth_regress(const float* logp, const float* d_candi, int D, size_t 
         for (int k = 0; k < D; ++k) {
             float v = logp[(size_t)k * n + p];
             acc = acc + expf(v) * d_candi[k];
-            m = v > m ? v : m;
+            m = (v > m || v != v) ? v : m;          /* torch.max: a NaN, once taken, stays */
         }
         if (depth) depth[p] = acc;
         if (conf) conf[p] = m;
@@ -418,7 +418,7 @@ int oracle_export_depth_u16(const float* logp, const float* d_candi, int D, size
         for (int k = 0; k < D; ++k) {
             float v = logp[(size_t)k * n + p];
             acc = acc + exp_rn(v) * d_candi[k];
-            m = v > m ? v : m;
+            m = (v > m || v != v) ? v : m;          /* as oracle_depth_regress */
         }
         float c = exp_rn(m);
         if (depth) depth[p] = acc;
