@@ -666,6 +666,10 @@ int nrgbd_rnet_pack(const float* dpv_log, const float* feat, int feat_planar, fl
  *   stay on the vendor library): x [P][C], stats [nrgbd_nhwc_stats_workgroups(P)][2*C]; C in {32, 64, 128}.
  * nrgbd_nhwc_act: y[p*ldy + c] = act(x*s+t) [+ act(res*s'+t')] — the loader's prologue as a stand-alone pass, for
  *   consumers that are not the conv kernel (pooling, the SPP concat of psm_submodule.py:160-163, the 1x1 head).
+ * nrgbd_nhwc_act_lean: the same pass, the same bits, in a shape that shares a CU with a matrix-bound convolution of another
+ *   stream: wg_per_cu (1 .. 8, else NRGBD_E_ARG) workgroups of one wave per SIMD per CU walk the tensor with a grid stride, 32
+ *   registers per lane, 16 * C bytes of LDS.  wg_per_cu = 1 beside a convolution, more when the pass runs alone.  C a power of two
+ *   in 4 .. 1024, P <= 2^30, ldy <= 2^22 (NRGBD_E_SHAPE otherwise); x, res and y 16-byte aligned (NRGBD_E_ALIGN).
  */
 /*
  * nrgbd_conv2d_taps_f32 — the trunk's remaining convolution forms on the same kernel (round 2: no vendor convolution is left in
@@ -894,6 +898,8 @@ int nrgbd_nhwc_stats_workgroups(long P);
 int nrgbd_nhwc_stats(const float* x, long P, int C, float* stats, void* stream);
 int nrgbd_nhwc_act(const float* x, const float* x_ss, int x_relu, const float* res, const float* res_ss,
                    int res_relu, float* y, long P, int C, int ldy, void* stream);
+int nrgbd_nhwc_act_lean(const float* x, const float* x_ss, int x_relu, const float* res, const float* res_ss,
+                        int res_relu, float* y, long P, int C, int ldy, int wg_per_cu, void* stream);
 /*
  * On-device depth evaluation (depth_eval.hip; neuralrgbd_amd/evaluate.py): the error metrics of a depth map against ground truth
  * as sums and counts that stay on the device, per confidence set.  Replaces: the host evaluation of test_utils/export_res.py:108-116

@@ -162,6 +162,7 @@ SIGNATURES = {
     "nrgbd_nhwc_stats_workgroups": (_I, [_L]),
     "nrgbd_nhwc_stats": (_I, [_P, _L, _I, _P, _P]),
     "nrgbd_nhwc_act": (_I, [_P, _P, _I, _P, _P, _I, _P, _L, _I, _I, _P]),
+    "nrgbd_nhwc_act_lean": (_I, [_P, _P, _I, _P, _P, _I, _P, _L, _I, _I, _I, _P]),
 }
 
 _lib = None

@@ -17,6 +17,7 @@
 // then 9 taps x 2 k-groups, each = 2 A reads (LDS, b128) + COUT/32 B loads (L2, one 1 KB line per wave) +
 // 8 * COUT/32 MFMAs.  The raw words of block c+1 (input and residual operand) are fetched into registers
 // while the MFMAs of block c run, one 16-B load per step, and normalised / published to LDS after the loop.
+#include <cstdint>
 #include <cstdlib>
 
 #include "conv_tile.hpp"
@@ -406,6 +407,88 @@ __global__ __launch_bounds__(256) void nhwc_act_kernel(const float* __restrict__
     *reinterpret_cast<f32x4*>(y + p * ldy + c) = v;
 }
 
+// The same pass in a shape that can be resident on a CU BESIDE a matrix-bound convolution of another stream: a bounded
+// grid of k workgroups per CU (one wave per SIMD each) walks the pixels with a grid stride, inside the kLeanVgprs registers per lane
+// that two waves of a trunk convolution leave free on a SIMD.  Every lane has kLeanWords slots of one 16-byte word of x and one of
+// res each, a slot requested again as soon as it has been stored: up to 4 x 64 x 2 x kLeanWords x 16 B = 16 KB of loads in flight per
+// CU (a third slot would reach HBM rate from four waves, and does not fit).  What makes two fit the registers:
+//   * 256 % (C / 4) == 0, so a lane keeps its channel word over the whole walk: its addresses are a uniform base (scalar registers)
+//     plus a 32-bit lane offset that never changes;
+//   * the accesses are buffer accesses whose descriptor ends with the tensor: the lanes of a partial last step, and whole steps
+//     past the end, read zeros and write nothing, so there is no per-lane bounds code;
+//   * the (scale, shift) tables sit in 16 * C bytes of LDS, scales and shifts apart, and are read where they are used.
+// Its loads and stores are non-temporal: the three tensors are streamed once and are larger than the last-level cache (supposed: the
+// convolution beside the pass keeps more of its own lines).  Measured: 0.15 of the 0.35 ms per frame this form gains at config B come
+// from the shape and 0.2 from the cache policy (profiles/pass_overlap.txt).
+// Same arithmetic in the same order as nhwc_act_kernel (fma, max, the same for res, one add): the same bits.
+constexpr int kLeanWords = 2;
+constexpr int kLeanVgprs = 32;
+constexpr int kLeanNt = 2;       // cache policy of its loads and stores: non-temporal
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void lean_apply(f32x4& v, const float* tab, int C, bool affine, int relu) {
+    if (affine) {
+        const f32x4 s = *reinterpret_cast<const f32x4*>(tab), t = *reinterpret_cast<const f32x4*>(tab + C);
+        v.x = __builtin_fmaf(v.x, s.x, t.x); v.y = __builtin_fmaf(v.y, s.y, t.y);
+        v.z = __builtin_fmaf(v.z, s.z, t.z); v.w = __builtin_fmaf(v.w, s.w, t.w);
+    }
+    if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+}
+
+// The descriptor of the step that starts at pixel q of a [P][ld] tensor of which C channels per pixel are touched: its bytes end
+// with the last touched word of the step or of the tensor, whichever comes first (none at all from q = P on).  Raw buffer, no stride;
+// 0x00020000 is the gfx9 descriptor's 32-bit data format word
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t lean_window(const float* base, int q, int P, int ld, int C, int ppw) {
+    const int left = P - q, n = left < ppw ? left : ppw;
+    const unsigned bytes = n > 0 ? ((unsigned)(n - 1) * (unsigned)ld + (unsigned)C) * 4u : 0u;      // < 2^32: n <= 256, ld <= 2^22
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base + (long)q * ld), 0, (int)bytes, 0x00020000);
+}
+
+template <bool RES>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(kLeanVgprs)))
+void nhwc_act_lean_kernel(const float* __restrict__ x, const float* __restrict__ x_ss, int x_relu, const float* __restrict__ res,
+                          const float* __restrict__ res_ss, int res_relu, float* __restrict__ y, int P, int C, int ldy) {
+    extern __shared__ __attribute__((aligned(16))) float lean_tab[];        // x: [C] scales, [C] shifts; then the same of res
+    const int tid = threadIdx.x, cq = C >> 2, ppw = 256 / cq;               // ppw pixels per workgroup and step
+    const bool xa = x_ss != nullptr, ra = RES && res_ss != nullptr;
+    for (int j = tid; j < 2 * C; j += 256) {                                // [C][2] in memory -> scales and shifts apart
+        if (xa) lean_tab[(j & 1) * C + (j >> 1)] = x_ss[j];
+        if (ra) lean_tab[2 * C + (j & 1) * C + (j >> 1)] = res_ss[j];
+    }
+    __syncthreads();
+    const int lp = tid / cq, c = (tid - lp * cq) * 4;                       // this lane's pixel within the step, its channel word
+    const unsigned lx = (unsigned)tid * 16u;                                // its byte offset from the step's base in x / res ...
+    const unsigned ly = ((unsigned)lp * (unsigned)ldy + (unsigned)c) * 4u;  // ... and in y
+    const float* tx = lean_tab + c;
+    const int pstep = (int)gridDim.x * ppw;
+    int pb = (int)blockIdx.x * ppw;                                         // first pixel of the current step (uniform)
+    u32x4 v[kLeanWords], r[RES ? kLeanWords : 1];
+    auto request = [&](int u, int q) {                                      // slot u <- the words of the step that starts at pixel q
+        v[u] = __builtin_amdgcn_raw_buffer_load_b128(lean_window(x, q, P, C, C, ppw), lx, 0, kLeanNt);
+        if constexpr (RES) r[u] = __builtin_amdgcn_raw_buffer_load_b128(lean_window(res, q, P, C, C, ppw), lx, 0, kLeanNt);
+    };
+    auto finish = [&](int u, int q) {                                       // slot u -> y, for the step that starts at pixel q
+        f32x4 a = __builtin_bit_cast(f32x4, v[u]);
+        lean_apply(a, tx, C, xa, x_relu);
+        if constexpr (RES) {
+            f32x4 b = __builtin_bit_cast(f32x4, r[u]);
+            lean_apply(b, tx + 2 * C, C, ra, res_relu);
+            a = a + b;
+        }
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, a), lean_window(y, q, P, ldy, C, ppw), ly, 0, kLeanNt);
+    };
+    // two slots, each requested one step before it is finished: the wait in front of a slot's arithmetic leaves the other slot's
+    // loads in flight (the order of the requests is what the compiler's counted waits are derived from)
+    static_assert(kLeanWords == 2, "the loop below names its two slots");
+    request(0, pb);
+    for (; pb < P; pb += 2 * pstep) {
+        request(1, pb + pstep);
+        finish(0, pb);
+        request(0, pb + 2 * pstep);
+        finish(1, pb + pstep);
+    }
+}
+
 // Reduce per-workgroup partials [nwg][2C] to BatchNorm (scale, shift) [C][2] and update the running statistics
 // (train mode: biased variance normalises, unbiased variance feeds running_var).  One workgroup per channel.
 __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ stats, int nwg, int C, double count,
@@ -712,6 +795,31 @@ extern "C" int nrgbd_nhwc_act(const float* x, const float* x_ss, int x_relu, con
     const long total = P * (C >> 2);
     hipLaunchKernelGGL(nhwc_act_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, x_ss,
                        x_relu, res, res_ss, res_relu, y, P, C, ldy);
+    NRGBD_CHECK_LAUNCH();
+    return NRGBD_OK;
+}
+
+extern "C" int nrgbd_nhwc_act_lean(const float* x, const float* x_ss, int x_relu, const float* res, const float* res_ss,
+                                   int res_relu, float* y, long P, int C, int ldy, int wg_per_cu, void* stream) {
+    using namespace nrgbd;
+    if (!x || !y) return NRGBD_E_NULL;
+    if (P <= 0 || P > (1L << 30) || C < 4 || C > 1024 || (C & 3) || 256 % (C >> 2) || ldy < C || (ldy & 3) || ldy > (1 << 22))
+        return NRGBD_E_SHAPE;
+    if (wg_per_cu < 1 || wg_per_cu > 8) return NRGBD_E_ARG;
+    if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)res) & 15) return NRGBD_E_ALIGN;
+    int dev = 0, ncu = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e != hipSuccess) return (int)e;
+    if (ncu <= 0) return NRGBD_E_ARG;
+    const int ppw = 256 / (C >> 2);
+    const long steps = (P + ppw - 1) / ppw, cap = (long)wg_per_cu * ncu;
+    const dim3 grid((unsigned)(steps < cap ? steps : cap));
+    const size_t lds = (size_t)16 * C;
+    if (res) hipLaunchKernelGGL(nhwc_act_lean_kernel<true>, grid, dim3(256), lds, (hipStream_t)stream, x, x_ss, x_relu, res, res_ss,
+                                res_relu, y, (int)P, C, ldy);
+    else hipLaunchKernelGGL(nhwc_act_lean_kernel<false>, grid, dim3(256), lds, (hipStream_t)stream, x, x_ss, x_relu, res, res_ss,
+                            res_relu, y, (int)P, C, ldy);
     NRGBD_CHECK_LAUNCH();
     return NRGBD_OK;
 }

@@ -596,6 +596,10 @@ class KalmanGainNet(_PackedWeightsMixin, nn.Module):
     kernels = {16: ("dw4", "dw", "pc", "direct"), 64: ("dw4", "dw", "pc", "direct")}
     kernels32 = ("dw4", "dw", "pc")     # the first layer of a 7-frame window (22 channels in two 16-channel blocks): conv3d.hip has no 32-input form
     _GENERATIONS = {None: None, "wino_pc": ("pc", "direct"), "direct": ("direct",)}   # forward_channels_last(generation=): tests only
+    # workgroups per CU of the four residual passes' co-resident form (ops.nhwc_act_lean), 0 = the plain pass.  A pipelined DepthStream
+    # that has its device to itself sets it on its model's K-Net while it captures the back half, whose passes then run beside the front
+    # half's 2-D convolutions; everywhere else the plain pass is the faster one
+    lean_passes = 0
     _split_residual = True      # measured (tools/knet_ab.py, NO_SPLIT=1): K-Net 25.37 -> 24.67 ms at config B when introduced, 22.74 -> 22.40 after the shared strips; identical bits
 
     def forward_channels_last(self, vol, generation=None):
@@ -639,7 +643,10 @@ class KalmanGainNet(_PackedWeightsMixin, nn.Module):
                 # issue slots are what bounds the kernel (profiles/r4_wino_design_probe.txt).  res may be a (tensor, scale/shift, relu)
                 # triple: c0 = relu(bn(z1)) is never written on its own (lazy_c0 below), the pass applies it while it adds
                 r, r_ss, r_relu = res if isinstance(res, tuple) else (res, None, False)
-                x = ops.nhwc_act(x, x_ss, x_relu, r, r_ss, r_relu)
+                if self.lean_passes:
+                    x = ops.nhwc_act_lean(x, x_ss, x_relu, r, r_ss, r_relu, wg_per_cu=self.lean_passes)
+                else:
+                    x = ops.nhwc_act(x, x_ss, x_relu, r, r_ss, r_relu)
                 y, ss, _ = run(i, x, None, False)
                 return y, ss, x
             # (1) the kernel

@@ -1339,6 +1339,25 @@ def nhwc_act(x, x_ss=None, x_relu=False, res=None, res_ss=None, res_relu=False, 
     return out
 
 
+def nhwc_act_lean(x, x_ss=None, x_relu=False, res=None, res_ss=None, res_relu=False, out=None, ldy=None, wg_per_cu=1):
+    """nhwc_act with the same bits from the co-resident form of the kernel: wg_per_cu workgroups of four waves per CU (1 = meant
+    to share the CUs with a convolution of another stream; up to 8 when it runs alone).  C a power of two."""
+    x = _need(x, "x")
+    C = x.shape[-1]
+    P = x.numel() // C
+    if res is not None:
+        res = _need(res, "res", x.shape)
+    if out is None:
+        out, ldy = torch.empty_like(x), C
+    elif ldy is None:
+        raise ValueError("nhwc_act_lean: out needs its pixel stride ldy")
+    with torch.cuda.device(x.device):
+        rc = _lib.load().nrgbd_nhwc_act_lean(_p(x), _p(x_ss), int(x_relu), _p(res), _p(res_ss), int(res_relu), _p(out), P, C,
+                                              int(ldy), int(wg_per_cu), _stream(x))
+    _lib.check(rc, "nrgbd_nhwc_act_lean")
+    return out
+
+
 def bn2d_train_act(x, gamma, beta, eps, relu=False, residual=None, inplace=True, want_mean_var=False):
     """Train-mode BatchNorm2d + activation (+ residual) in two HBM passes.  x [N,C,H,W] -> (y, mean_var | None)."""
     x = _need(x, "x")

@@ -22,10 +22,12 @@ same per-frame semantics (KVNET.forward + PREDICT, i.e. exactly `neuralrgbd_amd.
 Config 5 of BASELINE.json (a 300-frame high-resolution stream) is this object in a loop.
 """
 import math
+import weakref
 
 import torch
 
 from . import homography as warp_homo
+from . import nets
 from . import ops
 
 
@@ -35,7 +37,20 @@ def _capture_mode():
     return graph_capture_mode()
 
 
+_PIPELINED = weakref.WeakSet()      # the live DepthStream(pipeline=True) objects: a stream counts its neighbours when it captures
+
+
+def _gpu_index(device):
+    d = torch.device(device)
+    return d.index if d.index is not None else torch.cuda.current_device()
+
+
 class DepthStream:
+    # pipeline=True: workgroups per CU of the K-Net residual passes in the captured back half (ops.nhwc_act_lean; 0 = the plain pass).
+    # Used only by a stream that is the one pipelined stream of its device when it captures: beside further videos a pass can land next
+    # to another video's K-Net convolution or run alone, where the plain pass is the faster one
+    lean_passes = 1
+
     def __init__(self, model, cam_intrinsics, d_candi, t_win_r=2, use_graph=True, device=None, copy_outputs=False,
                  allow_eager_fallback=False, pipeline=False):
         self.model = model
@@ -60,6 +75,8 @@ class DepthStream:
         # pipeline=True: two slots of static inputs + D-Net records, the slot of the frame whose back half is still owed, the
         # second HIP stream and the events that order the halves
         self.pipeline = bool(pipeline)
+        if self.pipeline:
+            _PIPELINED.add(self)
         self._slots = None
         self._pending = None            # slot index of the frame that has been measured but not filtered yet
         self._side = None
@@ -128,8 +145,24 @@ class DepthStream:
             with torch.cuda.graph(gf, capture_error_mode=_capture_mode()):
                 self._front(sl)
             gb = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gb, capture_error_mode=_capture_mode()):
-                self._back(sl, self._bv)
+            # the back half is replayed beside the next frame's front half: its K-Net residual passes go into the graph in their
+            # co-resident form (nets.KalmanGainNet.lean_passes), for this capture only and only without further pipelined videos
+            alone = not any(s is not self and _gpu_index(s.device) == _gpu_index(self.device) for s in _PIPELINED)
+            knets = [m for m in self.model.modules() if isinstance(m, nets.KalmanGainNet)]
+            if not knets:
+                raise RuntimeError("DepthStream(pipeline=True): the model has no nets.KalmanGainNet to capture a back half of")
+            kept = [m.__dict__.get("lean_passes") for m in knets]       # what the caller set on the instance, if anything
+            for m in knets:
+                m.lean_passes = self.lean_passes if alone else 0
+            try:
+                with torch.cuda.graph(gb, capture_error_mode=_capture_mode()):
+                    self._back(sl, self._bv)
+            finally:
+                for m, k in zip(knets, kept):
+                    if k is None:
+                        del m.lean_passes
+                    else:
+                        m.lean_passes = k
             sl["gf"], sl["gb"] = gf, gb
         self._consts = warp_homo.cache_snapshot()
         self._graph = True            # "the graphs are active" (reported by the callers through `_graph is not None`)
