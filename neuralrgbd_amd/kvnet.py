@@ -181,7 +181,7 @@ class KVNET(nn.Module):
         return {"BV_cur": BV_cur, "features": features, "texels": self.d_net.texels, "rgb4": self.d_net.rgb4}
 
     def forward(self, ref_frame, src_frames, src_cam_poses, BatchIdx, cam_intrinsics=None,
-                BV_predict=None, mGPU=False, IntMs=None, unit_ray_Ms_2D=None, dpv_valid=None, measured=None):
+                BV_predict=None, mGPU=False, IntMs=None, unit_ray_Ms_2D=None, dpv_valid=None, measured=None, knet_lean_passes=None):
         """
         ref_frame [1,3,H,W], src_frames [1,V,3,H,W], src_cam_poses [1,V,4,4], BatchIdx [1],
         cam_intrinsics: list of dicts, BV_predict [1,D,h,w] or None.
@@ -192,6 +192,7 @@ class KVNET(nn.Module):
         `dpv_valid` (extension): host-side validity of BV_predict; None = probe the tensor like
         the reference's valid_dpv (one device->host read).
         `measured` (extension): the record of `measure()` for this window — the D-Net is then not run again.
+        `knet_lean_passes` (extension): KalmanGainNet.forward_channels_last(lean_passes=) of this call; None = the K-Net's attribute.
         """
         has_pred = isinstance(BV_predict, torch.Tensor)
         if has_pred and dpv_valid is None:
@@ -253,7 +254,7 @@ class KVNET(nn.Module):
         if fused:   # inference: hand-written MFMA conv3d stack on the channels-last volume
             volume = ops.warp_volume(*warp_args, bv_cur=BV_cur[0], bv_pred=BV_predict[0],
                                      align_corners=self.d_net.align_corners, channels_last=True, pad_channels=C_pad)
-            gain = self.kv_net.forward_channels_last(volume)                # [D,h,w]
+            gain = self.kv_net.forward_channels_last(volume, lean_passes=knet_lean_passes)      # [D,h,w]
             DPV = ops.logsoftmax_d(gain, BV_predict[0]).unsqueeze(0)        # UPDATE
         else:       # autograd path (training): the warped RGB is constant, BV_cur - BV_predict carries the gradient
             warped = ops.warp_volume(*warp_args, align_corners=self.d_net.align_corners)   # [3V+3,D,h,w]

@@ -597,12 +597,12 @@ class KalmanGainNet(_PackedWeightsMixin, nn.Module):
     kernels32 = ("dw4", "dw", "pc")     # the first layer of a 7-frame window (22 channels in two 16-channel blocks): conv3d.hip has no 32-input form
     _GENERATIONS = {None: None, "wino_pc": ("pc", "direct"), "direct": ("direct",)}   # forward_channels_last(generation=): tests only
     # workgroups per CU of the four residual passes' co-resident form (ops.nhwc_act_lean), 0 = the plain pass.  A pipelined DepthStream
-    # that has its device to itself sets it on its model's K-Net while it captures the back half, whose passes then run beside the front
-    # half's 2-D convolutions; everywhere else the plain pass is the faster one
+    # that has its device to itself passes 1 (forward_channels_last(lean_passes=)) while it captures the back half, whose passes then run
+    # beside the front half's 2-D convolutions; everywhere else the plain pass is the faster one
     lean_passes = 0
     _split_residual = True      # measured (tools/knet_ab.py, NO_SPLIT=1): K-Net 25.37 -> 24.67 ms at config B when introduced, 22.74 -> 22.40 after the shared strips; identical bits
 
-    def forward_channels_last(self, vol, generation=None):
+    def forward_channels_last(self, vol, generation=None, lean_passes=None):
         """Inference on the hand-written kernels: vol [D,H,W,Cp] (channels-last; Cp = padded_channels(in_channels), zeros in
         channels in_channels .. Cp-1) -> gain [D,H,W].
 
@@ -614,8 +614,11 @@ class KalmanGainNet(_PackedWeightsMixin, nn.Module):
         The 3x3x3 layers run on the first of wino_dw4.hip (D % 4 == 0), wino_dw.hip (D even) — both where the grid is whole 8x16
         tiles: every configuration of the path —, wino_pc.hip and conv3d.hip (direct) that takes the grid (ops.conv3d_kernel).
         generation: None = that choice; "wino_pc" / "direct" = start the choice at that kernel (tests compare the kernels on
-        the whole stack; nothing in the package passes it)."""
+        the whole stack; nothing in the package passes it).
+        lean_passes: None = the attribute; else the workgroups per CU of the residual passes for this call (0 = the plain pass)."""
         from . import ops
+        if lean_passes is None:
+            lean_passes = self.lean_passes
         if self.if_normalize or self.up_sample_ratio is not None:
             raise NotImplementedError("if_normalize / up_sample_ratio are never enabled by the reference scripts")
         if generation not in self._GENERATIONS:
@@ -643,8 +646,8 @@ class KalmanGainNet(_PackedWeightsMixin, nn.Module):
                 # issue slots are what bounds the kernel (profiles/r4_wino_design_probe.txt).  res may be a (tensor, scale/shift, relu)
                 # triple: c0 = relu(bn(z1)) is never written on its own (lazy_c0 below), the pass applies it while it adds
                 r, r_ss, r_relu = res if isinstance(res, tuple) else (res, None, False)
-                if self.lean_passes:
-                    x = ops.nhwc_act_lean(x, x_ss, x_relu, r, r_ss, r_relu, wg_per_cu=self.lean_passes)
+                if lean_passes:
+                    x = ops.nhwc_act_lean(x, x_ss, x_relu, r, r_ss, r_relu, wg_per_cu=lean_passes)
                 else:
                     x = ops.nhwc_act(x, x_ss, x_relu, r, r_ss, r_relu)
                 y, ss, _ = run(i, x, None, False)
