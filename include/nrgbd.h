@@ -67,7 +67,7 @@ extern "C" {
  * indexed triangle mesh), and for the colour entries nrgbd_tsdf_integrate_color_f32, nrgbd_tsdf_extract_points_color,
  * nrgbd_tsdf_extract_mesh_color and nrgbd_tsdf_raycast_color_f32 (the frames' colour fused into the volume), and for the tracking
  * entries nrgbd_icp_workgroups, nrgbd_icp_workspace, nrgbd_icp_terms_f32 and nrgbd_icp_update (a depth frame registered against the
- * fused volume). */
+ * fused volume), and for nrgbd_icp_terms_photo_f32 (the same with a photometric term against the volume's rendered colour). */
 #define NRGBD_INTERFACE_VERSION "0.10"
 const char* nrgbd_version(void);
 const char* nrgbd_strerror(int code);
@@ -1174,7 +1174,8 @@ int nrgbd_tsdf_raycast_color_f32(const float* tsdf, const float* weight, const f
  *     int32  flag     0, or the NRGBD_ICP_* reason the iteration stopped for (sticky)
  *     int32  iterations   the steps that updated T since step 0
  * partial: nwg = nrgbd_icp_workgroups(Hs, Ws) records of NRGBD_ICP_RECORD_BYTES (240): double[28] = A_ij for i <= j in row-major
- *   order (A_00, A_01 .. A_05, A_11 ..: 21), g_0 .. g_5, E; then an int64 count; then 8 bytes of padding (written as 0).
+ *   order (A_00, A_01 .. A_05, A_11 ..: 21), g_0 .. g_5, E; then an int64 count; then 8 bytes of padding (written as 0;
+ *   nrgbd_icp_terms_photo_f32 writes its int64 count of photometric pairs there).
  *
  * nrgbd_icp_workgroups — no counterpart in the reference: min(ceil(Hs Ws / 256), NRGBD_ICP_MAX_WG); a fixed cap, larger maps are
  *   covered by a grid-stride loop.  NRGBD_E_SHAPE: Hs or Ws <= 0 or > 32768.  Needs no GPU.
@@ -1217,6 +1218,43 @@ int nrgbd_tsdf_raycast_color_f32(const float* tsdf, const float* weight, const f
  *                finite, cx, cy, cxm or cym not finite, dist_thr or huber <= 0 or not finite, d_near < d_far not true (a NaN bound
  *                included), a NaN gate_thr beside a gate;  NRGBD_E_ALIGN: state or partial not 8-byte aligned.  Checked in this
  *                order, before anything touches the device.
+ * nrgbd_icp_terms_photo_f32 — no counterpart in the reference: nrgbd_icp_terms_f32 with one photometric (intensity) residual more per
+ *   pair, added to the same normal equations: a single plane leaves point-to-plane ICP blind to the two in-plane translations and
+ *   the rotation about the normal; the surface's texture pins them.  The arguments of nrgbd_icp_terms_f32, and
+ *   image        device fp32 [3][H][W]: the frame's picture at the depth map's size
+ *   aff_a aff_b  HOST float [3] each: a pixel's colour is image * a + b per channel, as nrgbd_tsdf_integrate_color_f32 takes it
+ *   mrgb         device fp32 [3][Hm][Wm]: the model's colour, what nrgbd_tsdf_raycast_color_f32 writes beside mdepth and mnormal
+ *   photo_weight the weight of a photometric term beside a geometric one (whose weight is at most 1), > 0 and finite
+ *   photo_huber  intensity residuals beyond it are down-weighted, > 0 and finite
+ *   per visited pixel, fp32: the sequence of nrgbd_icp_terms_f32 unchanged — resid, the geometric sums and count have that entry's
+ *   bits.  Then, for a pixel that was not skipped, with its q, u, v and dm (model pixel n covers [n, n + 1): its centre is at n + 0.5):
+ *     c_k = image[k][y][x] * a_k + b_k;  Lf = (0.299f * c_0 + 0.587f * c_1) + 0.114f * c_2         (the visited pixel itself)
+ *     ub = u - 0.5f;  vb = v - 0.5f;  x0 = floorf(ub);  y0 = floorf(vb)
+ *     skip the photometric term unless x0 >= 0 && x0 + 1 <= (float)(Wm - 1) && y0 >= 0 && y0 + 1 <= (float)(Hm - 1)
+ *     the four neighbours (y0, x0), (y0, x0 + 1), (y0 + 1, x0), (y0 + 1, x0 + 1), called 00, 10, 01, 11: skip unless each
+ *       mdepth_n > 0 and fabsf(mdepth_n - dm) <= dist_thr (a NaN fails: a neighbour on another surface is not interpolated with)
+ *     L_n = (0.299f * mrgb[0]_n + 0.587f * mrgb[1]_n) + 0.114f * mrgb[2]_n;  skip unless Lf and the four L_n are finite
+ *     fu = ub - x0;  fv = vb - y0;  gu0 = L10 - L00;  gu1 = L11 - L01
+ *     Im = (1 - fv) * (L00 + fu * gu0) + fv * (L01 + fu * gu1)                                     (the bilinear interpolant)
+ *     gu = (1 - fv) * gu0 + fv * gu1;  gv = (1 - fu) * (L01 - L00) + fu * (L11 - L10)              (its gradient, per model pixel)
+ *     ri = Im - Lf
+ *     xq = q_x / q_z;  yq = q_y / q_z                                                              (the quotients u and v were formed from)
+ *     a_x = (gu * fxm) / q_z;  a_y = (gv * fym) / q_z;  a_z = -(a_x * xq + a_y * yq)                (a = d Im / d q)
+ *     ci = q x a:  ci_x = q_y * a_z - q_z * a_y;  ci_y = q_z * a_x - q_x * a_z;  ci_z = q_x * a_y - q_y * a_x
+ *     Ji = (a_x, a_y, a_z, ci_x, ci_y, ci_z)       (d ri / d(v, omega) of the same left perturbation as J)
+ *     wi = fabsf(ri) <= photo_huber ? photo_weight : photo_weight * (photo_huber / fabsf(ri))
+ *   and for a pixel whose photometric term was not skipped, in double from the promoted values, after the pixel's geometric adds and
+ *   into the same 28 sums:
+ *     A_ij += (double)wi * ((double)Ji_i * (double)Ji_j)   (i <= j);   g_i += (double)wi * ((double)Ji_i * (double)ri);
+ *     E += (double)wi * ((double)ri * (double)ri);   photo_count += 1
+ *   count stays the geometric pair count; the record's last word (padding, 0, from nrgbd_icp_terms_f32) holds the int64
+ *   photo_count, folded like count.  nrgbd_icp_update reads the 28 sums and count alone: it neither reads that word nor changes.
+ *   resid        as nrgbd_icp_terms_f32 writes it
+ *   resid_photo  device fp32 [H][W] or NULL: ri at the pixels with a photometric term, a quiet NaN at every other pixel of the map
+ *                (the pixels that are not visited included)
+ *   errors       those of nrgbd_icp_terms_f32 in its order, each class with the new arguments:  NRGBD_E_NULL: also image, mrgb, aff_a
+ *                or aff_b NULL;  NRGBD_E_ARG: also (after that entry's own) photo_weight or photo_huber <= 0 or not finite, an entry of
+ *                aff_a or aff_b not finite.  Before anything touches the device.
  * nrgbd_icp_update — no counterpart in the reference: the solve and the pose update, one workgroup, one launch.
  *   init         HOST double [12] or NULL (= the identity), read at the call when step == 0
  *   step == 0:   T = init; Tf = (float)T (rounded once); flag = 0; iterations = 0.  partial and log are not touched (may be NULL).
@@ -1265,6 +1303,12 @@ int nrgbd_icp_terms_f32(const float* depth, const float* gate, float gate_thr, i
                         float fx, float fy, float cx, float cy, int sub, const float* mdepth, const float* mnormal, int Hm,
                         int Wm, float fxm, float fym, float cxm, float cym, const void* state, float dist_thr, float huber,
                         void* partial, long partial_bytes, float* resid, void* stream);
+int nrgbd_icp_terms_photo_f32(const float* depth, const float* gate, float gate_thr, int H, int W, float d_near, float d_far,
+                              float fx, float fy, float cx, float cy, int sub, const float* mdepth, const float* mnormal, int Hm,
+                              int Wm, float fxm, float fym, float cxm, float cym, const void* state, float dist_thr, float huber,
+                              void* partial, long partial_bytes, float* resid, const float* image, const float* aff_a,
+                              const float* aff_b, const float* mrgb, float photo_weight, float photo_huber, float* resid_photo,
+                              void* stream);
 int nrgbd_icp_update(void* state, const double* init, int step, const void* partial, int nwg, long long min_pairs,
                      double min_pivot, double* log, void* stream);
 

@@ -267,19 +267,21 @@ class TSDFVolume:
         return ops.tsdf_raycast(self.tsdf, self.weight, self.origin, self.voxel_size, m, intrinsics, (H, W), depth_range, w_min=w_min,
                                 step=step, normals=normals, out=out, color=planes, rgb=bool(color))
 
-    def track(self, depth, extM_guess, intrinsics, levels=None, **kw):
+    def track(self, depth, extM_guess, intrinsics, levels=None, image=None, **kw):
         """The pose of a depth frame registered against the volume, from a guess: tracking.FrameTracker(self, depth's size,
-        intrinsics, levels).track(depth, extM_guess, **kw), the tracker built once per (size, intrinsics, levels) and kept — the
-        second call with a size allocates nothing.  Returns a tracking.TrackResult (extM, ok, flag, log, delta).  Synchronises once,
-        at the end."""
+        intrinsics, levels, photo).track(depth, extM_guess, image=image, **kw) with photo = an image was given; the tracker is built
+        once per (size, intrinsics, levels, photo) and kept — the second call with a size allocates nothing.  image=[3,H,W] (a colour
+        volume): the frame's picture, for the photometric term (image_affine, photo_weight, photo_huber go with it in kw).  Returns a
+        tracking.TrackResult (extM, ok, flag, log, delta).  Synchronises once, at the end."""
         from .tracking import DEFAULT_LEVELS, FrameTracker
         levels = DEFAULT_LEVELS if levels is None else tuple((int(s), int(n)) for s, n in levels)
         size = tuple(int(n) for n in depth.shape[-2:])
         K = intrinsics_at(intrinsics, *size) if isinstance(intrinsics, dict) else tuple(float(k) for k in intrinsics)
-        key = (size, K, levels)
+        photo = image is not None
+        key = (size, K, levels, photo)
         if key not in self._trackers:
-            self._trackers[key] = FrameTracker(self, size, intrinsics, levels)
-        return self._trackers[key].track(depth, extM_guess, **kw)
+            self._trackers[key] = FrameTracker(self, size, intrinsics, levels, photo=photo)
+        return self._trackers[key].track(depth, extM_guess, image=image, **kw)
 
 
 def to_uint8(rgb):
@@ -319,10 +321,13 @@ class FusionVideoStream(VideoDepthStream):
     at the tracked pose; where the track is lost it is integrated at the guess and `n_track_lost` counts it.  `last_ext` is the pose
     that was integrated (what render() uses), `tracked_poses` keeps (ref_index, extM, ok).  A tracked push synchronises once per depth
     frame (the tracker reads its result back).  The network's own cost volume keeps using the pushed poses: tracking touches only
-    where the map is integrated.  With track=False nothing of this is constructed or launched."""
+    where the map is integrated.  With track=False nothing of this is constructed or launched.
+    photo=True (with color=True, track=True and source='refined': the depth map is then the ring picture's size): the track also
+    carries the photometric term (FrameTracker(photo=True)) — the picture is the reference frame's ring slot and the affine
+    (std, mean), what the colour integration already uses.  With photo=False nothing of this is constructed or launched."""
 
     def __init__(self, model, cam_intrinsics, d_candi, volume, t_win_r=2, source="refined", conf_threshold=0., weight="uniform",
-                 depth_range=None, color=False, track=False, track_kwargs=None, **video_kwargs):
+                 depth_range=None, color=False, track=False, track_kwargs=None, photo=False, **video_kwargs):
         from .nets import require_volume_refiner
         require_volume_refiner(model, "FusionVideoStream")
         if source not in ("refined", "dpv"):
@@ -349,6 +354,10 @@ class FusionVideoStream(VideoDepthStream):
         if track_kwargs is not None and not self.track:
             raise ValueError("FusionVideoStream: track_kwargs come with track=True")
         self.track_kwargs = dict(track_kwargs or {})
+        self.photo = bool(photo)
+        if self.photo and not (self.color and self.track and source == "refined"):
+            raise ValueError("FusionVideoStream: photo=True needs color=True, track=True and source='refined' (the depth map at the "
+                             "ring picture's size)")
         self.n_track_lost = 0
         self.tracked_poses = []
         self._prev = None                                       # (pushed extrinsic, integrated pose) of the last frame integrated
@@ -410,8 +419,9 @@ class FusionVideoStream(VideoDepthStream):
         pose = self._ext[slot]
         if self.track and self._prev is not None:
             guess = pose @ np.linalg.solve(self._prev[0], self._prev[1])       # E_i E_prev^-1 T_prev, float64 on the host
+            photo = dict(image=self.ring[ref_index % self.R], image_affine=(self.std, self.mean)) if self.photo else {}
             res = self.volume.track(depth, guess, self.cam, gate=gate, gate_thr=self.gate_thr, depth_range=self.depth_range,
-                                    **self.track_kwargs)
+                                    **photo, **self.track_kwargs)
             self.n_track_lost += 0 if res.ok else 1
             self.tracked_poses.append((ref_index, res.extM, res.ok))
             pose = res.extM                                     # lost: the guess (as the ray casts used it, float32-rounded)

@@ -2004,6 +2004,36 @@ def _icp_words(t, name, words, dev, who):
     return t
 
 
+def _icp_terms_args(who, depth, intrinsics, sub, mdepth, mnormal, model_intrinsics, state, partial, gate, resid, image=None, mrgb=None,
+                    resid_photo=None, photo=False):
+    """The checks icp_terms and icp_terms_photo share -> (dev, H, W, Hm, Wm, k, km, sub)."""
+    depth = _need(depth, "depth", strided=True)
+    if depth.dim() != 2:
+        raise ValueError("%s: depth must be [H,W], got %s" % (who, tuple(depth.shape),))
+    dev = depth.device
+    H, W = depth.shape
+    mdepth = _need(mdepth, "mdepth", strided=True)
+    if mdepth.dim() != 2:
+        raise ValueError("%s: mdepth must be [Hm,Wm], got %s" % (who, tuple(mdepth.shape),))
+    Hm, Wm = mdepth.shape
+    maps = [(depth, "depth", (H, W)), (gate, "gate", (H, W)), (resid, "resid", (H, W)), (mdepth, "mdepth", (Hm, Wm)),
+            (mnormal, "mnormal", (3, Hm, Wm))]
+    if photo:
+        maps += [(image, "image", (3, H, W)), (mrgb, "mrgb", (3, Hm, Wm)), (resid_photo, "resid_photo", (H, W))]
+    for t, nm, shape in maps:
+        if t is None and nm in ("gate", "resid", "resid_photo"):
+            continue
+        t = _need(t, nm, shape, strided=True)
+        if t.device != dev or not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous and on %s" % (who, nm, dev))
+    k, km = tuple(float(x) for x in intrinsics), tuple(float(x) for x in model_intrinsics)
+    if len(k) != 4 or len(km) != 4:
+        raise ValueError("%s: intrinsics = (fx, fy, cx, cy)" % who)
+    _icp_words(state, "state", ICP_STATE_WORDS, dev, who)
+    _icp_words(partial, "partial", 0, dev, who)
+    return dev, H, W, Hm, Wm, k, km, int(sub)
+
+
 def icp_terms(depth, intrinsics, sub, mdepth, mnormal, model_intrinsics, state, partial, dist_thr, huber, depth_range=(0.0, float("inf")),
               gate=None, gate_thr=0.0, resid=None):
     """Association, point-to-plane residuals and the partial normal equations of one Gauss-Newton iteration, one launch
@@ -2012,34 +2042,44 @@ def icp_terms(depth, intrinsics, sub, mdepth, mnormal, model_intrinsics, state, 
     is visited; mdepth [Hm,Wm] / mnormal [3,Hm,Wm]: the model maps of tsdf_raycast with model_intrinsics at their size; state: float64
     [ICP_STATE_WORDS] (icp_update's); partial: float64, at least icp_workspace(H // sub, W // sub) bytes; depth_range = (d_near,
     d_far].  Returns the number of records written.  Nothing is allocated, nothing synchronised."""
-    depth = _need(depth, "depth", strided=True)
-    if depth.dim() != 2:
-        raise ValueError("icp_terms: depth must be [H,W], got %s" % (tuple(depth.shape),))
-    dev = depth.device
-    H, W = depth.shape
-    mdepth = _need(mdepth, "mdepth", strided=True)
-    if mdepth.dim() != 2:
-        raise ValueError("icp_terms: mdepth must be [Hm,Wm], got %s" % (tuple(mdepth.shape),))
-    Hm, Wm = mdepth.shape
-    for t, nm, shape in ((depth, "depth", (H, W)), (gate, "gate", (H, W)), (resid, "resid", (H, W)), (mdepth, "mdepth", (Hm, Wm)),
-                         (mnormal, "mnormal", (3, Hm, Wm))):
-        if t is None and nm in ("gate", "resid"):
-            continue
-        t = _need(t, nm, shape, strided=True)
-        if t.device != dev or not t.is_contiguous():
-            raise ValueError("icp_terms: %s must be contiguous and on %s" % (nm, dev))
-    k, km = tuple(float(x) for x in intrinsics), tuple(float(x) for x in model_intrinsics)
-    if len(k) != 4 or len(km) != 4:
-        raise ValueError("icp_terms: intrinsics = (fx, fy, cx, cy)")
-    sub = int(sub)
-    state = _icp_words(state, "state", ICP_STATE_WORDS, dev, "icp_terms")
-    partial = _icp_words(partial, "partial", 0, dev, "icp_terms")
+    dev, H, W, Hm, Wm, k, km, sub = _icp_terms_args("icp_terms", depth, intrinsics, sub, mdepth, mnormal, model_intrinsics, state, partial,
+                                                    gate, resid)
     with torch.cuda.device(dev):
         rc = _lib.load().nrgbd_icp_terms_f32(_p(depth), _p(gate), float(gate_thr), H, W, float(depth_range[0]), float(depth_range[1]),
                                              k[0], k[1], k[2], k[3], sub, _p(mdepth), _p(mnormal), Hm, Wm, km[0], km[1], km[2], km[3],
                                              _p(state), float(dist_thr), float(huber), _p(partial), partial.numel() * 8, _p(resid),
                                              _stream(depth))
     _lib.check(rc, "nrgbd_icp_terms_f32")
+    return icp_workgroups(H // sub, W // sub)
+
+
+def icp_terms_photo(depth, intrinsics, sub, mdepth, mnormal, model_intrinsics, state, partial, dist_thr, huber, image, mrgb,
+                    photo_weight, photo_huber, image_affine=None, depth_range=(0.0, float("inf")), gate=None, gate_thr=0.0, resid=None,
+                    resid_photo=None):
+    """icp_terms with one photometric residual more per pair, added to the same normal equations, one launch
+    (nrgbd_icp_terms_photo_f32; the operation sequence is written out in include/nrgbd.h): the frame's luminance at the visited pixel
+    against the model's, interpolated bilinearly in mrgb where the point projects.  image: contiguous CUDA fp32 [3,H,W], the frame's
+    picture at the depth map's size; image_affine = (a [3], b [3]): a pixel's colour is image * a + b per channel (None: a = 1,
+    b = 0), as tsdf_integrate_color takes it; mrgb [3,Hm,Wm]: the rgb of tsdf_raycast beside mdepth and mnormal; photo_weight: a
+    photometric term's weight beside a geometric one's; photo_huber: intensity residuals beyond it are down-weighted; resid_photo
+    (or None): [H,W].  Everything else, and the result, as icp_terms: resid, the geometric pair count and nrgbd_icp_update's reading
+    of the record are unchanged; the record's last word holds the count of photometric pairs.  Nothing is allocated on the device,
+    nothing synchronised."""
+    dev, H, W, Hm, Wm, k, km, sub = _icp_terms_args("icp_terms_photo", depth, intrinsics, sub, mdepth, mnormal, model_intrinsics, state,
+                                                    partial, gate, resid, image, mrgb, resid_photo, photo=True)
+    if image_affine is None:
+        image_affine = ((1.0, 1.0, 1.0), (0.0, 0.0, 0.0))
+    affine = np.ascontiguousarray(np.concatenate([np.asarray(v, dtype=np.float32).reshape(-1) for v in image_affine]))
+    if affine.shape != (6,):
+        raise ValueError("icp_terms_photo: image_affine = (a [3], b [3])")
+    with torch.cuda.device(dev):
+        rc = _lib.load().nrgbd_icp_terms_photo_f32(_p(depth), _p(gate), float(gate_thr), H, W, float(depth_range[0]), float(depth_range[1]),
+                                                   k[0], k[1], k[2], k[3], sub, _p(mdepth), _p(mnormal), Hm, Wm, km[0], km[1], km[2],
+                                                   km[3], _p(state), float(dist_thr), float(huber), _p(partial), partial.numel() * 8,
+                                                   _p(resid), _p(image), ctypes.c_void_p(affine.ctypes.data),
+                                                   ctypes.c_void_p(affine.ctypes.data + 12), _p(mrgb), float(photo_weight),
+                                                   float(photo_huber), _p(resid_photo), _stream(depth))
+    _lib.check(rc, "nrgbd_icp_terms_photo_f32")
     return icp_workgroups(H // sub, W // sub)
 
 

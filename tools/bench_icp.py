@@ -4,6 +4,7 @@ on a 256^3 volume with a 768 x 1024 map (config B's image, the size of its refin
 grid, the size of source='dpv').
 
     python tools/bench_icp.py [--reps 50] [--warmup 5] [--repeats 3] [--json out.json]
+    python tools/bench_icp.py --photo ...                       # also the photometric track (colour ICP) beside the geometric one
     python tools/bench_icp.py --trace-only --size 768x1024     # 20 track() calls for `rocprofv3 --kernel-trace --stats -- python ...`
     python tools/bench_icp.py --stats <kernel_stats.csv> [...]  # such a run's kernel time and launches per track()
 
@@ -12,7 +13,9 @@ cube of 256^3 voxels, trunc = 3 voxels; the frame is the volume's own ray cast f
 off.  Timing: HIP events around `reps` back-to-back calls after `warmup` untimed ones, per call, the median of `repeats` such
 measurements and their spread; track() ends with a device-to-host copy, so its event time is also its wall time (printed beside
 it); the calls of one entry timed back to back give its call period (launch included), the kernels' own durations come from the
-kernel trace (--trace-only).  There is no other implementation to compare with: the numbers say where a tracked frame's time goes."""
+kernel trace (--trace-only).  --photo: the volume also carries a texture (tests/icp_photo_ref.texture, sheared along z), the frame's
+picture is its own colour ray cast, and every level's colour ray cast, icp_terms_photo and a whole track(image=...) are timed
+beside the geometric ones, in total and per icp_terms_photo launch.  There is no other implementation to compare with: the numbers say where a tracked frame's time goes."""
 import argparse
 import csv
 import json
@@ -53,14 +56,19 @@ def measure(fn, a):
     return {"ms": t, "median_ms": float(np.median(t)), "spread_ms": max(t) - min(t)}
 
 
-def scene():
+def scene(photo=False):
     import icp_ref as ir
     vs = EXTENT / N
     origin = (-1.2, -1.2, 0.0)
     field = ir.corner_field((N, N, N), origin, vs, 3 * vs, ir.CORNER["planes"])
-    vol = fusion.TSDFVolume((N, N, N), vs, origin, device=DEV)
+    vol = fusion.TSDFVolume((N, N, N), vs, origin, device=DEV, color=photo)
     vol.tsdf.copy_(torch.from_numpy(field[0]))
     vol.weight.copy_(torch.from_numpy(field[1]))
+    if photo:                                                       # plane by plane: the host never holds 3 x 256^3 float64
+        import icp_photo_ref as pr
+        x, y, z = pr.lattice((N, N, N), origin, vs)
+        for k in range(N):
+            vol.color[:, k].copy_(torch.from_numpy(pr.texture(x[0] + z[k], y[0] + z[k]).astype(np.float32)))
     truth, guess = ir.corner_poses()
     return vol, truth, guess, ir
 
@@ -83,6 +91,7 @@ def main():
     ap.add_argument("--trace-only", action="store_true")
     ap.add_argument("--size", choices=sorted(SIZES), default="768x1024")
     ap.add_argument("--stats", nargs="*", default=None)
+    ap.add_argument("--photo", action="store_true")
     a = ap.parse_args()
     if a.stats is not None:
         for path in a.stats:
@@ -91,13 +100,14 @@ def main():
             for name, (us, calls) in sorted(per.items(), key=lambda kv: -kv[1][0])[:8]:
                 print("    %8.2f us  %6.1f x  (%.2f us each)  %s" % (us, calls, us / max(calls, 1e-9), name[:90]))
         return 0
-    vol, truth, guess, ir = scene()
+    vol, truth, guess, ir = scene(a.photo)
     if a.trace_only:                                                # the scene's two launches (upload, frame) are in the trace as well
         H, W = SIZES[a.size]
         K = (0.9375 * W, 0.9375 * W, W / 2.0, H / 2.0)
-        depth = vol.raycast(truth, K, (H, W))
+        depth, picture = vol.raycast(truth, K, (H, W), color=True) if a.photo else (vol.raycast(truth, K, (H, W)), None)
+        kw = dict(image=picture) if a.photo else {}
         for _ in range(TRACE_CALLS):
-            vol.track(depth, guess, K)
+            vol.track(depth, guess, K, **kw)
         torch.cuda.synchronize()
         return 0
     out = {"version": ops.version(), "volume": N, "levels": tracking.DEFAULT_LEVELS}
@@ -136,6 +146,27 @@ def main():
         res["track"]["sum_of_parts_ms"] = parts
         print("%s: track() %.4f ms per call (spread %.4f; wall %.4f ms; its launches timed alone add up to %.4f ms)"
               % (name, res["track"]["median_ms"], res["track"]["spread_ms"], res["track"]["wall_ms"], parts))
+        if a.photo:
+            picture = vol.raycast(truth, K, (H, W), color=True)[1]
+            ptracker = tracking.FrameTracker(vol, (H, W), K, photo=True)
+            r = vol.track(depth, guess, K, image=picture)
+            e1 = ir.pose_error(r.extM, truth)
+            res["photo_track_result"] = {"ok": r.ok, "end_m_rad": e1}
+            print("%s: photometric track ok=%s, -> %.3g m / %.3g rad" % (name, r.ok, e1[0], e1[1]))
+            ops.icp_update(ptracker._state, 0)
+            for sub, iters, (Hs, Ws), Kl, maps in ptracker._levels:
+                cast = lambda: vol.raycast(guess, Kl, (Hs, Ws), normals=True, out=maps, color=True)
+                res["raycast_color_sub%d" % sub] = measure(cast, a)
+                terms = lambda: ops.icp_terms_photo(depth, ptracker.K, sub, maps[0], maps[1], Kl, ptracker._state, ptracker._partial,
+                                                    2 * vol.trunc, vol.voxel_size, picture, maps[2], 0.1, 0.1)
+                res["terms_photo_sub%d" % sub] = dict(measure(terms, a), visited=Hs * Ws)
+                print("%s sub %d: colour raycast %.4f ms (depth and normals alone %.4f), icp_terms_photo %.4f ms (icp_terms %.4f); spreads "
+                      "%.4f / %.4f" % (name, sub, res["raycast_color_sub%d" % sub]["median_ms"], res["raycast_sub%d" % sub]["median_ms"],
+                                       res["terms_photo_sub%d" % sub]["median_ms"], res["terms_sub%d" % sub]["median_ms"],
+                                       res["raycast_color_sub%d" % sub]["spread_ms"], res["terms_photo_sub%d" % sub]["spread_ms"]))
+            res["photo_track"] = measure(lambda: vol.track(depth, guess, K, image=picture), a)
+            print("%s: track(image=) %.4f ms per call (spread %.4f) against %.4f ms geometric"
+                  % (name, res["photo_track"]["median_ms"], res["photo_track"]["spread_ms"], res["track"]["median_ms"]))
         out[name] = res
     if a.json:
         with open(a.json, "w") as fh:
