@@ -67,7 +67,9 @@ extern "C" {
  * indexed triangle mesh), and for the colour entries nrgbd_tsdf_integrate_color_f32, nrgbd_tsdf_extract_points_color,
  * nrgbd_tsdf_extract_mesh_color and nrgbd_tsdf_raycast_color_f32 (the frames' colour fused into the volume), and for the tracking
  * entries nrgbd_icp_workgroups, nrgbd_icp_workspace, nrgbd_icp_terms_f32 and nrgbd_icp_update (a depth frame registered against the
- * fused volume), and for nrgbd_icp_terms_photo_f32 (the same with a photometric term against the volume's rendered colour). */
+ * fused volume), and for nrgbd_icp_terms_photo_f32 (the same with a photometric term against the volume's rendered colour), and for
+ * nrgbd_tsdf_reintegrate_f32 and nrgbd_tsdf_reintegrate_color_f32 (a fused frame taken out of the volume and put back at a corrected
+ * pose). */
 #define NRGBD_INTERFACE_VERSION "0.10"
 const char* nrgbd_version(void);
 const char* nrgbd_strerror(int code);
@@ -1094,6 +1096,39 @@ int nrgbd_dgf_refine_f32(const float* depth_lr, int n, int h, int w, const float
  *                lerp(C011, C111, fx), fy), fz) (the corners are requested only where the test passed).  A miss is (0, 0, 0).  The
  *                colour does not depend on the gradient being non-zero.  depth and normal keep their bits; normal may be NULL.
  *   errors       those of nrgbd_tsdf_raycast_f32 in its order;  NRGBD_E_NULL also: color or rgb NULL.
+ * nrgbd_tsdf_reintegrate_f32 — no counterpart in the reference (tsdf_reint.hip): a frame that was integrated is taken out of the volume
+ *   again (pose_add NULL), or taken out at pose_remove and put back at pose_add in the same launch — what a pose correction needs
+ *   (BundleFusion's re-integration).  One launch, capturable.  Every argument that nrgbd_tsdf_integrate_f32 has means what it means
+ *   there; the caller passes the maps the frame was integrated with.
+ *   pose_remove  HOST fp32 [12], read at the call: the pose the frame was integrated with
+ *   pose_add     HOST fp32 [12], read at the call, or NULL: the removal alone
+ *   w_floor      >= 0: a voxel whose weight does not stay above it after the removal is fresh again.  A parameter, not a measurement:
+ *                it absorbs the rounding residue of the weight maps' sums (1e-3 is the Python default)
+ *   per voxel of the box, removal: the chain of nrgbd_tsdf_integrate_f32 with pose_remove unchanged up to t, w — the same skips, the
+ *   same pixel, the same bits —, and for a voxel that passes, with T, Wt its stored values:
+ *     Wn = Wt - w
+ *     Wn > w_floor not true (a NaN Wn included):   T' = 0;  W' = 0                                  (the voxel is fresh again)
+ *     else:   T' = fminf(1, fmaxf(-1, (T * Wt - t * w) / Wn));  W' = Wn
+ *   With unit weights the sums are exact integers and removing a voxel's only observation gives exactly (0, 0).  The removal inverts
+ *   the integration only while Wt never reached w_max: on a saturated voxel the formula is applied to the clamped weight, and what
+ *   comes out is not what the other observations alone would have given (undoing the saturation would take a second weight plane).
+ *   pose_add given: then, on the values the removal left (in registers: every plane is loaded once and stored once), the unchanged
+ *   update of nrgbd_tsdf_integrate_f32 with pose_add: T' = (T * Wt + t * w) / (Wt + w); W' = fminf(Wt + w, w_max).  Voxels are
+ *   independent, so the result is bit for bit that of the removal launch followed by nrgbd_tsdf_integrate_f32.
+ *   A voxel that neither pose updates keeps its bits; a lane group without an update is neither loaded nor stored.  Four x-neighbours
+ *   per lane with 16-byte accesses when X % 4 == 0 and the planes are 16-byte aligned, one voxel per lane otherwise: the same bits.
+ *   errors       those of nrgbd_tsdf_integrate_f32 in its order (NRGBD_E_NULL: tsdf, weight, depth or pose_remove NULL — without a
+ *                pose to remove the call is nrgbd_tsdf_integrate_f32), then NRGBD_E_ARG: w_floor negative or not finite.  Before
+ *                anything touches the device.
+ * nrgbd_tsdf_reintegrate_color_f32 — no counterpart in the reference: the same on a colour volume, with the color, image, colour
+ *   intrinsics and affine arguments of nrgbd_tsdf_integrate_color_f32 (the picture the frame was integrated with).  For a voxel the
+ *   removal passes, with c_j the colour nrgbd_tsdf_integrate_color_f32 forms for it and C_j, Wt the stored values:
+ *     Wn > w_floor not true:        C_j' = 0                                                            (j = r, g, b)
+ *     else, c_r c_g c_b all finite: C_j' = (C_j * Wt - c_j * w) / Wn        with the stored Wt, the Wn of T'
+ *     else:                         the three colour values keep their bits (the integration left them alone as well)
+ *   and the addition is nrgbd_tsdf_integrate_color_f32's.  When X % 4 != 0 or a plane is not 16-byte aligned, remove-and-add runs as
+ *   two launches (the removal, then the integration's own kernel): the same bits.
+ *   errors       those of nrgbd_tsdf_integrate_color_f32 in its order (pose_remove in pose's place), then NRGBD_E_ARG: w_floor.
  * nrgbd_tsdf_mesh_workspace — no counterpart in the reference: the bytes nrgbd_tsdf_extract_mesh needs for an X Y Z grid (24 per
  *   NRGBD_TSDF_EXTRACT_VOXELS voxels and 4 per voxel; needs no GPU); NRGBD_E_SHAPE: a dimension <= 0, 3 X Y Z > 2^31 - 1.
  * nrgbd_tsdf_extract_mesh — no counterpart in the reference: the volume's surface as an indexed triangle mesh (tsdf_mesh.hip), four
@@ -1158,6 +1193,16 @@ int nrgbd_tsdf_raycast_color_f32(const float* tsdf, const float* weight, const f
                                  float oy, float oz, float voxel_size, const float* pose, const float* centre, float fx,
                                  float fy, float cx, float cy, int H, int W, float d_near, float d_far, float w_min, float step,
                                  float* depth, float* normal, float* rgb, void* stream);
+int nrgbd_tsdf_reintegrate_f32(float* tsdf, float* weight, int X, int Y, int Z, float ox, float oy, float oz, float voxel_size,
+                               const float* depth, const float* gate, const float* wmap, const float* pose_remove,
+                               const float* pose_add, int H, int W, float fx, float fy, float cx, float cy, float trunc,
+                               float d_near, float d_far, float w_max, float w_floor, float gate_thr, const int* box, void* stream);
+int nrgbd_tsdf_reintegrate_color_f32(float* tsdf, float* weight, float* color, int X, int Y, int Z, float ox, float oy, float oz,
+                                     float voxel_size, const float* depth, const float* gate, const float* wmap,
+                                     const float* pose_remove, const float* pose_add, int H, int W, float fx, float fy, float cx,
+                                     float cy, float trunc, float d_near, float d_far, float w_max, float w_floor, float gate_thr,
+                                     const int* box, const float* image, int Hc, int Wc, float fxc, float fyc, float cxc,
+                                     float cyc, const float* affine, void* stream);
 /*
  * Frame-to-model tracking (icp.hip; neuralrgbd_amd/tracking.py: FrameTracker; fusion.py: TSDFVolume.track, FusionVideoStream(track=
  * True)): a depth frame registered against the maps nrgbd_tsdf_raycast_f32 writes, by point-to-plane ICP with projective data

@@ -154,6 +154,10 @@ SIGNATURES = {
     "nrgbd_tsdf_extract_points_color": (_I, [_P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _F, _P, _L, _P, _P, _L, _P, _P]),
     "nrgbd_tsdf_extract_mesh_color": (_I, [_P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _F, _P, _L, _P, _P, _L, _P, _L, _P, _P]),
     "nrgbd_tsdf_raycast_color_f32": (_I, [_P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P, _P, _F, _F, _F, _F, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P]),
+    "nrgbd_tsdf_reintegrate_f32": (_I, [_P, _P, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F,
+                                        _P, _P]),
+    "nrgbd_tsdf_reintegrate_color_f32": (_I, [_P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F,
+                                              _F, _F, _P, _P, _I, _I, _F, _F, _F, _F, _P, _P]),
     "nrgbd_icp_workgroups": (_I, [_I, _I]),
     "nrgbd_icp_workspace": (_L, [_I, _I]),
     "nrgbd_icp_terms_f32": (_I, [_P, _P, _F, _I, _I, _F, _F, _F, _F, _F, _F, _I, _P, _P, _I, _I, _F, _F, _F, _F, _P, _F, _F, _P, _L, _P,

@@ -35,106 +35,9 @@
 //                             below the capacity: ascending (linear voxel index, axis) order, nothing behind the written rows.
 // The crossing predicate, a lane's four voxels, the point writer and the scan live in tsdf_extract.hpp: tsdf_mesh.hip (the triangle
 // mesh, whose vertices are these points) runs the same device code.
-#include "tsdf_extract.hpp"      // the crossings, the lane's four voxels, the scan: shared with tsdf_mesh.hip
+#include "tsdf_integrate.hpp"    // the frame, the chain up to (t, w), the colour pixel, the averages, the checks: shared with tsdf_reint.hip
 
 namespace nrgbd {
-
-struct TsdfFrame {
-    float r[12];                        // float32(extM[:3,:4]) row-major: r00 r01 r02 tx | r10 r11 r12 ty | r20 r21 r22 tz
-    float ox, oy, oz, vs;
-    float fx, fy, cx, cy;
-    float trunc, d_near, d_far, w_max, gate_thr;
-    int X, Y, H, W;
-    int x0, y0, z0, x1, y1, z1;         // half-open voxel box
-};
-
-// What does not depend on x: the lattice row's contribution to the three camera coordinates.
-struct TsdfRow {
-    float bx, cx, by, cy, bz, cz;       // r01 yw, r02 zw | r11 yw, r12 zw | r21 yw, r22 zw
-};
-
-__device__ __forceinline__ TsdfRow tsdf_row(const TsdfFrame& f, int iy, int iz) {
-    const float yw = f.oy + f.vs * (float)iy;
-    const float zw = f.oz + f.vs * (float)iz;
-    TsdfRow r;
-    r.bx = f.r[1] * yw; r.cx = f.r[2] * zw;
-    r.by = f.r[5] * yw; r.cy = f.r[6] * zw;
-    r.bz = f.r[9] * yw; r.cz = f.r[10] * zw;
-    return r;
-}
-
-// The colour image of nrgbd_tsdf_integrate_color_f32: its size and intrinsics, the affine c = image * a + b per channel.
-struct TsdfImage {
-    float fx, fy, cx, cy;
-    float a[3], b[3];
-    int H, W;
-    size_t volume;                      // X Y Z: the distance between two colour planes
-};
-
-// The chain of include/nrgbd.h up to t and w for lattice column ix of a row; false: the voxel is skipped.  COLOR: the two quotients of
-// the projection as well (xq = xc / zc, yq = yc / zc: the colour image is projected with the same ones).
-template <bool COLOR>
-__device__ __forceinline__ bool tsdf_observe(const TsdfFrame& f, const TsdfRow& row, int ix, const float* __restrict__ depth,
-                                             const float* __restrict__ gate, const float* __restrict__ wmap, float& t, float& w,
-                                             float& xq, float& yq) {
-    const float xw = f.ox + f.vs * (float)ix;
-    const float xc = ((f.r[0] * xw + row.bx) + row.cx) + f.r[3];
-    const float yc = ((f.r[4] * xw + row.by) + row.cy) + f.r[7];
-    const float zc = ((f.r[8] * xw + row.bz) + row.cz) + f.r[11];
-    if (!(zc > 0.f)) return false;
-    const float xz = xc / zc, yz = yc / zc;
-    const float u = f.fx * xz + f.cx;
-    const float v = f.fy * yz + f.cy;
-    if (COLOR) {
-        xq = xz;
-        yq = yz;
-    }
-    if (!(u >= 0.f && u < (float)f.W && v >= 0.f && v < (float)f.H)) return false;       // a NaN fails
-    const int iu = (int)floorf(u), iv = (int)floorf(v);                                  // 0 <= iu < W, 0 <= iv < H
-    const size_t p = (size_t)iv * (size_t)f.W + (size_t)iu;
-    const float d = depth[p];
-    if (!(fabsf(d) <= kFltMax && d > f.d_near && d <= f.d_far)) return false;
-    if (gate && !(gate[p] >= f.gate_thr)) return false;
-    w = wmap ? wmap[p] : 1.f;
-    if (!(w <= kFltMax && w > 0.f)) return false;
-    const float s = d - zc;
-    if (s < -f.trunc) return false;
-    t = fminf(1.f, s / f.trunc);
-    return true;
-}
-
-__device__ __forceinline__ void tsdf_average(float& T, float& Wt, float t, float w, float w_max) {
-    T = (T * Wt + t * w) / (Wt + w);
-    Wt = fminf(Wt + w, w_max);
-}
-
-// The pixel of the colour image a voxel sees (clamped into the image: colour never vetoes a distance update), through the affine.
-// false: one of the three values is not finite and the voxel's colour keeps its bits.
-__device__ __forceinline__ bool tsdf_colour(const TsdfImage& m, const float* __restrict__ image, float xq, float yq, float (&c)[3]) {
-    float uc = m.fx * xq + m.cx;
-    float vc = m.fy * yq + m.cy;
-    uc = fminf(fmaxf(uc, 0.f), (float)(m.W - 1));
-    vc = fminf(fmaxf(vc, 0.f), (float)(m.H - 1));
-    const int icu = (int)floorf(uc), icv = (int)floorf(vc);
-    const size_t plane = (size_t)m.H * (size_t)m.W;
-    const float* px = image + ((size_t)icv * (size_t)m.W + (size_t)icu);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) c[j] = px[j * plane] * m.a[j] + m.b[j];
-    return fabsf(c[0]) <= kFltMax && fabsf(c[1]) <= kFltMax && fabsf(c[2]) <= kFltMax;                // a NaN fails
-}
-
-// C' = (C * Wt + c * w) / (Wt + w) with the OLD Wt: the denominator of T'
-__device__ __forceinline__ float tsdf_blend(float C, float Wt, float c, float w) { return (C * Wt + c * w) / (Wt + w); }
-
-// The coloured form's further kernel arguments; the colourless form has none (an empty pack: the kernel it was before colour).
-struct TsdfColour {
-    float* color;                       // [3][Z][Y][X]
-    const float* image;                 // [3][Hc][Wc]
-    TsdfImage m;
-};
-
-__device__ __forceinline__ TsdfColour tsdf_colour_args() { return TsdfColour(); }
-__device__ __forceinline__ const TsdfColour& tsdf_colour_args(const TsdfColour& k) { return k; }
 
 // block (64, 4): threadIdx.x walks x (groups of four voxels, or voxels), threadIdx.y rows; blockIdx.y / .z stride over rows and slices
 template <bool VEC, class... Colour>
@@ -244,48 +147,6 @@ __global__ __launch_bounds__(256) void tsdf_scan_kernel(const int* __restrict__ 
                                                         long long capacity, long long* __restrict__ counts) {
     __shared__ long long lds[4];
     tsdf_scan_records(wg_count, wg_offset, nwg, capacity, counts, lds);
-}
-
-}  // namespace nrgbd
-
-namespace nrgbd {
-
-// The checks the two integrations share, in the documented order (m: the colour entry's image, else NULL), and the frame.
-static int tsdf_frame(TsdfFrame& f, int X, int Y, int Z, float ox, float oy, float oz, float voxel_size, int H, int W, const float* pose,
-                      float fx, float fy, float cx, float cy, float trunc, float d_near, float d_far, float w_max, float gate_thr,
-                      const int* box, const TsdfImage* m) {
-    const long n = tsdf_voxels(X, Y, Z);
-    if (n < 0) return (int)n;
-    if (H <= 0 || W <= 0) return NRGBD_E_SHAPE;
-    if (m && (m->H <= 0 || m->W <= 0)) return NRGBD_E_SHAPE;
-    f.x0 = f.y0 = f.z0 = 0;
-    f.x1 = X; f.y1 = Y; f.z1 = Z;
-    if (box) {
-        f.x0 = box[0]; f.y0 = box[1]; f.z0 = box[2];
-        f.x1 = box[3]; f.y1 = box[4]; f.z1 = box[5];
-        if (f.x0 < 0 || f.y0 < 0 || f.z0 < 0 || f.x1 > X || f.y1 > Y || f.z1 > Z) return NRGBD_E_SHAPE;
-        if (f.x0 >= f.x1 || f.y0 >= f.y1 || f.z0 >= f.z1) return NRGBD_E_SHAPE;
-    }
-    if (!tsdf_positive(voxel_size) || !tsdf_positive(trunc) || !tsdf_positive(w_max)) return NRGBD_E_ARG;
-    if (!(d_near < d_far)) return NRGBD_E_ARG;                   // a NaN bound included
-    if (m) {
-        const float k[10] = {m->fx, m->fy, m->cx, m->cy, m->a[0], m->a[1], m->a[2], m->b[0], m->b[1], m->b[2]};
-        for (int i = 0; i < 10; ++i)
-            if (!(fabsf(k[i]) <= kFltMax)) return NRGBD_E_ARG;   // a NaN fails
-    }
-    for (int i = 0; i < 12; ++i) f.r[i] = pose[i];
-    f.ox = ox; f.oy = oy; f.oz = oz; f.vs = voxel_size;
-    f.fx = fx; f.fy = fy; f.cx = cx; f.cy = cy;
-    f.trunc = trunc; f.d_near = d_near; f.d_far = d_far; f.w_max = w_max; f.gate_thr = gate_thr;
-    f.X = X; f.Y = Y; f.H = H; f.W = W;
-    return NRGBD_OK;
-}
-
-static dim3 tsdf_integrate_grid(const TsdfFrame& f, bool vec) {
-    const int units = vec ? (f.x1 + 3) / 4 - f.x0 / 4 : f.x1 - f.x0;
-    const int rows = f.y1 - f.y0, slices = f.z1 - f.z0;
-    return dim3((unsigned)ceil_div(units, 64), (unsigned)(ceil_div(rows, 4) < 65535 ? ceil_div(rows, 4) : 65535),
-                (unsigned)(slices < 65535 ? slices : 65535));
 }
 
 }  // namespace nrgbd

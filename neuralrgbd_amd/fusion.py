@@ -20,6 +20,9 @@ conventions (lattice, projection, update rule, crossings) are written out in inc
   * tracking: `TSDFVolume.track` registers a depth frame against the volume from a pose guess (tracking.FrameTracker: ray casts and
     point-to-plane Gauss-Newton iterations on the device, ops.icp_terms / ops.icp_update), and `FusionVideoStream(track=True)`
     integrates every map at its tracked pose instead of the pushed one;
+  * pose corrections: `TSDFVolume.deintegrate` takes a fused frame out of the volume again and `TSDFVolume.reintegrate` moves it to a
+    corrected pose in one launch (ops.tsdf_reintegrate: BundleFusion's re-integration); `FusionVideoStream(history=N)` keeps the maps
+    of the last N frames for it — `repose`, `retrack`;
   * `fuse_sequence`, `save_ply`.
 """
 import math
@@ -123,6 +126,45 @@ class TSDFVolume:
         """An empty volume again (asynchronous)."""
         self._buf.zero_()
 
+    def _frame(self, who, depth, intrinsics, gate, gate_thr, weight, color, color_intrinsics, color_affine):
+        """What integrate, deintegrate and reintegrate check and prepare alike: -> (depth [H,W], gate, weight, (fx, fy, cx, cy),
+        the colour intrinsics or None)."""
+        who = "TSDFVolume." + who
+        if (color is None) != (self.color is None):
+            raise ValueError("%s: a colour volume is integrated with a colour image (the weight is shared), a volume "
+                             "without colour without one" % who)
+        if color is None and (color_intrinsics is not None or color_affine is not None):
+            raise ValueError("%s: color_intrinsics / color_affine come with color" % who)
+        if color is not None:
+            if not isinstance(color, torch.Tensor) or color.dtype != torch.float32:
+                raise TypeError("%s: color is an fp32 tensor [3,Hc,Wc]" % who)
+            if color.dim() != 3 or color.shape[0] != 3 or color.shape[1] < 1 or color.shape[2] < 1:
+                raise ValueError("%s: color is [3,Hc,Wc], got %s" % (who, tuple(color.shape),))
+            if color.device != self.device or not color.is_contiguous():
+                raise ValueError("%s: color must be contiguous and on %s" % (who, self.device,))
+        if depth.dim() == 3 and depth.shape[0] == 1:
+            depth = depth[0]
+            gate = gate if gate is None else gate.view(depth.shape)
+            weight = weight if weight is None else weight.view(depth.shape)
+        if depth.dim() != 2:
+            raise ValueError("%s: depth is [H,W], got %s" % (who, tuple(depth.shape),))
+        H, W = depth.shape
+        if color is not None and color_intrinsics is None:
+            if isinstance(intrinsics, dict):
+                color_intrinsics = intrinsics_at(intrinsics, color.shape[1], color.shape[2])
+            elif tuple(color.shape[1:]) != (H, W):
+                raise ValueError("%s: a %d x %d colour image beside a %d x %d depth map needs color_intrinsics"
+                                 % (who, color.shape[1], color.shape[2], H, W))
+        if isinstance(color_intrinsics, dict):
+            color_intrinsics = intrinsics_at(color_intrinsics, color.shape[1], color.shape[2])
+        if isinstance(intrinsics, dict):
+            intrinsics = intrinsics_at(intrinsics, H, W)
+        if color is not None and color_intrinsics is None:
+            color_intrinsics = intrinsics
+        if (gate is None) != (gate_thr is None):
+            raise ValueError("%s: gate and gate_thr come together" % who)
+        return depth, gate, weight, intrinsics, color_intrinsics
+
     def integrate(self, depth, extM, intrinsics, gate=None, gate_thr=None, weight=None, depth_range=(0., float("inf")), cull=True,
                   color=None, color_intrinsics=None, color_affine=None):
         """One depth frame: depth [H,W] (or [1,H,W]) CUDA fp32 z-depth in metres; extM: the host [4,4] world -> camera matrix
@@ -134,43 +176,12 @@ class TSDFVolume:
         colour volume refuses a frame without: the shared weight would go out of step with the colour); color_intrinsics:
         (fx, fy, cx, cy) at that size — by default intrinsics_at when `intrinsics` is a dict, or the depth map's when the sizes are
         equal; color_affine = (a [3], b [3]): a pixel's colour is image * a + b per channel (default a = 1, b = 0)."""
-        if (color is None) != (self.color is None):
-            raise ValueError("TSDFVolume.integrate: a colour volume is integrated with a colour image (the weight is shared), a volume "
-                             "without colour without one")
-        if color is None and (color_intrinsics is not None or color_affine is not None):
-            raise ValueError("TSDFVolume.integrate: color_intrinsics / color_affine come with color")
-        if color is not None:
-            if not isinstance(color, torch.Tensor) or color.dtype != torch.float32:
-                raise TypeError("TSDFVolume.integrate: color is an fp32 tensor [3,Hc,Wc]")
-            if color.dim() != 3 or color.shape[0] != 3 or color.shape[1] < 1 or color.shape[2] < 1:
-                raise ValueError("TSDFVolume.integrate: color is [3,Hc,Wc], got %s" % (tuple(color.shape),))
-            if color.device != self.device or not color.is_contiguous():
-                raise ValueError("TSDFVolume.integrate: color must be contiguous and on %s" % (self.device,))
-        if depth.dim() == 3 and depth.shape[0] == 1:
-            depth = depth[0]
-            gate = gate if gate is None else gate.view(depth.shape)
-            weight = weight if weight is None else weight.view(depth.shape)
-        if depth.dim() != 2:
-            raise ValueError("TSDFVolume.integrate: depth is [H,W], got %s" % (tuple(depth.shape),))
-        H, W = depth.shape
-        if color is not None and color_intrinsics is None:
-            if isinstance(intrinsics, dict):
-                color_intrinsics = intrinsics_at(intrinsics, color.shape[1], color.shape[2])
-            elif tuple(color.shape[1:]) != (H, W):
-                raise ValueError("TSDFVolume.integrate: a %d x %d colour image beside a %d x %d depth map needs color_intrinsics"
-                                 % (color.shape[1], color.shape[2], H, W))
-        if isinstance(color_intrinsics, dict):
-            color_intrinsics = intrinsics_at(color_intrinsics, color.shape[1], color.shape[2])
-        if isinstance(intrinsics, dict):
-            intrinsics = intrinsics_at(intrinsics, H, W)
-        if color is not None and color_intrinsics is None:
-            color_intrinsics = intrinsics
-        if (gate is None) != (gate_thr is None):
-            raise ValueError("TSDFVolume.integrate: gate and gate_thr come together")
+        depth, gate, weight, intrinsics, color_intrinsics = self._frame("integrate", depth, intrinsics, gate, gate_thr, weight, color,
+                                                                        color_intrinsics, color_affine)
         m = _host_matrix(extM, "TSDFVolume.integrate")
         box = None
         if cull:
-            box = frustum_box(m, intrinsics, (H, W), float(depth_range[1]) + self.trunc, self)
+            box = frustum_box(m, intrinsics, tuple(depth.shape), float(depth_range[1]) + self.trunc, self)
             if box is None:
                 return False
         if color is not None:
@@ -181,6 +192,48 @@ class TSDFVolume:
         ops.tsdf_integrate(self.tsdf, self.weight, self.origin, self.voxel_size, depth, m, intrinsics, self.trunc, depth_range, self.w_max,
                            gate=gate, gate_thr=0.0 if gate_thr is None else gate_thr, wmap=weight, box=box)
         return True
+
+    def _reintegrate(self, who, depth, extM_old, extM_new, intrinsics, gate, gate_thr, weight, depth_range, cull, color, color_intrinsics,
+                     color_affine, w_floor):
+        depth, gate, weight, intrinsics, color_intrinsics = self._frame(who, depth, intrinsics, gate, gate_thr, weight, color,
+                                                                        color_intrinsics, color_affine)
+        poses = [_host_matrix(m, "TSDFVolume." + who) for m in ((extM_old,) if extM_new is None else (extM_old, extM_new))]
+        box = None
+        if cull:                                                    # the hull of the boxes: culling is conservative, the same bits
+            boxes = [b for b in (frustum_box(m, intrinsics, tuple(depth.shape), float(depth_range[1]) + self.trunc, self) for m in poses)
+                     if b is not None]
+            if not boxes:
+                return False
+            box = tuple(min(b[k] for b in boxes) for k in range(3)) + tuple(max(b[k] for b in boxes) for k in range(3, 6))
+        kw = dict(pose_add=None if extM_new is None else poses[1], w_floor=w_floor, depth_range=depth_range, w_max=self.w_max, gate=gate,
+                  gate_thr=0.0 if gate_thr is None else gate_thr, wmap=weight, box=box)
+        if color is not None:
+            ops.tsdf_reintegrate_color(self.tsdf, self.weight, self.color, self.origin, self.voxel_size, depth, poses[0], intrinsics,
+                                       self.trunc, color, color_intrinsics, color_affine, **kw)
+        else:
+            ops.tsdf_reintegrate(self.tsdf, self.weight, self.origin, self.voxel_size, depth, poses[0], intrinsics, self.trunc, **kw)
+        return True
+
+    def deintegrate(self, depth, extM, intrinsics, gate=None, gate_thr=None, weight=None, depth_range=(0., float("inf")), cull=True,
+                    color=None, color_intrinsics=None, color_affine=None, w_floor=1e-3):
+        """A frame that `integrate` fused taken out of the volume again, one launch (ops.tsdf_reintegrate): the arguments are
+        integrate's — pass what the frame was integrated with — and w_floor >= 0: a voxel whose weight does not stay above it is
+        fresh again (0, 0, and colour 0).  An inverse on voxels whose weight never reached w_max; up to rounding, which a voxel whose
+        only observation this was does not see: it comes out exactly empty.  Returns False when the frustum box is empty and nothing
+        was launched.  Allocates nothing and synchronises nothing."""
+        return self._reintegrate("deintegrate", depth, extM, None, intrinsics, gate, gate_thr, weight, depth_range, cull, color,
+                                 color_intrinsics, color_affine, w_floor)
+
+    def reintegrate(self, depth, extM_old, extM_new, intrinsics, gate=None, gate_thr=None, weight=None, depth_range=(0., float("inf")),
+                    cull=True, color=None, color_intrinsics=None, color_affine=None, w_floor=1e-3):
+        """A fused frame moved from extM_old to extM_new — what a pose correction needs: deintegrate(extM_old) and integrate(extM_new)
+        in ONE launch over the hull of the two frustum boxes, bit for bit what the two calls give, with every plane read and written
+        once.  An empty box leaves the other; returns False when both are empty and nothing was launched.  Allocates nothing and
+        synchronises nothing."""
+        if extM_new is None:
+            raise ValueError("TSDFVolume.reintegrate: extM_new is the pose to put the frame back at (deintegrate takes it out alone)")
+        return self._reintegrate("reintegrate", depth, extM_old, extM_new, intrinsics, gate, gate_thr, weight, depth_range, cull, color,
+                                 color_intrinsics, color_affine, w_floor)
 
     def _need_color(self, who):
         if self.color is None:
@@ -324,10 +377,16 @@ class FusionVideoStream(VideoDepthStream):
     where the map is integrated.  With track=False nothing of this is constructed or launched.
     photo=True (with color=True, track=True and source='refined': the depth map is then the ring picture's size): the track also
     carries the photometric term (FrameTracker(photo=True)) — the picture is the reference frame's ring slot and the affine
-    (std, mean), what the colour integration already uses.  With photo=False nothing of this is constructed or launched."""
+    (std, mean), what the colour integration already uses.  With photo=False nothing of this is constructed or launched.
+    history=N: the stream keeps what the last N integrated frames were integrated with — the regressed depth map, the gate and the
+    weight map where it uses them, with color=True a copy of the picture (the ring's slot is overwritten later), in device slots
+    allocated once and filled by memory copies, and on the host (ref_index, integrated pose): `history_poses()`.  `repose(ref_index,
+    extM)` moves such a frame to a corrected pose (TSDFVolume.reintegrate, one launch) and `retrack(ref_index)` registers it again
+    against the model without it; a frame that falls out of the history stays fused for good; reset() clears it.  With history=0
+    (the default) nothing of this is constructed or launched."""
 
     def __init__(self, model, cam_intrinsics, d_candi, volume, t_win_r=2, source="refined", conf_threshold=0., weight="uniform",
-                 depth_range=None, color=False, track=False, track_kwargs=None, photo=False, **video_kwargs):
+                 depth_range=None, color=False, track=False, track_kwargs=None, photo=False, history=0, **video_kwargs):
         from .nets import require_volume_refiner
         require_volume_refiner(model, "FusionVideoStream")
         if source not in ("refined", "dpv"):
@@ -361,6 +420,12 @@ class FusionVideoStream(VideoDepthStream):
         self.n_track_lost = 0
         self.tracked_poses = []
         self._prev = None                                       # (pushed extrinsic, integrated pose) of the last frame integrated
+        self.history = int(history)
+        if self.history < 0 or self.history != history:
+            raise ValueError("FusionVideoStream: history is a number of frames >= 0, got %r" % (history,))
+        self._held = []                                         # [ref_index, integrated pose, slot], oldest first
+        self._slots = None                                      # the maps of the held frames, allocated at the first one
+        self._n_held = 0
         super().__init__(model, cam_intrinsics, d_candi, t_win_r=t_win_r, **video_kwargs)
         if _indexed(volume.device) != _indexed(self.device):
             raise ValueError("FusionVideoStream: the volume is on %s, the stream on %s" % (volume.device, self.device))
@@ -373,6 +438,7 @@ class FusionVideoStream(VideoDepthStream):
         self.last_ext = None                                    # the extrinsic of the last frame integrated on this trajectory
         self._prev = None
         self.tracked_poses = []
+        self._held = []                                         # the history goes with the trajectory (its slots stay allocated)
 
     def render(self, extM=None, size=None, normals=False, color=False, **kw):
         """The fused model as a depth map (and normals, and with color=True its colours): TSDFVolume.raycast from extM — by default the extrinsic of the last frame
@@ -431,7 +497,81 @@ class FusionVideoStream(VideoDepthStream):
             self.last_ext = pose
             if self.track:
                 self._prev = (np.asarray(self._ext[slot], dtype=np.float64), np.asarray(pose, dtype=np.float64))
+            if self.history:
+                self._hold(ref_index, pose, depth, gate, wmap, kw.get("color"))
         return out
+
+    # ---- the history: what the last `history` frames were integrated with, so that a corrected pose can move them ----------------
+
+    def _hold(self, ref_index, pose, depth, gate, wmap, image):
+        """Copies the frame's maps into the oldest slot (contiguous fp32 device-to-device copies: memory copies, no kernel) and
+        notes its pose; the frame that held the slot stays fused for good."""
+        if self._slots is None:                                 # once: the maps' size is the source's
+            new = lambda t: None if t is None else torch.empty((self.history,) + tuple(t.shape), dtype=torch.float32, device=self.device)
+            self._slots = dict(depth=new(depth), gate=new(gate), wmap=new(wmap), image=new(image))
+        slot = self._n_held % self.history
+        self._n_held += 1
+        for key, t in (("depth", depth), ("gate", gate), ("wmap", wmap), ("image", image)):
+            if t is not None:
+                self._slots[key][slot].copy_(t)
+        self._held = [h for h in self._held if h[2] != slot] + [[ref_index, np.array(pose, dtype=np.float64), slot]]
+
+    def history_poses(self):
+        """[(ref_index, extM)] of the frames the history holds, oldest first: the poses they are integrated at now."""
+        return [(h[0], h[1].copy()) for h in self._held]
+
+    def _held_frame(self, ref_index, who):
+        """The history entry of a frame and what it was integrated with: (entry, depth, keywords of integrate / deintegrate)."""
+        for h in self._held:
+            if h[0] == ref_index:
+                break
+        else:
+            raise KeyError("FusionVideoStream.%s: frame %r is not in the history (history=%d holds %s)"
+                           % (who, ref_index, self.history, [e[0] for e in self._held]))
+        pick = lambda key: None if self._slots[key] is None else self._slots[key][h[2]]
+        kw = dict(gate=pick("gate"), gate_thr=self.gate_thr, weight=pick("wmap"), depth_range=self.depth_range)
+        if self.color:
+            kw.update(color=pick("image"), color_intrinsics=intrinsics_at(self.cam, self.H, self.W), color_affine=(self.std, self.mean))
+        return h, pick("depth"), kw
+
+    def _reposed(self, h, pose):
+        h[1] = np.array(pose, dtype=np.float64)
+        if self._held[-1] is h:                                 # the last frame integrated: tracking goes on from the corrected pose
+            self.last_ext = h[1].copy()
+            if self._prev is not None:
+                self._prev = (self._prev[0], h[1].copy())
+
+    def repose(self, ref_index, extM):
+        """A pose correction for a frame of the history: the frame is taken out of the volume at the pose it was integrated with
+        and put back at extM (host [4,4] world -> camera) in one launch — TSDFVolume.reintegrate with the frame's own maps, the
+        stream's gate, weights, depth range and colour arguments.  The new pose is what the history holds from now on; for the last
+        frame integrated it also becomes `last_ext` and the pose tracking continues from.  KeyError: the frame is not (or no
+        longer) held.  Allocates nothing and synchronises nothing."""
+        h, depth, kw = self._held_frame(ref_index, "repose")
+        new = self._extrinsic(extM)
+        if not np.all(np.isfinite(new)):
+            raise ValueError("FusionVideoStream.repose: the pose is not finite")
+        done = self.volume.reintegrate(depth, h[1], new, self.cam, **kw)
+        self._reposed(h, new)
+        return done
+
+    def retrack(self, ref_index, **track_kwargs):
+        """A held frame registered again, against the model WITHOUT it (track=True): the frame is de-integrated, its depth map is
+        tracked against what remains from its stored pose (with its picture from the history when photo=True; track_kwargs go on
+        top of the stream's), and it is integrated at the tracked pose — or, when the track is lost, back at the stored pose: the
+        volume then differs from before by rounding only.  Returns the tracking.TrackResult; the history's pose is updated as
+        `repose` does.  Synchronises once (the tracker reads its result back)."""
+        if not self.track:
+            raise ValueError("FusionVideoStream.retrack: the stream was built with track=False")
+        h, depth, kw = self._held_frame(ref_index, "retrack")
+        self.volume.deintegrate(depth, h[1], self.cam, **kw)
+        photo = dict(image=kw["color"], image_affine=(self.std, self.mean)) if self.photo else {}
+        res = self.volume.track(depth, h[1], self.cam, gate=kw["gate"], gate_thr=self.gate_thr, depth_range=self.depth_range, **photo,
+                                **dict(self.track_kwargs, **track_kwargs))
+        pose = res.extM if res.ok else h[1]
+        self.volume.integrate(depth, pose, self.cam, **kw)
+        self._reposed(h, pose)
+        return res
 
     def push(self, frame, extM):
         """As VideoDepthStream.push; the maps that come out (of frame ref_index) are integrated before they are returned."""

@@ -1675,6 +1675,18 @@ def _vec3(v, name):
     return v
 
 
+def _tsdf_pose(who, pose):
+    """A host [3,4] or [4,4] world -> camera matrix as the float32 [3,4] the C entries read."""
+    if isinstance(pose, torch.Tensor):
+        if pose.is_cuda:
+            raise ValueError("%s: pose is a host matrix (it is read at the call)" % who)
+        pose = pose.detach().numpy()
+    pose = np.asarray(pose)
+    if pose.shape not in ((3, 4), (4, 4)):
+        raise ValueError("%s: pose is [3,4] or [4,4] world -> camera, got %s" % (who, pose.shape))
+    return np.ascontiguousarray(pose[:3, :4], dtype=np.float32)
+
+
 def _tsdf_frame(who, tsdf, weight, origin, depth, gate, wmap, pose, intrinsics, box):
     """What the two integrations check and prepare alike: -> (tsdf, weight, [depth, gate, wmap], float32 pose [3,4], (fx, fy, cx, cy),
     origin, the box as a C array or None)."""
@@ -1690,14 +1702,7 @@ def _tsdf_frame(who, tsdf, weight, origin, depth, gate, wmap, pose, intrinsics, 
             if t.device != dev or not t.is_contiguous():
                 raise ValueError("%s: %s must be contiguous and on %s" % (who, nm, dev))
         maps.append(t)
-    if isinstance(pose, torch.Tensor):
-        if pose.is_cuda:
-            raise ValueError("%s: pose is a host matrix (it is read at the call)" % who)
-        pose = pose.detach().numpy()
-    pose = np.asarray(pose)
-    if pose.shape not in ((3, 4), (4, 4)):
-        raise ValueError("%s: pose is [3,4] or [4,4] world -> camera, got %s" % (who, pose.shape))
-    pose = np.ascontiguousarray(pose[:3, :4], dtype=np.float32)
+    pose = _tsdf_pose(who, pose)
     k = tuple(float(x) for x in intrinsics)
     if len(k) != 4:
         raise ValueError("%s: intrinsics = (fx, fy, cx, cy)" % who)
@@ -1739,6 +1744,24 @@ def _tsdf_color(color, tsdf, who):
     return color
 
 
+def _tsdf_image(who, image, color_intrinsics, color_affine, dev):
+    """What the coloured integrations check and prepare alike: -> (image, (fxc, fyc, cxc, cyc), the affine as float32 [6])."""
+    image = _need(image, "image", strided=True)
+    if image.dim() != 3 or image.shape[0] != 3 or image.shape[1] < 1 or image.shape[2] < 1:
+        raise ValueError("%s: image must be [3,Hc,Wc], got %s" % (who, tuple(image.shape),))
+    if image.device != dev or not image.is_contiguous():
+        raise ValueError("%s: image must be contiguous and on %s" % (who, dev,))
+    kc = tuple(float(x) for x in color_intrinsics)
+    if len(kc) != 4:
+        raise ValueError("%s: color_intrinsics = (fx, fy, cx, cy)" % who)
+    if color_affine is None:
+        color_affine = ((1.0, 1.0, 1.0), (0.0, 0.0, 0.0))
+    affine = np.ascontiguousarray(np.concatenate([np.asarray(v, dtype=np.float32).reshape(-1) for v in color_affine]))
+    if affine.shape != (6,):
+        raise ValueError("%s: color_affine = (a [3], b [3])" % who)
+    return image, kc, affine
+
+
 def tsdf_integrate_color(tsdf, weight, color, origin, voxel_size, depth, pose, intrinsics, trunc, image, color_intrinsics,
                          color_affine=None, depth_range=(0.0, float("inf")), w_max=64.0, gate=None, gate_thr=0.0, wmap=None, box=None):
     """tsdf_integrate with the frame's colour averaged into the volume's colour planes, one launch (nrgbd_tsdf_integrate_color_f32;
@@ -1750,19 +1773,7 @@ def tsdf_integrate_color(tsdf, weight, color, origin, voxel_size, depth, pose, i
     tsdf, weight, maps, pose, k, o, cbox = _tsdf_frame("tsdf_integrate_color", tsdf, weight, origin, depth, gate, wmap, pose, intrinsics, box)
     color = _tsdf_color(color, tsdf, "tsdf_integrate_color")
     dev = tsdf.device
-    image = _need(image, "image", strided=True)
-    if image.dim() != 3 or image.shape[0] != 3 or image.shape[1] < 1 or image.shape[2] < 1:
-        raise ValueError("tsdf_integrate_color: image must be [3,Hc,Wc], got %s" % (tuple(image.shape),))
-    if image.device != dev or not image.is_contiguous():
-        raise ValueError("tsdf_integrate_color: image must be contiguous and on %s" % (dev,))
-    kc = tuple(float(x) for x in color_intrinsics)
-    if len(kc) != 4:
-        raise ValueError("tsdf_integrate_color: color_intrinsics = (fx, fy, cx, cy)")
-    if color_affine is None:
-        color_affine = ((1.0, 1.0, 1.0), (0.0, 0.0, 0.0))
-    affine = np.ascontiguousarray(np.concatenate([np.asarray(v, dtype=np.float32).reshape(-1) for v in color_affine]))
-    if affine.shape != (6,):
-        raise ValueError("tsdf_integrate_color: color_affine = (a [3], b [3])")
+    image, kc, affine = _tsdf_image("tsdf_integrate_color", image, color_intrinsics, color_affine, dev)
     Z, Y, X = tsdf.shape
     H, W = maps[0].shape
     with torch.cuda.device(dev):
@@ -1773,6 +1784,54 @@ def tsdf_integrate_color(tsdf, weight, color, origin, voxel_size, depth, pose, i
                                                         image.shape[1], image.shape[2], kc[0], kc[1], kc[2], kc[3],
                                                         ctypes.c_void_p(affine.ctypes.data), _stream(tsdf))
     _lib.check(rc, "nrgbd_tsdf_integrate_color_f32")
+
+
+def tsdf_reintegrate(tsdf, weight, origin, voxel_size, depth, pose_remove, intrinsics, trunc, pose_add=None, w_floor=1e-3,
+                     depth_range=(0.0, float("inf")), w_max=64.0, gate=None, gate_thr=0.0, wmap=None, box=None):
+    """A depth frame that tsdf_integrate fused at pose_remove taken out of the volume again and, when pose_add is given, put back at
+    that pose, in place, one launch (nrgbd_tsdf_reintegrate_f32; the operation sequence is written out in include/nrgbd.h).  The
+    arguments are tsdf_integrate's — pass the maps the frame was integrated with —, and w_floor >= 0: a voxel whose weight does not
+    stay above it after the removal is fresh again (0, 0).  With pose_add the result is bit for bit that of the removal followed by
+    tsdf_integrate at pose_add, with every plane read and written once.  The removal inverts the integration on voxels whose
+    weight never reached w_max.  Nothing is allocated, nothing synchronised."""
+    tsdf, weight, maps, pose, k, o, cbox = _tsdf_frame("tsdf_reintegrate", tsdf, weight, origin, depth, gate, wmap, pose_remove, intrinsics,
+                                                       box)
+    add = None if pose_add is None else _tsdf_pose("tsdf_reintegrate", pose_add)
+    dev = tsdf.device
+    Z, Y, X = tsdf.shape
+    H, W = maps[0].shape
+    with torch.cuda.device(dev):
+        rc = _lib.load().nrgbd_tsdf_reintegrate_f32(_p(tsdf), _p(weight), X, Y, Z, o[0], o[1], o[2], float(voxel_size), _p(maps[0]),
+                                                    _p(maps[1]), _p(maps[2]), ctypes.c_void_p(pose.ctypes.data),
+                                                    None if add is None else ctypes.c_void_p(add.ctypes.data), H, W, k[0], k[1], k[2],
+                                                    k[3], float(trunc), float(depth_range[0]), float(depth_range[1]), float(w_max),
+                                                    float(w_floor), float(gate_thr), cbox, _stream(tsdf))
+    _lib.check(rc, "nrgbd_tsdf_reintegrate_f32")
+
+
+def tsdf_reintegrate_color(tsdf, weight, color, origin, voxel_size, depth, pose_remove, intrinsics, trunc, image, color_intrinsics,
+                           color_affine=None, pose_add=None, w_floor=1e-3, depth_range=(0.0, float("inf")), w_max=64.0, gate=None,
+                           gate_thr=0.0, wmap=None, box=None):
+    """tsdf_reintegrate on a colour volume (nrgbd_tsdf_reintegrate_color_f32): the frame's colour leaves the colour planes with its
+    distance — pass the picture, intrinsics and affine it was integrated with — and enters them again at pose_add; an emptied voxel's
+    colour is 0.  The arguments are tsdf_integrate_color's and tsdf_reintegrate's.  Nothing is allocated, nothing synchronised."""
+    who = "tsdf_reintegrate_color"
+    tsdf, weight, maps, pose, k, o, cbox = _tsdf_frame(who, tsdf, weight, origin, depth, gate, wmap, pose_remove, intrinsics, box)
+    add = None if pose_add is None else _tsdf_pose(who, pose_add)
+    color = _tsdf_color(color, tsdf, who)
+    dev = tsdf.device
+    image, kc, affine = _tsdf_image(who, image, color_intrinsics, color_affine, dev)
+    Z, Y, X = tsdf.shape
+    H, W = maps[0].shape
+    with torch.cuda.device(dev):
+        rc = _lib.load().nrgbd_tsdf_reintegrate_color_f32(_p(tsdf), _p(weight), _p(color), X, Y, Z, o[0], o[1], o[2], float(voxel_size),
+                                                          _p(maps[0]), _p(maps[1]), _p(maps[2]), ctypes.c_void_p(pose.ctypes.data),
+                                                          None if add is None else ctypes.c_void_p(add.ctypes.data), H, W, k[0], k[1],
+                                                          k[2], k[3], float(trunc), float(depth_range[0]), float(depth_range[1]),
+                                                          float(w_max), float(w_floor), float(gate_thr), cbox, _p(image), image.shape[1],
+                                                          image.shape[2], kc[0], kc[1], kc[2], kc[3], ctypes.c_void_p(affine.ctypes.data),
+                                                          _stream(tsdf))
+    _lib.check(rc, "nrgbd_tsdf_reintegrate_color_f32")
 
 
 def tsdf_extract_workspace(X, Y, Z):

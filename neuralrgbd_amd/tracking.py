@@ -14,9 +14,11 @@ volume adds a photometric term to the same normal equations (colour ICP): the ra
 pixel that kept its geometric pair compares its own luminance with the model's, interpolated bilinearly where the point projects
 (ops.icp_terms_photo, still two launches per iteration).  Geometry pins the motions it can see, texture the rest.
 
-Deliberately not built: frame normals and a normal-angle gate, relocalisation after a loss, re-integration of the volume after a
-pose correction, an image pyramid with pre-filtering — the coarse levels compare the visited pixel's own value with the point-sampled
-ray cast."""
+A pose this tracker (or anything else) corrects later can be applied to a frame that is already fused: TSDFVolume.reintegrate moves
+the frame in one launch, FusionVideoStream(history=N).repose / retrack do it for the stream's last N frames (fusion.py).
+
+Deliberately not built: frame normals and a normal-angle gate, relocalisation after a loss, an image pyramid with pre-filtering — the
+coarse levels compare the visited pixel's own value with the point-sampled ray cast."""
 import math
 
 import numpy as np
