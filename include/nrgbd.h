@@ -69,7 +69,7 @@ extern "C" {
  * entries nrgbd_icp_workgroups, nrgbd_icp_workspace, nrgbd_icp_terms_f32 and nrgbd_icp_update (a depth frame registered against the
  * fused volume), and for nrgbd_icp_terms_photo_f32 (the same with a photometric term against the volume's rendered colour), and for
  * nrgbd_tsdf_reintegrate_f32 and nrgbd_tsdf_reintegrate_color_f32 (a fused frame taken out of the volume and put back at a corrected
- * pose). */
+ * pose), and for nrgbd_depth_consistency_f32 (a depth map cross-checked against other views' maps before it is fused). */
 #define NRGBD_INTERFACE_VERSION "0.10"
 const char* nrgbd_version(void);
 const char* nrgbd_strerror(int code);
@@ -1356,6 +1356,53 @@ int nrgbd_icp_terms_photo_f32(const float* depth, const float* gate, float gate_
                               void* stream);
 int nrgbd_icp_update(void* state, const double* init, int step, const void* partial, int nwg, long long min_pairs,
                      double min_pivot, double* log, void* stream);
+/*
+ * Multi-view depth consistency (consistency.hip; neuralrgbd_amd/fusion.py: filter_depth, FusionVideoStream(consistency=k)): a depth map
+ * cross-checked against other views' depth maps before it is fused — the geometric filter of the learned multi-view-stereo pipelines.
+ * The network's depth is the expectation of a candidate distribution; at a depth discontinuity it lies between foreground and
+ * background, a flying pixel no other view confirms.  No counterpart in the reference, which stops at the maps; the conventions are
+ * the ones written here.  Everything is fp32; every operation below is ONE IEEE operation in the order written (no fused
+ * multiply-add, no reciprocal, no library function); there are no atomics and no workspace, and the same inputs give the same bits in
+ * every run.  One launch on the caller's stream, capturable.
+ *
+ * nrgbd_depth_consistency_f32 — no counterpart in the reference: per reference pixel the number of source views whose depth map
+ *   agrees with it, and the depth map with the pixels too few views confirm set to 0.
+ *   depth        device fp32 [H][W]: the reference view's z-depth in metres
+ *   gate         device fp32 [H][W] or NULL: a pixel counts where gate >= gate_thr (a NaN fails), as nrgbd_icp_terms_f32 takes it
+ *   d_near d_far a pixel (of the reference and of a source) counts where d is finite, d > d_near and d <= d_far
+ *   fx fy cx cy  the pinhole intrinsics at H x W, the reference's and every source's; pixel x covers [x, x + 1)
+ *   src_depth    device fp32: a stack of [H][W] maps src_stride floats apart (the size and intrinsics of the reference map)
+ *   src_gate     the sources' gates in the same layout; NULL exactly when gate is NULL
+ *   src_slots    HOST int [n_src]: source s is map src_slots[s] of the stack (repeats allowed)
+ *   src_T        HOST fp32 [n_src][12]: (R | t) of source s, [3][4] row-major, reference camera -> source camera s
+ *   n_src        0 .. NRGBD_CONSISTENCY_MAX_SRC; with 0 the source pointers may be NULL and the launch folds the pixel's own tests
+ *   per reference pixel (y, x), fp32:
+ *     d = depth[y][x];  the pixel is valid when d > d_near, d <= d_far and d is finite (a NaN fails each) and, when a gate is given,
+ *     gate[y][x] >= gate_thr.  An invalid pixel: votes = -1, depth_out = 0, and no source is read for it.
+ *     xn = (((float)x + 0.5) - cx) / fx;  yn = (((float)y + 0.5) - cy) / fy;  p = (xn * d, yn * d, d)
+ *     agreeing = 0;  for s = 0 .. n_src - 1 in order:
+ *       q_j = ((R_j0 * p_x + R_j1 * p_y) + R_j2 * p_z) + t_j                    (j = x, y, z: the point in source camera s)
+ *       skip the source unless q_z > 0
+ *       u = fx * (q_x / q_z) + cx;  v = fy * (q_y / q_z) + cy
+ *       skip unless u >= 0 && u < (float)W && v >= 0 && v < (float)H            (a NaN fails)
+ *       iu = (int)floorf(u);  iv = (int)floorf(v);  ds = src_depth[src_slots[s]][iv][iu]      (nearest: no interpolation across an edge)
+ *       skip unless the source pixel is valid: the four tests above on ds and src_gate[src_slots[s]][iv][iu]
+ *       agreeing += 1 when fabsf(ds - q_z) <= rel_thr * q_z                     (a NaN fails)
+ *   votes        device fp32 [H][W] or NULL: (float)agreeing, -1 at an invalid pixel — a gate for nrgbd_tsdf_integrate_f32 or
+ *                nrgbd_icp_terms_f32 (gate_thr = the views asked for)
+ *   depth_out    device fp32 [H][W] or NULL: agreeing >= min_views ? d : 0.  May be `depth` itself (a pixel reads its own value only);
+ *                must not overlap a source map.
+ *   errors       NRGBD_E_NULL: depth NULL; votes and depth_out both NULL; n_src > 0 and src_depth, src_slots or src_T NULL; n_src > 0
+ *                and one of gate, src_gate NULL but not the other;  NRGBD_E_SHAPE: H or W <= 0 or > 32768, n_src < 0 or >
+ *                NRGBD_CONSISTENCY_MAX_SRC, min_views < 0, n_src > 0 and src_stride < H W, a negative slot;  NRGBD_E_ARG: fx or fy <= 0
+ *                or not finite, cx or cy not finite, rel_thr <= 0 or not finite, d_near < d_far not true (a NaN bound included), a
+ *                NaN gate_thr beside a gate, an entry of src_T not finite.  Checked in this order, before anything touches the device.
+ */
+#define NRGBD_CONSISTENCY_MAX_SRC 16
+int nrgbd_depth_consistency_f32(const float* depth, const float* gate, float gate_thr, int H, int W, float d_near, float d_far,
+                                float fx, float fy, float cx, float cy, const float* src_depth, const float* src_gate,
+                                long src_stride, const int* src_slots, const float* src_T, int n_src, float rel_thr,
+                                int min_views, float* votes, float* depth_out, void* stream);
 
 #ifdef __cplusplus
 }

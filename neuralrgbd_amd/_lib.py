@@ -31,6 +31,7 @@ ICP_RECORD_BYTES = 240          # NRGBD_ICP_RECORD_BYTES
 ICP_STATE_BYTES = 152           # NRGBD_ICP_STATE_BYTES
 ICP_FEW, ICP_NONFINITE, ICP_DEGENERATE, ICP_LARGE = 1, 2, 3, 4     # NRGBD_ICP_*: why an iteration stopped
 ICP_MAX_THETA2 = 0.25           # NRGBD_ICP_MAX_THETA2
+CONSISTENCY_MAX_SRC = 16        # NRGBD_CONSISTENCY_MAX_SRC
 
 
 class WindowSlots(ctypes.Structure):
@@ -165,6 +166,7 @@ SIGNATURES = {
     "nrgbd_icp_terms_photo_f32": (_I, [_P, _P, _F, _I, _I, _F, _F, _F, _F, _F, _F, _I, _P, _P, _I, _I, _F, _F, _F, _F, _P, _F, _F, _P, _L,
                                        _P, _P, _P, _P, _P, _F, _F, _P, _P]),
     "nrgbd_icp_update": (_I, [_P, _P, _I, _P, _I, _c.c_longlong, _D, _P, _P]),
+    "nrgbd_depth_consistency_f32": (_I, [_P, _P, _F, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P, _L, _P, _P, _I, _F, _I, _P, _P, _P]),
     "nrgbd_nhwc_stats_workgroups": (_I, [_L]),
     "nrgbd_nhwc_stats": (_I, [_P, _L, _I, _P, _P]),
     "nrgbd_nhwc_act": (_I, [_P, _P, _I, _P, _P, _I, _P, _L, _I, _I, _P]),

@@ -23,6 +23,12 @@ conventions (lattice, projection, update rule, crossings) are written out in inc
   * pose corrections: `TSDFVolume.deintegrate` takes a fused frame out of the volume again and `TSDFVolume.reintegrate` moves it to a
     corrected pose in one launch (ops.tsdf_reintegrate: BundleFusion's re-integration); `FusionVideoStream(history=N)` keeps the maps
     of the last N frames for it — `repose`, `retrack`;
+  * multi-view consistency: `filter_depth` cross-checks a depth map against other views' maps in one launch (ops.depth_consistency:
+    a pixel stays where enough views see the same surface at the same depth) and `FusionVideoStream(history=N, consistency=k)` does
+    it for every frame against the held ones before the frame is tracked and fused: the flying pixels of a depth expectation at a
+    discontinuity never enter the volume.  Not built: deferred two-sided filtering (with the frames that arrive later), a fused
+    depth averaged over the agreeing views, a free-space-violation count, sources of another size or intrinsics, and scoring the
+    filtered set in evaluate.EvalVideoStream;
   * `fuse_sequence`, `save_ply`.
 """
 import math
@@ -354,6 +360,49 @@ def shade(normal):
     return np.rint(np.clip(-np.asarray(normal)[2], 0., 1.) * 255.).astype(np.uint8)
 
 
+def relative_poses(pose, poses):
+    """float32 [n,3,4]: (T_s T_ref^-1)[:3] for every world -> camera pose T_s of `poses`, with T_ref = pose — the motions reference
+    camera -> source camera ops.depth_consistency takes —, formed in float64 on the host and rounded once."""
+    inv = np.linalg.inv(_host4(pose, "relative_poses"))
+    return np.stack([(_host4(m, "relative_poses") @ inv)[:3] for m in poses]).astype(np.float32)
+
+
+def _host4(extM, who):
+    m = _host_matrix(extM, who)
+    return m if m.shape == (4, 4) else np.vstack([m, [0.0, 0.0, 0.0, 1.0]])
+
+
+def filter_depth(depth, pose, sources, poses, intrinsics, rel=0.01, min_views=1, depth_range=(0., float("inf")), gate=None, gate_thr=None,
+                 source_gates=None, votes=None, out=None):
+    """A depth map cross-checked against other views' maps, for a caller with a loop of its own (no TSDFVolume, no stream): one launch
+    (ops.depth_consistency).  depth [H,W] CUDA fp32 at the host world -> camera pose `pose`; sources: the other views' maps at the
+    same size and intrinsics, a CUDA fp32 tensor [S,H,W] (read where it lies) or a sequence of [H,W] maps (stacked here), at most
+    NRGBD_CONSISTENCY_MAX_SRC, with their world -> camera `poses`; intrinsics: (fx, fy, cx, cy) at the maps' size or a
+    cam_intrinsics dict (intrinsics_at); a source agrees with a pixel where |ds - q_z| <= rel q_z (a parameter, not a measurement);
+    gate / gate_thr with source_gates (a stack or a sequence like `sources`): a pixel of either side counts where its gate >=
+    gate_thr; depth_range = (d_near, d_far] alike.  Returns (filtered, votes): the map with every pixel that fails its own tests or
+    that fewer than min_views sources agree with set to 0 — what to hand to TSDFVolume.integrate or track without a gate —, and
+    the agreeing views per pixel (-1: the pixel failed its own tests).  votes / out: tensors to write into (out may be `depth`).
+    Synchronises nothing."""
+    if depth.dim() == 3 and depth.shape[0] == 1:
+        depth = depth[0]
+        gate = gate if gate is None else gate.view(depth.shape)
+    if (gate is None) != (gate_thr is None) or (len(sources) > 0 and (gate is None) != (source_gates is None)):
+        raise ValueError("filter_depth: gate, gate_thr and source_gates come together")
+    stack = lambda maps: maps if isinstance(maps, torch.Tensor) else torch.stack([m.view(depth.shape) for m in maps])
+    src = dict(src_depth=None, src_T=None)
+    if len(sources) > 0:
+        if len(poses) != len(sources):
+            raise ValueError("filter_depth: %d sources with %d poses" % (len(sources), len(poses)))
+        src = dict(src_depth=stack(sources), src_gate=None if source_gates is None else stack(source_gates),
+                   src_T=relative_poses(pose, poses))
+    if isinstance(intrinsics, dict):
+        intrinsics = intrinsics_at(intrinsics, *depth.shape)
+    got = ops.depth_consistency(depth, intrinsics, rel_thr=rel, min_views=min_views, depth_range=depth_range, gate=gate,
+                                gate_thr=0.0 if gate_thr is None else gate_thr, votes=votes, depth_out=out, **src)
+    return got[1], got[0]
+
+
 class FusionVideoStream(VideoDepthStream):
     """VideoDepthStream + a TSDFVolume: push(frame, extM) returns what VideoDepthStream.push returns, and every depth frame that comes
     out is integrated into `volume` with the extrinsic pushed with its reference frame — one depth-regression launch and one
@@ -383,10 +432,25 @@ class FusionVideoStream(VideoDepthStream):
     allocated once and filled by memory copies, and on the host (ref_index, integrated pose): `history_poses()`.  `repose(ref_index,
     extM)` moves such a frame to a corrected pose (TSDFVolume.reintegrate, one launch) and `retrack(ref_index)` registers it again
     against the model without it; a frame that falls out of the history stays fused for good; reset() clears it.  With history=0
-    (the default) nothing of this is constructed or launched."""
+    (the default) nothing of this is constructed or launched.
+    consistency=k >= 1 (needs history >= k): every depth map is cross-checked against the held frames before it is used — one launch
+    (ops.depth_consistency) with the held frames' RAW regressed maps and gates as sources, their transforms float32((T_s T_ref^-1)[:3])
+    formed in float64 on the host from `history_poses()`' current poses (a repose counts) and the pose the frame is about to be
+    integrated or tracked from (track=False: the pushed pose; track=True: the guess), at most the newest NRGBD_CONSISTENCY_MAX_SRC of
+    them, min_views = min(k, sources), the stream's depth_range and gate.  The filtered map — 0 where the pixel fails its own tests
+    or fewer than min_views sources agree — replaces the regressed one for track, integrate and the history's `depth` slot (the slot
+    holds what was integrated: repose and retrack stay exact), and with the gate folded into it they take no gate.  The history holds
+    one more slot tensor, `raw`, and its `gate` slots are the sources' gates: a later frame is checked against what the network
+    regressed, not against what survived, so a newly seen region that was filtered out once can still gain support.  The first frame
+    of a trajectory has no sources and is fused as before; after that a region is fused from the k-th time after its first sighting
+    on: surfaces enter the volume k frames late, the price of never fusing what no other view confirms.  consistency_rel: a source
+    agrees where |ds - q_z| <= consistency_rel q_z; like the tracker's dist_thr a parameter, not a measurement.  `last_votes` is
+    the votes map of the last frame (a buffer the next frame overwrites).  With consistency=0 (the default) nothing of this is
+    constructed or launched, and the stream's launches and bits are what they were."""
 
     def __init__(self, model, cam_intrinsics, d_candi, volume, t_win_r=2, source="refined", conf_threshold=0., weight="uniform",
-                 depth_range=None, color=False, track=False, track_kwargs=None, photo=False, history=0, **video_kwargs):
+                 depth_range=None, color=False, track=False, track_kwargs=None, photo=False, history=0, consistency=0,
+                 consistency_rel=0.01, **video_kwargs):
         from .nets import require_volume_refiner
         require_volume_refiner(model, "FusionVideoStream")
         if source not in ("refined", "dpv"):
@@ -426,6 +490,20 @@ class FusionVideoStream(VideoDepthStream):
         self._held = []                                         # [ref_index, integrated pose, slot], oldest first
         self._slots = None                                      # the maps of the held frames, allocated at the first one
         self._n_held = 0
+        self.consistency = int(consistency)
+        if self.consistency < 0 or self.consistency != consistency:
+            raise ValueError("FusionVideoStream: consistency is a number of views >= 0, got %r" % (consistency,))
+        if self.consistency > self.history:
+            raise ValueError("FusionVideoStream: consistency=%d needs history >= %d (the held frames are the sources), got history=%d"
+                             % (self.consistency, self.consistency, self.history))
+        self.consistency_rel = float(consistency_rel)
+        if not (self.consistency_rel > 0 and math.isfinite(self.consistency_rel)):
+            raise ValueError("FusionVideoStream: consistency_rel must be positive and finite, got %r" % (consistency_rel,))
+        if self.consistency and self.depth_range[0] < 0:
+            raise ValueError("FusionVideoStream: consistency writes 0 for a dropped pixel, which depth_range = %s would fuse"
+                             % (self.depth_range,))
+        self._votes = self._filtered = None                     # the filter's two outputs, allocated at the first frame
+        self.last_votes = None
         super().__init__(model, cam_intrinsics, d_candi, t_win_r=t_win_r, **video_kwargs)
         if _indexed(volume.device) != _indexed(self.device):
             raise ValueError("FusionVideoStream: the volume is on %s, the stream on %s" % (volume.device, self.device))
@@ -439,6 +517,7 @@ class FusionVideoStream(VideoDepthStream):
         self._prev = None
         self.tracked_poses = []
         self._held = []                                         # the history goes with the trajectory (its slots stay allocated)
+        self.last_votes = None
 
     def render(self, extM=None, size=None, normals=False, color=False, **kw):
         """The fused model as a depth map (and normals, and with color=True its colours): TSDFVolume.raycast from extM — by default the extrinsic of the last frame
@@ -483,35 +562,61 @@ class FusionVideoStream(VideoDepthStream):
             kw = dict(color=self.ring[ref_index % self.R], color_intrinsics=intrinsics_at(self.cam, self.H, self.W),
                       color_affine=(self.std, self.mean))
         pose = self._ext[slot]
-        if self.track and self._prev is not None:
-            guess = pose @ np.linalg.solve(self._prev[0], self._prev[1])       # E_i E_prev^-1 T_prev, float64 on the host
+        tracked = self.track and self._prev is not None
+        if tracked:
+            pose = pose @ np.linalg.solve(self._prev[0], self._prev[1])        # the guess E_i E_prev^-1 T_prev, float64 on the host
+        raw, gate_thr = None, self.gate_thr
+        if self.consistency:                                    # the gate is folded into the filtered map
+            raw, raw_gate = depth, gate
+            depth, gate, gate_thr = self._consistent(raw, raw_gate, pose), None, None
+        if tracked:
             photo = dict(image=self.ring[ref_index % self.R], image_affine=(self.std, self.mean)) if self.photo else {}
-            res = self.volume.track(depth, guess, self.cam, gate=gate, gate_thr=self.gate_thr, depth_range=self.depth_range,
+            res = self.volume.track(depth, pose, self.cam, gate=gate, gate_thr=gate_thr, depth_range=self.depth_range,
                                     **photo, **self.track_kwargs)
             self.n_track_lost += 0 if res.ok else 1
             self.tracked_poses.append((ref_index, res.extM, res.ok))
             pose = res.extM                                     # lost: the guess (as the ray casts used it, float32-rounded)
-        if self.volume.integrate(depth, pose, self.cam, gate=gate, gate_thr=self.gate_thr, weight=wmap,
+        if self.volume.integrate(depth, pose, self.cam, gate=gate, gate_thr=gate_thr, weight=wmap,
                                  depth_range=self.depth_range, **kw):
             self.n_integrated += 1
             self.last_ext = pose
             if self.track:
                 self._prev = (np.asarray(self._ext[slot], dtype=np.float64), np.asarray(pose, dtype=np.float64))
             if self.history:
-                self._hold(ref_index, pose, depth, gate, wmap, kw.get("color"))
+                if self.consistency:
+                    self._hold(ref_index, pose, depth, raw_gate, wmap, kw.get("color"), raw)
+                else:
+                    self._hold(ref_index, pose, depth, gate, wmap, kw.get("color"))
         return out
+
+    def _consistent(self, depth, gate, pose):
+        """The regressed map checked against the held frames' raw maps from `pose` (one launch): -> the filtered map, in a buffer
+        the next frame overwrites; `last_votes` beside it."""
+        if self._votes is None:
+            self._votes, self._filtered = torch.empty_like(depth), torch.empty_like(depth)
+        held = self._held[-ops.CONSISTENCY_MAX_SRC:]
+        src = dict(src_depth=None, src_T=None)
+        if held:
+            src = dict(src_depth=self._slots["raw"], src_gate=self._slots["gate"], src_slots=[h[2] for h in held],
+                       src_T=relative_poses(pose, [h[1] for h in held]))
+        ops.depth_consistency(depth, intrinsics_at(self.cam, *depth.shape), rel_thr=self.consistency_rel,
+                              min_views=min(self.consistency, len(held)), depth_range=self.depth_range, gate=gate,
+                              gate_thr=0.0 if self.gate_thr is None else self.gate_thr, votes=self._votes, depth_out=self._filtered, **src)
+        self.last_votes = self._votes
+        return self._filtered
 
     # ---- the history: what the last `history` frames were integrated with, so that a corrected pose can move them ----------------
 
-    def _hold(self, ref_index, pose, depth, gate, wmap, image):
+    def _hold(self, ref_index, pose, depth, gate, wmap, image, raw=None):
         """Copies the frame's maps into the oldest slot (contiguous fp32 device-to-device copies: memory copies, no kernel) and
-        notes its pose; the frame that held the slot stays fused for good."""
+        notes its pose; the frame that held the slot stays fused for good.  raw (consistency > 0): the regressed map before the
+        filter, with `gate` its gate — what later frames are checked against; `depth` is then the filtered map that was integrated."""
         if self._slots is None:                                 # once: the maps' size is the source's
             new = lambda t: None if t is None else torch.empty((self.history,) + tuple(t.shape), dtype=torch.float32, device=self.device)
-            self._slots = dict(depth=new(depth), gate=new(gate), wmap=new(wmap), image=new(image))
+            self._slots = dict(depth=new(depth), gate=new(gate), wmap=new(wmap), image=new(image), raw=new(raw))
         slot = self._n_held % self.history
         self._n_held += 1
-        for key, t in (("depth", depth), ("gate", gate), ("wmap", wmap), ("image", image)):
+        for key, t in (("depth", depth), ("gate", gate), ("wmap", wmap), ("image", image), ("raw", raw)):
             if t is not None:
                 self._slots[key][slot].copy_(t)
         self._held = [h for h in self._held if h[2] != slot] + [[ref_index, np.array(pose, dtype=np.float64), slot]]
@@ -530,6 +635,8 @@ class FusionVideoStream(VideoDepthStream):
                            % (who, ref_index, self.history, [e[0] for e in self._held]))
         pick = lambda key: None if self._slots[key] is None else self._slots[key][h[2]]
         kw = dict(gate=pick("gate"), gate_thr=self.gate_thr, weight=pick("wmap"), depth_range=self.depth_range)
+        if self.consistency:                                    # the held map carries its gate; the gate slot is the raw map's
+            kw.update(gate=None, gate_thr=None)
         if self.color:
             kw.update(color=pick("image"), color_intrinsics=intrinsics_at(self.cam, self.H, self.W), color_affine=(self.std, self.mean))
         return h, pick("depth"), kw
@@ -566,7 +673,7 @@ class FusionVideoStream(VideoDepthStream):
         h, depth, kw = self._held_frame(ref_index, "retrack")
         self.volume.deintegrate(depth, h[1], self.cam, **kw)
         photo = dict(image=kw["color"], image_affine=(self.std, self.mean)) if self.photo else {}
-        res = self.volume.track(depth, h[1], self.cam, gate=kw["gate"], gate_thr=self.gate_thr, depth_range=self.depth_range, **photo,
+        res = self.volume.track(depth, h[1], self.cam, gate=kw["gate"], gate_thr=kw["gate_thr"], depth_range=self.depth_range, **photo,
                                 **dict(self.track_kwargs, **track_kwargs))
         pose = res.extM if res.ok else h[1]
         self.volume.integrate(depth, pose, self.cam, **kw)

@@ -2163,3 +2163,85 @@ def icp_update(state, step, partial=None, nwg=0, min_pairs=6, min_pivot=1e-6, lo
         rc = _lib.load().nrgbd_icp_update(_p(state), cinit, step, _p(partial if step > 0 else None), int(nwg), int(min_pairs),
                                           float(min_pivot), _p(log if step > 0 else None), _stream(state))
     _lib.check(rc, "nrgbd_icp_update")
+
+
+# ---- multi-view depth consistency (consistency.hip; neuralrgbd_amd/fusion.py) -------------------------------------------------------
+
+CONSISTENCY_MAX_SRC = _lib.CONSISTENCY_MAX_SRC
+
+
+def depth_consistency(depth, intrinsics, src_depth, src_T, rel_thr, min_views, depth_range=(0.0, float("inf")), gate=None, gate_thr=0.0,
+                      src_gate=None, src_slots=None, votes=None, depth_out=None):
+    """A depth map cross-checked against other views' maps, one launch (nrgbd_depth_consistency_f32; the per-pixel operation sequence
+    is written out in include/nrgbd.h): every valid pixel is lifted, moved into each source camera, projected, and compared with the
+    source's depth at the nearest pixel; a source agrees where |ds - q_z| <= rel_thr q_z.
+    depth (and gate, or None): contiguous CUDA fp32 [H,W]; intrinsics = (fx, fy, cx, cy) at H x W, the sources' too; src_depth (and
+    src_gate, given exactly when gate is): CUDA fp32 [S,H,W], the maps contiguous and any stride >= H W between them (None: no
+    sources); src_slots: which map of the stack each source is (default 0 .. S-1; repeats allowed); src_T: host [n,3,4] or [n,4,4],
+    reference camera -> source camera, one per entry of src_slots, rounded to fp32 once; depth_range = (d_near, d_far]: what a pixel
+    of either map needs to count; min_views: the agreeing sources a pixel needs to stay.
+    votes / depth_out: a tensor [H,W] to write into, None: allocated here, False: not produced.  Returns (votes, depth_out) with
+    None for what was not produced: votes = the agreeing sources per pixel as fp32, -1 at an invalid pixel; depth_out = depth where
+    votes >= min_views, else 0; depth_out may be `depth` itself.  Nothing else is allocated, nothing synchronised."""
+    who = "depth_consistency"
+    depth = _need(depth, "depth", strided=True)
+    if depth.dim() != 2:
+        raise ValueError("%s: depth must be [H,W], got %s" % (who, tuple(depth.shape),))
+    dev = depth.device
+    H, W = depth.shape
+    if votes is False and depth_out is False:
+        raise ValueError("%s: neither votes nor depth_out is asked for" % who)
+    for t, nm in ((depth, "depth"), (gate, "gate"), (votes, "votes"), (depth_out, "depth_out")):
+        if t is None or t is False:
+            continue
+        t = _need(t, nm, (H, W), strided=True)
+        if t.device != dev or not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous and on %s" % (who, nm, dev))
+    k = tuple(float(x) for x in intrinsics)
+    if len(k) != 4:
+        raise ValueError("%s: intrinsics = (fx, fy, cx, cy)" % who)
+    n_src, stride, slots, cT = 0, 0, None, None
+    if src_depth is None:
+        if src_gate is not None or src_slots:
+            raise ValueError("%s: src_gate and src_slots come with src_depth" % who)
+    else:
+        if (gate is None) != (src_gate is None):
+            raise ValueError("%s: gate and src_gate come together" % who)
+        src_depth = _need(src_depth, "src_depth", strided=True)
+        if src_depth.dim() != 3 or tuple(src_depth.shape[1:]) != (H, W):
+            raise ValueError("%s: src_depth must be [S,%d,%d], got %s" % (who, H, W, tuple(src_depth.shape),))
+        S = src_depth.shape[0]
+        stride = src_depth.stride(0) if S > 1 else H * W
+        for t, nm in ((src_depth, "src_depth"), (src_gate, "src_gate")):
+            if t is None:
+                continue
+            t = _need(t, nm, (S, H, W), strided=True)
+            if t.device != dev or not t[0].is_contiguous() or (S > 1 and (t.stride(0) != stride or stride < H * W)):
+                raise ValueError("%s: %s must hold contiguous maps, the same stride >= H W apart, on %s" % (who, nm, dev))
+        slots = list(range(S)) if src_slots is None else [int(s) for s in src_slots]
+        if any(s < 0 or s >= S for s in slots):
+            raise ValueError("%s: src_slots %s name maps of a stack of %d" % (who, slots, S))
+        n_src = len(slots)
+        if n_src > CONSISTENCY_MAX_SRC:
+            raise ValueError("%s: %d sources, at most %d" % (who, n_src, CONSISTENCY_MAX_SRC))
+    if n_src:
+        m = np.asarray(src_T, dtype=np.float64)
+        if m.ndim != 3 or m.shape[0] != n_src or m.shape[1:] not in ((3, 4), (4, 4)):
+            raise ValueError("%s: src_T is [%d,3,4] or [%d,4,4], got %s" % (who, n_src, n_src, m.shape))
+        with np.errstate(over="ignore"):
+            cT = np.ascontiguousarray(m[:, :3, :4].astype(np.float32)).reshape(-1)      # rounded once
+        slots = (ctypes.c_int * n_src)(*slots)
+    if votes is None:
+        votes = torch.empty((H, W), dtype=torch.float32, device=dev)
+    if depth_out is None:
+        depth_out = torch.empty((H, W), dtype=torch.float32, device=dev)
+    votes = None if votes is False else votes
+    depth_out = None if depth_out is False else depth_out
+    with torch.cuda.device(dev):
+        rc = _lib.load().nrgbd_depth_consistency_f32(_p(depth), _p(gate), float(gate_thr), H, W, float(depth_range[0]), float(depth_range[1]),
+                                                     k[0], k[1], k[2], k[3], _p(src_depth if n_src else None),
+                                                     _p(src_gate if n_src else None), int(stride), slots if n_src else None,
+                                                     ctypes.c_void_p(cT.ctypes.data) if n_src else None, n_src, float(rel_thr),
+                                                     int(min_views), _p(votes), _p(depth_out), _stream(depth))
+    _lib.check(rc, "nrgbd_depth_consistency_f32")
+    return votes, depth_out
