@@ -69,7 +69,8 @@ extern "C" {
  * entries nrgbd_icp_workgroups, nrgbd_icp_workspace, nrgbd_icp_terms_f32 and nrgbd_icp_update (a depth frame registered against the
  * fused volume), and for nrgbd_icp_terms_photo_f32 (the same with a photometric term against the volume's rendered colour), and for
  * nrgbd_tsdf_reintegrate_f32 and nrgbd_tsdf_reintegrate_color_f32 (a fused frame taken out of the volume and put back at a corrected
- * pose), and for nrgbd_depth_consistency_f32 (a depth map cross-checked against other views' maps before it is fused). */
+ * pose), and for nrgbd_depth_consistency_f32 (a depth map cross-checked against other views' maps before it is fused), and for nrgbd_tsdf_shift_f32
+ * (the TSDF volume moved by whole voxels so that it follows the camera, with the leaving part handed out). */
 #define NRGBD_INTERFACE_VERSION "0.10"
 const char* nrgbd_version(void);
 const char* nrgbd_strerror(int code);
@@ -1403,6 +1404,36 @@ int nrgbd_depth_consistency_f32(const float* depth, const float* gate, float gat
                                 float fx, float fy, float cx, float cy, const float* src_depth, const float* src_gate,
                                 long src_stride, const int* src_slots, const float* src_T, int n_src, float rel_thr,
                                 int min_views, float* votes, float* depth_out, void* stream);
+
+/*
+ * The moving TSDF volume (tsdf_shift.hip; neuralrgbd_amd/fusion.py: TSDFVolume.shift, follow_shift, FusionVideoStream(follow=...)): the
+ * grid moved by whole voxels so that it follows the camera — the scheme of Kintinuous and large-scale KinFu.  Every nrgbd_tsdf_* entry
+ * takes the origin per launch, so a moved volume is an ordinary volume at origin + voxel_size s whose contents sit s voxels lower.  No
+ * counterpart in the reference.  A pure copy: no arithmetic touches a value, so NaN payloads, signed zeros and denormals come through
+ * bit for bit; no atomics, no workspace, the same bits in every run.  One launch on the caller's stream, capturable.
+ *
+ * nrgbd_tsdf_shift_f32 — no counterpart in the reference: dst = src moved by s = (sx, sy, sz) voxels, the entering region empty, and
+ *   (spill) src turned into the spill volume: the part of the model that leaves, in the old frame.
+ *   src dst      device fp32 [planes][Z][Y][X], two buffers that do not overlap: planes = 2 (tsdf, weight) or 5 (tsdf, weight, r, g, b)
+ *   sx sy sz     the shift in voxels, any int: the new origin is origin + voxel_size s
+ *   per dst lattice index i = (ix, iy, iz), in every plane p:
+ *     j = i + s;  dst[p][i] = src[p][j] where 0 <= j_k < n_k for k = x, y, z, the bits unchanged; else +0.0f, and nothing is loaded
+ *   the old voxels j with j_k < s_k (s_k > 0) or j_k >= n_k + s_k (s_k < 0) for some k LEAVE — no dst voxel holds them —, every other
+ *   old voxel is RETAINED: each of its words is read by exactly one lane, the one that owns that plane's dst voxel i = j - s
+ *   spill != 0:  the RIM is the set of retained voxels whose new index i_k is 0 (s_k > 0) or n_k - 1 (s_k < 0) for some k: one voxel
+ *     thick, on the faces that face the motion only.  Every retained voxel that is not on the rim gets src[0][j] = src[1][j] = +0.0f
+ *     (tsdf and weight), each word written by the lane that read it, after its read.  Leaving voxels, rim voxels and planes 2 .. 4 of src keep
+ *     their bits.  A mesh cell is emitted only where all eight corners carry weight, so of the old volume's cells exactly those with a
+ *     leaving corner survive in src, and exactly those whose corners are all retained are cells of dst: no gap, no duplicate triangle.
+ *   spill == 0:  src is only read
+ *   |s_k| >= n_k for some k: nothing is retained — dst is all +0.0f and src keeps every bit;  s = 0: a plain copy (every voxel is
+ *     retained and none is on the rim: with spill, src's tsdf and weight become 0)
+ *   errors       NRGBD_E_NULL: src or dst NULL;  NRGBD_E_SHAPE: planes not 2 or 5, a dimension <= 0 or X Y Z > 2^31;  NRGBD_E_ARG:
+ *                the two buffers' byte ranges overlap.  Checked in this order, before anything touches the device.
+ *   The vector form (16-byte stores; 16-byte loads when sx % 4 == 0 too) needs X % 4 == 0 and both bases 16-byte aligned; anything
+ *   else runs the element form: the same bits.
+ */
+int nrgbd_tsdf_shift_f32(float* src, float* dst, int planes, int X, int Y, int Z, int sx, int sy, int sz, int spill, void* stream);
 
 #ifdef __cplusplus
 }

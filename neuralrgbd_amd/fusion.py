@@ -29,6 +29,12 @@ conventions (lattice, projection, update rule, crossings) are written out in inc
     discontinuity never enter the volume.  Not built: deferred two-sided filtering (with the frames that arrive later), a fused
     depth averaged over the agreeing views, a free-space-violation count, sources of another size or intrinsics, and scoring the
     filtered set in evaluate.EvalVideoStream;
+  * the moving volume: `TSDFVolume.shift` moves the grid by whole voxels in one launch (ops.tsdf_shift: what stays keeps its bits,
+    what enters is empty, what leaves is handed out as a spill volume), `follow_shift` says when and by how much from a camera pose,
+    and `FusionVideoStream(follow=distance)` keeps the volume around the camera's focus, extracts every spill (`chunks`) and
+    stitches them with the live mesh (`world_mesh`, `world_points`) — the scheme of Kintinuous and large-scale KinFu.  Not built:
+    exact `repose` of frames integrated before a shift (it would clip the removal to the region that has existed since), swapping
+    spilled slabs back in when the camera returns, circular addressing in place of the copy, a sparse block volume;
   * `fuse_sequence`, `save_ply`.
 """
 import math
@@ -99,6 +105,39 @@ def frustum_box(extM, intrinsics, size, depth_max, volume):
     return tuple(v[0] for v in lo_hi) + tuple(v[1] for v in lo_hi)
 
 
+def follow_shift(extM, volume, distance, margin=0.25, step=8):
+    """The shift (sx, sy, sz) in whole voxels that brings `volume` back around a camera at extM (host world -> camera): float64 on
+    the host, nothing launched.  The focus point is the camera centre plus `distance` metres along the optical axis, in world
+    coordinates; g is its lattice coordinate (focus - origin) / voxel_size and c = (dims - 1) / 2 the grid's centre.  Along each axis
+    the shift is step * round((g_k - c_k) / step) where |g_k - c_k| > margin * dims_k (Python's round: a tie goes to the even
+    multiple), and 0 otherwise: the volume stays put while the focus is inside the middle 2 margin of the grid, and moves by whole
+    steps that re-centre it when it is not.  step: a positive multiple of 4, so that an x shift keeps the shift kernel's 16-byte
+    source loads; 0 < margin < 0.5; distance finite.  distance, margin and step are parameters, not measurements: where the fused
+    surface lies in front of the camera, and how often the volume may move.  A non-finite or singular pose gives (0, 0, 0)."""
+    distance, margin = float(distance), float(margin)
+    if not math.isfinite(distance):
+        raise ValueError("follow_shift: distance must be finite, got %r" % (distance,))
+    if not 0 < margin < 0.5:
+        raise ValueError("follow_shift: margin %r is not in (0, 0.5)" % (margin,))
+    if isinstance(step, bool) or int(step) != step or step <= 0 or int(step) % 4:
+        raise ValueError("follow_shift: step is a positive multiple of 4 voxels (the 16-byte source path), got %r" % (step,))
+    step = int(step)
+    m = _host_matrix(extM, "follow_shift")
+    if not np.isfinite(m).all():
+        return (0, 0, 0)
+    try:
+        focus = np.linalg.solve(m[:3, :3], np.array([0.0, 0.0, distance]) - m[:3, 3])
+    except np.linalg.LinAlgError:
+        return (0, 0, 0)
+    out = []
+    for k in range(3):
+        off = (float(focus[k]) - volume.origin[k]) / volume.voxel_size - (volume.dims[k] - 1) / 2.0
+        if not math.isfinite(off):
+            return (0, 0, 0)
+        out.append(step * int(round(off / step)) if abs(off) > margin * volume.dims[k] else 0)
+    return tuple(out)
+
+
 class TSDFVolume:
     """A dense TSDF volume on the device: `tsdf` and `weight`, fp32 [Z,Y,X]; lattice point (ix, iy, iz) lies at
     origin + voxel_size (ix, iy, iz).  color=True: also `color`, fp32 [3,Z,Y,X] (r, g, b), the running average of the colours of
@@ -121,16 +160,78 @@ class TSDFVolume:
         self._buf = torch.zeros((5 if color else 2, Z, Y, X), dtype=torch.float32,
                                 device=torch.device(device if device is not None else "cuda"))
         self.device = self._buf.device                              # with its index: "cuda" names the current device
-        self.tsdf, self.weight = self._buf[0], self._buf[1]
-        self.color = self._buf[2:5] if color else None
+        self._origin0 = self.origin                                 # the construction origin: `origin` is always formed from it
+        self.offset = (0, 0, 0)                                     # the cumulative shift in voxels (shift)
+        self._spare = None                                          # the second buffer, allocated at the first shift
+        self._generation = 0                                        # counts the shifts: a spill volume is valid for one
+        self._parent = None                                         # a spill volume: (the volume it came from, its generation then)
+        self._point(self._buf)
+        self._scratch()
+
+    def _point(self, buf):
+        self._buf = buf
+        self.tsdf, self.weight = buf[0], buf[1]
+        self.color = buf[2:5] if buf.shape[0] == 5 else None
+
+    def _scratch(self):
         self._counts = torch.zeros(2, dtype=torch.int64, device=self.device)
         self._workspace = None
         self._mesh_counts = self._mesh_workspace = None
         self._trackers = {}
 
+    def _live(self, who):
+        """The one check of a spill volume's validity: its buffer is the parent's spare, which the parent's next shift overwrites."""
+        if self._parent is not None and self._parent[0]._generation != self._parent[1]:
+            raise ValueError("TSDFVolume.%s: this spill volume is stale — the volume it came from has shifted again and reused its "
+                             "buffer (extract a spill before the next shift)" % who)
+
     def reset(self):
-        """An empty volume again (asynchronous)."""
+        """An empty volume again (asynchronous); `offset` and `origin` stay where the shifts have put them."""
+        self._live("reset")
         self._buf.zero_()
+
+    def shift(self, voxels, spill=False):
+        """The volume moved by voxels = (sx, sy, sz) whole voxels, one launch (ops.tsdf_shift): `offset` grows by it, `origin` becomes
+        origin0 + voxel_size * offset (formed in float64 from the construction origin: rounding does not accumulate over many
+        shifts), the voxels that stay keep their bits at their new indices, the region that enters is empty, and what leaves is gone
+        — or, with spill=True, returned: a TSDFVolume at the OLD origin (the same voxel size, trunc, w_max and colour) that holds the
+        leaving voxels and a one-voxel rim of the retained ones on the faces that face the motion, everything else at weight 0, so
+        that its mesh() is exactly the old mesh's triangles with a corner that left and the live volume's mesh the rest: no gap, no
+        duplicate.  points(), mesh() and raycast() work on it unchanged.  It is a view of this volume's other buffer, not a copy:
+        valid until this volume's next shift, after which its methods raise ValueError.
+        The volume keeps two buffers of the same shape and the launch copies from one into the other, then they swap roles: the
+        second is allocated at the first shift (the one allocation; a volume that is never shifted never has it).  `tsdf`, `weight`
+        and `color` are re-pointed: tensors fetched from these attributes BEFORE a shift are the spill buffer afterwards.
+        A zero shift launches nothing and returns None; without spill the result is None.  Synchronises nothing."""
+        self._live("shift")
+        try:
+            s = tuple(int(v) for v in voxels)
+            whole = len(s) == 3 and all(v == w for v, w in zip(s, voxels))
+        except (TypeError, ValueError):
+            whole = False
+        if not whole:
+            raise ValueError("TSDFVolume.shift: voxels = (sx, sy, sz), whole voxels; got %r" % (voxels,))
+        if s == (0, 0, 0):
+            return None
+        if self._spare is None:
+            self._spare = torch.empty_like(self._buf)
+        ops.tsdf_shift(self._buf, self._spare, s, spill=spill)
+        old_buf, old_origin = self._buf, self.origin
+        self._point(self._spare)
+        self._spare = old_buf
+        self._generation += 1                                       # whatever spill volume viewed the spare is stale from here
+        self.offset = tuple(o + v for o, v in zip(self.offset, s))
+        self.origin = tuple(o + self.voxel_size * k for o, k in zip(self._origin0, self.offset))       # Python floats: float64
+        if not spill:
+            return None
+        out = object.__new__(TSDFVolume)
+        out.dims, out.voxel_size, out.trunc, out.w_max, out.device = self.dims, self.voxel_size, self.trunc, self.w_max, self.device
+        out.origin = out._origin0 = old_origin
+        out.offset, out._spare, out._generation = (0, 0, 0), None, 0
+        out._parent = (self, self._generation)
+        out._point(old_buf)
+        out._scratch()
+        return out
 
     def _frame(self, who, depth, intrinsics, gate, gate_thr, weight, color, color_intrinsics, color_affine):
         """What integrate, deintegrate and reintegrate check and prepare alike: -> (depth [H,W], gate, weight, (fx, fy, cx, cy),
@@ -184,6 +285,7 @@ class TSDFVolume:
         equal; color_affine = (a [3], b [3]): a pixel's colour is image * a + b per channel (default a = 1, b = 0)."""
         depth, gate, weight, intrinsics, color_intrinsics = self._frame("integrate", depth, intrinsics, gate, gate_thr, weight, color,
                                                                         color_intrinsics, color_affine)
+        self._live("integrate")
         m = _host_matrix(extM, "TSDFVolume.integrate")
         box = None
         if cull:
@@ -203,6 +305,7 @@ class TSDFVolume:
                      color_affine, w_floor):
         depth, gate, weight, intrinsics, color_intrinsics = self._frame(who, depth, intrinsics, gate, gate_thr, weight, color,
                                                                         color_intrinsics, color_affine)
+        self._live(who)
         poses = [_host_matrix(m, "TSDFVolume." + who) for m in ((extM_old,) if extM_new is None else (extM_old, extM_new))]
         box = None
         if cull:                                                    # the hull of the boxes: culling is conservative, the same bits
@@ -253,6 +356,7 @@ class TSDFVolume:
         two voxels' colours interpolated at the crossing —, found).  Reads the count back: the one place this object synchronises
         (and allocates)."""
         color = self._need_color("points") if colors else None
+        self._live("points")
         if self._workspace is None:
             self._workspace = torch.empty(ops.tsdf_extract_workspace(*self.dims) // 8, dtype=torch.int64, device=self.device)
         args = (self.tsdf, self.weight, self.origin, self.voxel_size, w_min, self._workspace)
@@ -281,6 +385,7 @@ class TSDFVolume:
         (vertices, faces, colors [n,3] CUDA fp32 — row p the colour of vertex p —, (vertices found, triangles found)).  Reads the
         counts back: like `points`, the one place this object synchronises (and allocates)."""
         color = self._need_color("mesh") if colors else None
+        self._live("mesh")
         if self._mesh_workspace is None:
             self._mesh_workspace = torch.empty((ops.tsdf_mesh_workspace(*self.dims) + 7) // 8, dtype=torch.int64, device=self.device)
             self._mesh_counts = torch.zeros(4, dtype=torch.int64, device=self.device)
@@ -314,6 +419,7 @@ class TSDFVolume:
         as one more element of the result: (depth, rgb) or (depth, normal, rgb); `out` then takes the same tuple.  Synchronises
         nothing."""
         planes = self._need_color("raycast") if color else None
+        self._live("raycast")
         H, W = (int(n) for n in size)
         if isinstance(intrinsics, dict):
             intrinsics = intrinsics_at(intrinsics, H, W)
@@ -446,11 +552,25 @@ class FusionVideoStream(VideoDepthStream):
     on: surfaces enter the volume k frames late, the price of never fusing what no other view confirms.  consistency_rel: a source
     agrees where |ds - q_z| <= consistency_rel q_z; like the tracker's dist_thr a parameter, not a measurement.  `last_votes` is
     the votes map of the last frame (a buffer the next frame overwrites).  With consistency=0 (the default) nothing of this is
-    constructed or launched, and the stream's launches and bits are what they were."""
+    constructed or launched, and the stream's launches and bits are what they were.
+    follow=distance (metres): the volume follows the camera.  Before a depth frame is tracked or fused, follow_shift is evaluated
+    from the pose the frame is about to be tracked or integrated from (the pose the consistency filter uses) with `distance`,
+    follow_margin and follow_step — parameters, not measurements, like the tracker's dist_thr and consistency_rel —, and a non-zero
+    result moves the volume (TSDFVolume.shift: one launch; the volume's second buffer is allocated at the first shift).
+    follow_spill says what becomes of the part that leaves: 'mesh' (the default) or 'points' — the stream extracts the spill volume
+    with w_min = follow_w_min (with colours on a colour stream) and appends the result as host numpy arrays to `chunks`, which
+    synchronises once per shift (shifts are rare, and the extraction reads its counts back anyway) —, a callable that is handed the
+    spill volume (valid until the next shift), or None: what leaves is dropped and nothing is spilled.  `n_shifts` counts the shifts;
+    `world_mesh()` / `world_points()` return every chunk followed by the live volume's extraction.  reset() keeps the chunks, as
+    the volume keeps accumulating across it.  A held frame (history=N) that was integrated before a shift can no longer be taken out
+    exactly — the region that entered never held it —: `repose` and `retrack` of such a frame raise ValueError; it still serves as
+    a consistency source, which uses only its maps and pose.  With follow=None (the default) nothing of this is constructed,
+    allocated or launched, and the stream's launches and bits are what they were."""
 
     def __init__(self, model, cam_intrinsics, d_candi, volume, t_win_r=2, source="refined", conf_threshold=0., weight="uniform",
                  depth_range=None, color=False, track=False, track_kwargs=None, photo=False, history=0, consistency=0,
-                 consistency_rel=0.01, **video_kwargs):
+                 consistency_rel=0.01, follow=None, follow_margin=0.25, follow_step=8, follow_spill="mesh", follow_w_min=1.,
+                 **video_kwargs):
         from .nets import require_volume_refiner
         require_volume_refiner(model, "FusionVideoStream")
         if source not in ("refined", "dpv"):
@@ -504,6 +624,15 @@ class FusionVideoStream(VideoDepthStream):
                              % (self.depth_range,))
         self._votes = self._filtered = None                     # the filter's two outputs, allocated at the first frame
         self.last_votes = None
+        self.follow = None if follow is None else float(follow)
+        self.follow_margin, self.follow_step, self.follow_spill, self.follow_w_min = follow_margin, follow_step, follow_spill, float(follow_w_min)
+        if self.follow is not None:
+            follow_shift(np.eye(4), volume, self.follow, follow_margin, follow_step)      # the parameter refusals, at construction
+            if not (follow_spill is None or follow_spill in ("mesh", "points") or callable(follow_spill)):
+                raise ValueError("FusionVideoStream: follow_spill is 'mesh', 'points', None or a callable, got %r" % (follow_spill,))
+        self.n_shifts = 0
+        self.chunks = []                                        # what left the volume, per shift: host arrays (follow_spill)
+        self._held_shift = {}                                   # history slot -> n_shifts when its frame was integrated
         super().__init__(model, cam_intrinsics, d_candi, t_win_r=t_win_r, **video_kwargs)
         if _indexed(volume.device) != _indexed(self.device):
             raise ValueError("FusionVideoStream: the volume is on %s, the stream on %s" % (volume.device, self.device))
@@ -565,6 +694,8 @@ class FusionVideoStream(VideoDepthStream):
         tracked = self.track and self._prev is not None
         if tracked:
             pose = pose @ np.linalg.solve(self._prev[0], self._prev[1])        # the guess E_i E_prev^-1 T_prev, float64 on the host
+        if self.follow is not None:                             # before the frame is tracked or fused: the volume around its focus
+            self._follow(pose)
         raw, gate_thr = None, self.gate_thr
         if self.consistency:                                    # the gate is folded into the filtered map
             raw, raw_gate = depth, gate
@@ -588,6 +719,44 @@ class FusionVideoStream(VideoDepthStream):
                 else:
                     self._hold(ref_index, pose, depth, gate, wmap, kw.get("color"))
         return out
+
+    def _follow(self, pose):
+        """Moves the volume when the focus of `pose` has left its middle (follow_shift), and hands out what leaves."""
+        s = follow_shift(pose, self.volume, self.follow, self.follow_margin, self.follow_step)
+        if s == (0, 0, 0):
+            return
+        spill = self.volume.shift(s, spill=self.follow_spill is not None)
+        self.n_shifts += 1
+        if callable(self.follow_spill):
+            self.follow_spill(spill)
+        elif self.follow_spill == "mesh":                       # (vertices, faces[, colors]); reads its counts back: synchronises
+            self.chunks.append(tuple(t.cpu().numpy() for t in spill.mesh(w_min=self.follow_w_min, colors=self.color)[:-1]))
+        elif self.follow_spill == "points":                     # (points[, colors])
+            self.chunks.append(tuple(t.cpu().numpy() for t in spill.points(w_min=self.follow_w_min, colors=self.color)[:-1]))
+
+    def world_mesh(self):
+        """Everything fused so far as one mesh on the host (follow_spill='mesh'): every chunk in the order it left, then the live
+        volume's mesh(w_min=follow_w_min), concatenated with each part's face rows offset by the vertices before it: (vertices [n,3]
+        fp32, faces [m,3] int32[, colors [n,3] fp32 on a colour stream]) as numpy arrays.  The parts partition the model's cells:
+        no triangle is missing and none occurs twice; the seam vertices exist in both neighbours, each part being a mesh of its
+        own.  Synchronises (the live extraction reads its counts back)."""
+        if self.follow is not None and self.follow_spill != "mesh":
+            raise ValueError("FusionVideoStream.world_mesh: the chunks are meshes only with follow_spill='mesh', got %r" % (self.follow_spill,))
+        parts = list(self.chunks) + [tuple(t.cpu().numpy() for t in self.volume.mesh(w_min=self.follow_w_min, colors=self.color)[:-1])]
+        base = np.cumsum([0] + [len(p[0]) for p in parts[:-1]])
+        out = (np.concatenate([p[0] for p in parts]), np.concatenate([p[1] + np.int32(b) for p, b in zip(parts, base)]).astype(np.int32))
+        return out + ((np.concatenate([p[2] for p in parts]),) if self.color else ())
+
+    def world_points(self):
+        """The same for points: every chunk's points (a mesh chunk's vertices ARE its points), then the live volume's
+        points(w_min=follow_w_min): (points [n,3] fp32[, colors [n,3] fp32]) as numpy arrays.  A crossing between two rim voxels
+        occurs in the chunk and in what follows it."""
+        if self.follow is not None and self.follow_spill not in ("mesh", "points"):
+            raise ValueError("FusionVideoStream.world_points: no chunks are kept with follow_spill=%r" % (self.follow_spill,))
+        parts = [(p[0], p[-1]) for p in self.chunks]
+        parts.append(tuple(t.cpu().numpy() for t in self.volume.points(w_min=self.follow_w_min, colors=self.color)[:-1]))
+        out = (np.concatenate([p[0] for p in parts]),)
+        return out + ((np.concatenate([p[-1] for p in parts]),) if self.color else ())
 
     def _consistent(self, depth, gate, pose):
         """The regressed map checked against the held frames' raw maps from `pose` (one launch): -> the filtered map, in a buffer
@@ -620,6 +789,8 @@ class FusionVideoStream(VideoDepthStream):
             if t is not None:
                 self._slots[key][slot].copy_(t)
         self._held = [h for h in self._held if h[2] != slot] + [[ref_index, np.array(pose, dtype=np.float64), slot]]
+        if self.follow is not None:
+            self._held_shift[slot] = self.n_shifts
 
     def history_poses(self):
         """[(ref_index, extM)] of the frames the history holds, oldest first: the poses they are integrated at now."""
@@ -633,6 +804,10 @@ class FusionVideoStream(VideoDepthStream):
         else:
             raise KeyError("FusionVideoStream.%s: frame %r is not in the history (history=%d holds %s)"
                            % (who, ref_index, self.history, [e[0] for e in self._held]))
+        if self.follow is not None and self._held_shift[h[2]] != self.n_shifts:
+            raise ValueError("FusionVideoStream.%s: frame %r was integrated before the volume shifted: it cannot be taken out exactly "
+                             "any more (the region that entered never held it); it still serves as a consistency source"
+                             % (who, ref_index))
         pick = lambda key: None if self._slots[key] is None else self._slots[key][h[2]]
         kw = dict(gate=pick("gate"), gate_thr=self.gate_thr, weight=pick("wmap"), depth_range=self.depth_range)
         if self.consistency:                                    # the held map carries its gate; the gate slot is the raw map's

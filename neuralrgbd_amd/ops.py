@@ -1834,6 +1834,35 @@ def tsdf_reintegrate_color(tsdf, weight, color, origin, voxel_size, depth, pose_
     _lib.check(rc, "nrgbd_tsdf_reintegrate_color_f32")
 
 
+def tsdf_shift(src, dst, shift, spill=False):
+    """A TSDF volume moved by shift = (sx, sy, sz) whole voxels, one launch (nrgbd_tsdf_shift_f32; the semantics are written out in
+    include/nrgbd.h): dst[p][i] = src[p][i + shift] where i + shift lies in the grid, bit for bit, and +0.0 elsewhere — the contents
+    of a volume whose origin moved by voxel_size * shift.  src / dst: contiguous CUDA fp32 [2,Z,Y,X] (tsdf, weight) or [5,Z,Y,X]
+    (with r, g, b: TSDFVolume's buffer), the same shape and device, distinct storage (their bytes must not overlap).  spill=True:
+    the same launch turns src into the spill volume — the retained voxels' tsdf and weight set to 0 except on the one-voxel rim that
+    faces the motion, so that src's mesh cells are exactly the old volume's cells with a corner that left.  spill=False: src is only
+    read.  Nothing is allocated, nothing synchronised."""
+    who = "tsdf_shift"
+    src = _need(src, "src", strided=True)
+    if src.dim() != 4 or src.shape[0] not in (2, 5) or not src.is_contiguous():
+        raise ValueError("%s: src must be a contiguous [2|5,Z,Y,X] tensor, got %s" % (who, tuple(src.shape)))
+    dst = _need(dst, "dst", tuple(src.shape), strided=True)
+    if dst.device != src.device or not dst.is_contiguous():
+        raise ValueError("%s: dst must be contiguous and on %s" % (who, src.device))
+    nbytes = src.numel() * 4
+    if src.data_ptr() < dst.data_ptr() + nbytes and dst.data_ptr() < src.data_ptr() + nbytes:
+        raise ValueError("%s: src and dst need distinct storage (their bytes overlap)" % who)
+    s = tuple(int(v) for v in shift)
+    if len(s) != 3 or any(int(v) != v for v in shift):
+        raise ValueError("%s: shift = (sx, sy, sz) whole voxels, got %r" % (who, shift))
+    lim = 2 ** 31 - 1
+    s = tuple(max(-lim, min(lim, v)) for v in s)                # beyond the grid either way: nothing is retained
+    planes, Z, Y, X = src.shape
+    with torch.cuda.device(src.device):
+        rc = _lib.load().nrgbd_tsdf_shift_f32(_p(src), _p(dst), planes, X, Y, Z, s[0], s[1], s[2], 1 if spill else 0, _stream(src))
+    _lib.check(rc, "nrgbd_tsdf_shift_f32")
+
+
 def tsdf_extract_workspace(X, Y, Z):
     """Bytes of workspace nrgbd_tsdf_extract_points needs for an X x Y x Z grid (needs no GPU)."""
     rc = _lib.load().nrgbd_tsdf_extract_workspace(int(X), int(Y), int(Z))
