@@ -8,25 +8,28 @@
 // atomics, and the same inputs give the same bits in every run.
 //
 // tsdf_integrate_kernel<VEC>  one depth frame into the volume, one launch.  A lane owns four x-neighbours (VEC: X % 4 == 0 and both
-//                             arrays 16-byte aligned) or one voxel (any width: the same bits).  Per voxel: lattice point -> camera
-//                             -> pixel -> depth / gate / weight tests -> t = min(1, (d - zc) / trunc); only then the running average
-//                             is read.  A group none of whose voxels is updated is neither loaded nor stored; a group with one is
-//                             loaded once (2 x 16 bytes) and stored once, the voxels that were skipped with the bits they had.  The
-//                             row products r01 yw, r02 zw (and rows 1, 2) do not depend on x and are formed once per lane and row:
-//                             the same products, the same bits.
-//                             Resources (kernel-resource-usage remarks, gfx950, -O3): VEC 56 VGPRs, element form 28, 8 waves per
-//                             SIMD, no scratch, no LDS (the extraction kernels: 18 / 46 / 42 VGPRs, no scratch); two IEEE
+//                             arrays 16-byte aligned) or one voxel (any width: the same bits).  The element form's loop body is one
+//                             call of tsdf_integrate.hpp's tsdf_update_group, the update tsdf_reint.hip's kernel runs after its
+//                             removal; the VEC form spells the same update out in float4 registers, with the colour planes stored
+//                             as they are formed: on the shared group (50 / 91 VGPRs, 8 / 5 waves) the kernel gave the same bits but
+//                             ran 2 to 5 % longer at 256^3, so the VEC form is the instruction stream it was.
+//                             Per voxel: lattice point -> camera -> pixel -> depth / gate / weight tests -> t = min(1, (d - zc) /
+//                             trunc); only then the running average is read.  A group none of whose voxels is updated is neither
+//                             loaded nor stored; a group with one is loaded once (2 x 16 bytes) and stored once, the voxels that
+//                             were skipped with the bits they had.
+//                             Resources (kernel-resource-usage remarks, gfx950, -O3): VEC 56 VGPRs, element form 26, 8 waves per
+//                             SIMD, no scratch, no LDS (the extraction kernels: 18 / 44 / 42 VGPRs, no scratch); two IEEE
 //                             divisions for the projection, one for t and one for the average per updated voxel.
 // tsdf_integrate_kernel<VEC, TsdfColour>  the same kernel with the colour arguments (nrgbd_tsdf_integrate_color_f32): for a voxel that
 //                             is updated, the pixel of the colour image it projects to (the quotients xc / zc, yc / zc of the depth
 //                             projection, the image's own intrinsics, clamped into the image) goes through the affine and, when its
 //                             three values are finite, into the running average of the three colour planes with the OLD weight; the
 //                             image is read only for voxels that passed every test, a group that updates nothing touches no plane, and
-//                             a group with an update loads and stores five planes (5 x 16 bytes per lane in the VEC form, which also
-//                             needs the colour planes 16-byte aligned).  The colour arguments are an optional parameter pack: without
-//                             them (Colour... empty) COLOR is false and the kernel is the instruction stream it was before colour.
+//                             a group whose colour changes loads and stores five planes (5 x 16 bytes per lane in the VEC form,
+//                             which also needs the colour planes 16-byte aligned).  The colour arguments are an optional parameter
+//                             pack: without them (Colour... empty) COLOR is false and no colour code is compiled in.
 //                             Resources (kernel-resource-usage remarks, gfx950, -O3): VEC 94 VGPRs (5 waves per SIMD), element form
-//                             53 (7 waves); ScratchSize 0, no LDS; three more IEEE divisions per updated voxel.  The coloured point
+//                             45 (8 waves); ScratchSize 0, no LDS; three more IEEE divisions per updated voxel.  The coloured point
 //                             writer: 50 VGPRs, no scratch.
 // tsdf_extract_kernel<false>  surface crossings per workgroup of kExtractVoxels consecutive voxels (linear index order)
 // tsdf_scan_kernel            one workgroup: exclusive prefix of those counts in index order, kScanPass records per pass with a
@@ -35,7 +38,7 @@
 //                             below the capacity: ascending (linear voxel index, axis) order, nothing behind the written rows.
 // The crossing predicate, a lane's four voxels, the point writer and the scan live in tsdf_extract.hpp: tsdf_mesh.hip (the triangle
 // mesh, whose vertices are these points) runs the same device code.
-#include "tsdf_integrate.hpp"    // the frame, the chain up to (t, w), the colour pixel, the averages, the checks: shared with tsdf_reint.hip
+#include "tsdf_integrate.hpp"    // the frame, the lane group's update, the checks: shared with tsdf_reint.hip
 
 namespace nrgbd {
 
@@ -54,9 +57,9 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(float* __restrict__
     const int unit = (int)at;
     for (int iz = f.z0 + (int)blockIdx.z; iz < f.z1; iz += (int)gridDim.z) {
         for (int iy = f.y0 + (int)(blockIdx.y * 4 + threadIdx.y); iy < f.y1; iy += (int)gridDim.y * 4) {
-            const TsdfRow row = tsdf_row(f, iy, iz);
             const size_t base = ((size_t)iz * (size_t)f.Y + (size_t)iy) * (size_t)f.X;
-            if (VEC) {
+            if (VEC) {                                              // tsdf_update_group<4, false, true, COLOR> spelt out: see the header
+                const TsdfRow row = tsdf_row(f, iy, iz);
                 float t[4], w[4], xq[4], yq[4];
                 bool ok[4];
 #pragma unroll
@@ -98,26 +101,22 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(float* __restrict__
                 if (ok[3]) tsdf_average(T.w, Wt.w, t[3], w[3], f.w_max);
                 *pt = T;
                 *pw = Wt;
-            } else {
-                float t, w, xq = 0.f, yq = 0.f;
-                if (!tsdf_observe<COLOR>(f, row, unit, depth, gate, wmap, t, w, xq, yq)) continue;
-                float T = tsdf[base + unit], Wt = weight[base + unit];
-                if (COLOR) {
-                    float c[3];
-                    if (tsdf_colour(m, image, xq, yq, c)) {
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) {
-                            float* pc = color + k * m.volume + base + unit;
-                            *pc = tsdf_blend(*pc, Wt, c[k], w);
-                        }
-                    }
-                }
-                tsdf_average(T, Wt, t, w, f.w_max);
-                tsdf[base + unit] = T;
-                weight[base + unit] = Wt;
-            }
+            } else
+                tsdf_update_group<1, false, true, COLOR>(tsdf, weight, color, depth, gate, wmap, image, f, f, m, 0.f, iy, iz, unit,
+                                                         base + (size_t)unit);
         }
     }
+}
+
+// The launch of both entries: the form (VEC / element) chosen on the host.
+template <class... Colour>
+static void tsdf_integrate_launch(bool vec, const TsdfFrame& f, float* tsdf, float* weight, const float* depth, const float* gate,
+                                  const float* wmap, hipStream_t st, const Colour&... colour) {
+    const dim3 grid = tsdf_integrate_grid(f, vec), block(64, 4);
+    if (vec)
+        hipLaunchKernelGGL((tsdf_integrate_kernel<true, Colour...>), grid, block, 0, st, tsdf, weight, depth, gate, wmap, f, colour...);
+    else
+        hipLaunchKernelGGL((tsdf_integrate_kernel<false, Colour...>), grid, block, 0, st, tsdf, weight, depth, gate, wmap, f, colour...);
 }
 
 // ---- extraction ---------------------------------------------------------------------------------------------------------------
@@ -161,12 +160,7 @@ extern "C" int nrgbd_tsdf_integrate_f32(float* tsdf, float* weight, int X, int Y
     TsdfFrame f;
     const int rc = tsdf_frame(f, X, Y, Z, ox, oy, oz, voxel_size, H, W, pose, fx, fy, cx, cy, trunc, d_near, d_far, w_max, gate_thr, box, nullptr);
     if (rc != NRGBD_OK) return rc;
-    const bool vec = X % 4 == 0 && (((uintptr_t)tsdf | (uintptr_t)weight) & 15) == 0;
-    const dim3 grid = tsdf_integrate_grid(f, vec);
-    if (vec)
-        hipLaunchKernelGGL(tsdf_integrate_kernel<true>, grid, dim3(64, 4), 0, (hipStream_t)stream, tsdf, weight, depth, gate, wmap, f);
-    else
-        hipLaunchKernelGGL(tsdf_integrate_kernel<false>, grid, dim3(64, 4), 0, (hipStream_t)stream, tsdf, weight, depth, gate, wmap, f);
+    tsdf_integrate_launch(tsdf_vec_ok(X, tsdf, weight), f, tsdf, weight, depth, gate, wmap, (hipStream_t)stream);
     NRGBD_CHECK_LAUNCH();
     return NRGBD_OK;
 }
@@ -179,26 +173,12 @@ extern "C" int nrgbd_tsdf_integrate_color_f32(float* tsdf, float* weight, float*
                                               float fxc, float fyc, float cxc, float cyc, const float* affine, void* stream) {
     using namespace nrgbd;
     if (!tsdf || !weight || !depth || !pose || !color || !image || !affine) return NRGBD_E_NULL;
-    TsdfImage m;
-    m.fx = fxc; m.fy = fyc; m.cx = cxc; m.cy = cyc;
-    for (int j = 0; j < 3; ++j) {
-        m.a[j] = affine[j];
-        m.b[j] = affine[3 + j];
-    }
-    m.H = Hc; m.W = Wc;
-    m.volume = (size_t)(X > 0 ? X : 0) * (size_t)(Y > 0 ? Y : 0) * (size_t)(Z > 0 ? Z : 0);
+    const TsdfImage m = tsdf_image(X, Y, Z, Hc, Wc, fxc, fyc, cxc, cyc, affine);
     TsdfFrame f;
     const int rc = tsdf_frame(f, X, Y, Z, ox, oy, oz, voxel_size, H, W, pose, fx, fy, cx, cy, trunc, d_near, d_far, w_max, gate_thr, box, &m);
     if (rc != NRGBD_OK) return rc;
-    const bool vec = X % 4 == 0 && (((uintptr_t)tsdf | (uintptr_t)weight | (uintptr_t)color) & 15) == 0;      // X % 4 == 0: every plane
-    const dim3 grid = tsdf_integrate_grid(f, vec);
-    const TsdfColour k = {color, image, m};
-    if (vec)
-        hipLaunchKernelGGL((tsdf_integrate_kernel<true, TsdfColour>), grid, dim3(64, 4), 0, (hipStream_t)stream, tsdf, weight, depth, gate,
-                           wmap, f, k);
-    else
-        hipLaunchKernelGGL((tsdf_integrate_kernel<false, TsdfColour>), grid, dim3(64, 4), 0, (hipStream_t)stream, tsdf, weight, depth, gate,
-                           wmap, f, k);
+    tsdf_integrate_launch(tsdf_vec_ok(X, tsdf, weight, color), f, tsdf, weight, depth, gate, wmap, (hipStream_t)stream,
+                          TsdfColour{color, image, m});
     NRGBD_CHECK_LAUNCH();
     return NRGBD_OK;
 }

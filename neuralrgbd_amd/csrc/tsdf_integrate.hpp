@@ -1,7 +1,8 @@
 // tsdf_integrate.hpp — what the integration of a depth frame (tsdf.hip, nrgbd_tsdf_integrate_f32 and its coloured form) and its
 // inverse (tsdf_reint.hip, nrgbd_tsdf_reintegrate_f32: a frame taken out of the volume and put back at another pose) share: the frame,
-// the per-voxel chain up to (t, w), the colour pixel, the running average, the entries' argument checks and the launch grid.  They
-// exist once, here, so that what one launch adds is what the other removes, bit for bit.
+// the per-voxel chain up to (t, w), the colour pixel, the running average and its inverse, the lane group's update built from them
+// (tsdf_update_group), the entries' argument checks and the launch grid.  They exist once, here, so that what one launch adds is what
+// the other removes, bit for bit.
 #pragma once
 #include "tsdf_extract.hpp"      // kFltMax, tsdf_voxels, tsdf_positive
 
@@ -103,6 +104,170 @@ struct TsdfColour {
 
 __device__ __forceinline__ TsdfColour tsdf_colour_args() { return TsdfColour(); }
 __device__ __forceinline__ const TsdfColour& tsdf_colour_args(const TsdfColour& k) { return k; }
+
+// The second pose of a remove-and-add launch and the floor under which a removal empties the voxel.
+struct TsdfRepose {
+    float r[12];                        // float32(extM_add[:3,:4]); unused without ADD
+    float w_floor;
+};
+
+// Wn = Wt - w, and whether the voxel survives the removal (a NaN Wn does not)
+__device__ __forceinline__ bool tsdf_remaining(float Wt, float w, float w_floor, float& Wn) {
+    Wn = Wt - w;
+    return Wn > w_floor;
+}
+
+// C' = (C * Wt - c * w) / Wn with the stored Wt: the inverse of tsdf_blend
+__device__ __forceinline__ float tsdf_unblend(float C, float Wt, float c, float w, float Wn) { return (C * Wt - c * w) / Wn; }
+
+// T' = fminf(1, fmaxf(-1, (T * Wt - t * w) / Wn)), W' = Wn; an emptied voxel is (0, 0)
+__device__ __forceinline__ void tsdf_unaverage(float& T, float& Wt, float t, float w, float Wn, bool stays) {
+    T = stays ? fminf(1.f, fmaxf(-1.f, tsdf_unblend(T, Wt, t, w, Wn))) : 0.f;
+    Wt = stays ? Wn : 0.f;
+}
+
+__device__ __forceinline__ void tsdf_load4(const float* p, float (&v)[4]) {
+    const float4 q = *reinterpret_cast<const float4*>(p);
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+}
+
+__device__ __forceinline__ void tsdf_store4(float* p, const float (&v)[4]) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
+
+// The update of one lane group of N voxels (4: VEC, 16-byte accesses; 1: a voxel) starting at lattice column ix0 of a row: the loop
+// body of tsdf_reintegrate_kernel (REMOVE, or REMOVE and ADD) and of tsdf_integrate_kernel's element form (ADD alone, f == fa; its
+// VEC form keeps a spelling of its own in tsdf.hip, which measured faster).  REMOVE: the chain with f's pose, and the observation
+// subtracted from the weighted sums of the voxels that pass.  ADD: the chain with fa's pose and the running average.  Either way the
+// planes are loaded only when a voxel passes, colour is formed with the old weights before the distance replaces them, and a group
+// that was loaded is stored once per plane.
+template <int N, bool REMOVE, bool ADD, bool COLOR>
+__device__ __forceinline__ void tsdf_update_group(float* __restrict__ tsdf, float* __restrict__ weight, float* __restrict__ color,
+                                                  const float* __restrict__ depth, const float* __restrict__ gate,
+                                                  const float* __restrict__ wmap, const float* __restrict__ image, const TsdfFrame& f,
+                                                  const TsdfFrame& fa, const TsdfImage& m, float w_floor, int iy, int iz, int ix0,
+                                                  size_t at) {
+    float T[N], Wt[N], C[3][N];
+    bool have = false, have_c = false;
+    auto load = [&](const float* p, float (&v)[N]) {
+        if constexpr (N == 4) tsdf_load4(p + at, v);
+        else v[0] = p[at];
+    };
+    auto store = [&](float* p, const float (&v)[N]) {
+        if constexpr (N == 4) tsdf_store4(p + at, v);
+        else p[at] = v[0];
+    };
+    if (REMOVE) {                                                   // its chain ends with this scope
+        const TsdfRow row = tsdf_row(f, iy, iz);
+        float t[N], w[N], xq[N], yq[N];
+        bool ok[N];
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const int ix = ix0 + j;
+            t[j] = w[j] = xq[j] = yq[j] = 0.f;
+            ok[j] = ix >= f.x0 && ix < f.x1 && tsdf_observe<COLOR>(f, row, ix, depth, gate, wmap, t[j], w[j], xq[j], yq[j]);
+            have = have || ok[j];
+        }
+        if (have) {
+            load(tsdf, T);
+            load(weight, Wt);
+            float Wn[N];
+            bool stays[N];
+#pragma unroll
+            for (int j = 0; j < N; ++j) stays[j] = tsdf_remaining(Wt[j], w[j], w_floor, Wn[j]);
+            if (COLOR) {                                            // with the stored weights, before the removal replaces them
+                float c[N][3];
+                bool fin[N];
+#pragma unroll
+                for (int j = 0; j < N; ++j) {
+                    c[j][0] = c[j][1] = c[j][2] = 0.f;
+                    fin[j] = ok[j] && tsdf_colour(m, image, xq[j], yq[j], c[j]);
+                    have_c = have_c || fin[j] || (ok[j] && !stays[j]);
+                }
+                if (have_c) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        load(color + k * m.volume, C[k]);
+#pragma unroll
+                        for (int j = 0; j < N; ++j) {
+                            if (ok[j] && !stays[j]) C[k][j] = 0.f;
+                            else if (fin[j]) C[k][j] = tsdf_unblend(C[k][j], Wt[j], c[j][k], w[j], Wn[j]);
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < N; ++j)
+                if (ok[j]) tsdf_unaverage(T[j], Wt[j], t[j], w[j], Wn[j], stays[j]);
+        }
+    }
+    if (ADD) {                                                      // on the values in registers, where the removal loaded them
+        const TsdfRow row = tsdf_row(fa, iy, iz);
+        float t[N], w[N], xq[N], yq[N];
+        bool ok[N], any = false;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const int ix = ix0 + j;
+            t[j] = w[j] = xq[j] = yq[j] = 0.f;
+            ok[j] = ix >= fa.x0 && ix < fa.x1 && tsdf_observe<COLOR>(fa, row, ix, depth, gate, wmap, t[j], w[j], xq[j], yq[j]);
+            any = any || ok[j];
+        }
+        if (any) {
+            if (!have) {
+                load(tsdf, T);
+                load(weight, Wt);
+                have = true;
+            }
+            if (COLOR) {                                            // with the old weights, before the average replaces them
+                float c[N][3];
+                bool fin[N], any_fin = false;
+#pragma unroll
+                for (int j = 0; j < N; ++j) {
+                    c[j][0] = c[j][1] = c[j][2] = 0.f;
+                    fin[j] = ok[j] && tsdf_colour(m, image, xq[j], yq[j], c[j]);
+                    any_fin = any_fin || fin[j];
+                }
+                if (any_fin) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        if (!have_c) load(color + k * m.volume, C[k]);
+#pragma unroll
+                        for (int j = 0; j < N; ++j)
+                            if (fin[j]) C[k][j] = tsdf_blend(C[k][j], Wt[j], c[j][k], w[j]);
+                    }
+                    have_c = true;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < N; ++j)
+                if (ok[j]) tsdf_average(T[j], Wt[j], t[j], w[j], fa.w_max);
+        }
+    }
+    if (!have) return;
+    store(tsdf, T);
+    store(weight, Wt);
+    if (COLOR && have_c) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) store(color + k * m.volume, C[k]);
+    }
+}
+
+// The colour entries' image: intrinsics, affine (a [3], then b [3]), size, and the distance between two colour planes of the grid.
+static inline TsdfImage tsdf_image(int X, int Y, int Z, int Hc, int Wc, float fxc, float fyc, float cxc, float cyc, const float* affine) {
+    TsdfImage m;
+    m.fx = fxc; m.fy = fyc; m.cx = cxc; m.cy = cyc;
+    for (int j = 0; j < 3; ++j) {
+        m.a[j] = affine[j];
+        m.b[j] = affine[3 + j];
+    }
+    m.H = Hc; m.W = Wc;
+    m.volume = (size_t)(X > 0 ? X : 0) * (size_t)(Y > 0 ? Y : 0) * (size_t)(Z > 0 ? Z : 0);
+    return m;
+}
+
+// Whether the VEC form may run: rows of whole 16-byte groups (X % 4 == 0, which holds for every plane) in 16-byte aligned planes.
+template <class... Plane>
+static inline bool tsdf_vec_ok(int X, const Plane*... planes) {
+    return X % 4 == 0 && ((... | (uintptr_t)planes) & 15) == 0;
+}
 
 // The checks the integrations share, in the documented order (m: the colour entry's image, else NULL), and the frame.
 static inline int tsdf_frame(TsdfFrame& f, int X, int Y, int Z, float ox, float oy, float oz, float voxel_size, int H, int W, const float* pose,

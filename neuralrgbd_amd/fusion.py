@@ -38,6 +38,7 @@ conventions (lattice, projection, update rule, crossings) are written out in inc
   * `fuse_sequence`, `save_ply`.
 """
 import math
+import typing
 
 import numpy as np
 import torch
@@ -283,44 +284,33 @@ class TSDFVolume:
         colour volume refuses a frame without: the shared weight would go out of step with the colour); color_intrinsics:
         (fx, fy, cx, cy) at that size — by default intrinsics_at when `intrinsics` is a dict, or the depth map's when the sizes are
         equal; color_affine = (a [3], b [3]): a pixel's colour is image * a + b per channel (default a = 1, b = 0)."""
-        depth, gate, weight, intrinsics, color_intrinsics = self._frame("integrate", depth, intrinsics, gate, gate_thr, weight, color,
-                                                                        color_intrinsics, color_affine)
-        self._live("integrate")
-        m = _host_matrix(extM, "TSDFVolume.integrate")
-        box = None
-        if cull:
-            box = frustum_box(m, intrinsics, tuple(depth.shape), float(depth_range[1]) + self.trunc, self)
-            if box is None:
-                return False
-        if color is not None:
-            ops.tsdf_integrate_color(self.tsdf, self.weight, self.color, self.origin, self.voxel_size, depth, m, intrinsics, self.trunc, color,
-                                     color_intrinsics, color_affine, depth_range, self.w_max, gate=gate,
-                                     gate_thr=0.0 if gate_thr is None else gate_thr, wmap=weight, box=box)
-            return True
-        ops.tsdf_integrate(self.tsdf, self.weight, self.origin, self.voxel_size, depth, m, intrinsics, self.trunc, depth_range, self.w_max,
-                           gate=gate, gate_thr=0.0 if gate_thr is None else gate_thr, wmap=weight, box=box)
-        return True
+        return self._launch("integrate", depth, None, extM, intrinsics, gate, gate_thr, weight, depth_range, cull, color, color_intrinsics,
+                            color_affine, None)
 
-    def _reintegrate(self, who, depth, extM_old, extM_new, intrinsics, gate, gate_thr, weight, depth_range, cull, color, color_intrinsics,
-                     color_affine, w_floor):
+    def _launch(self, who, depth, extM_old, extM_new, intrinsics, gate, gate_thr, weight, depth_range, cull, color, color_intrinsics,
+                color_affine, w_floor):
+        """The one launch behind integrate (extM_old None: add only), deintegrate (extM_new None: remove only) and reintegrate:
+        _frame's checks, the frustum box — the hull of the boxes — of the poses given, and the entry."""
         depth, gate, weight, intrinsics, color_intrinsics = self._frame(who, depth, intrinsics, gate, gate_thr, weight, color,
                                                                         color_intrinsics, color_affine)
         self._live(who)
-        poses = [_host_matrix(m, "TSDFVolume." + who) for m in ((extM_old,) if extM_new is None else (extM_old, extM_new))]
-        box = None
+        removes = extM_old is not None                              # without a pose to remove, the pose to add is required
+        old = _host_matrix(extM_old, "TSDFVolume." + who) if removes else None
+        new = _host_matrix(extM_new, "TSDFVolume." + who) if extM_new is not None or not removes else None
+        kw = dict(depth_range=depth_range, w_max=self.w_max, gate=gate, gate_thr=0.0 if gate_thr is None else gate_thr, wmap=weight, box=None)
         if cull:                                                    # the hull of the boxes: culling is conservative, the same bits
-            boxes = [b for b in (frustum_box(m, intrinsics, tuple(depth.shape), float(depth_range[1]) + self.trunc, self) for m in poses)
-                     if b is not None]
+            boxes = [b for b in (frustum_box(m, intrinsics, tuple(depth.shape), float(depth_range[1]) + self.trunc, self)
+                                 for m in (old, new) if m is not None) if b is not None]
             if not boxes:
                 return False
-            box = tuple(min(b[k] for b in boxes) for k in range(3)) + tuple(max(b[k] for b in boxes) for k in range(3, 6))
-        kw = dict(pose_add=None if extM_new is None else poses[1], w_floor=w_floor, depth_range=depth_range, w_max=self.w_max, gate=gate,
-                  gate_thr=0.0 if gate_thr is None else gate_thr, wmap=weight, box=box)
+            kw["box"] = tuple(min(b[k] for b in boxes) for k in range(3)) + tuple(max(b[k] for b in boxes) for k in range(3, 6))
+        if removes:
+            kw.update(pose_add=new, w_floor=w_floor)
+        entry = "tsdf_reintegrate" if removes else "tsdf_integrate"
+        planes, colour = (self.tsdf, self.weight), ()
         if color is not None:
-            ops.tsdf_reintegrate_color(self.tsdf, self.weight, self.color, self.origin, self.voxel_size, depth, poses[0], intrinsics,
-                                       self.trunc, color, color_intrinsics, color_affine, **kw)
-        else:
-            ops.tsdf_reintegrate(self.tsdf, self.weight, self.origin, self.voxel_size, depth, poses[0], intrinsics, self.trunc, **kw)
+            entry, planes, colour = entry + "_color", planes + (self.color,), (color, color_intrinsics, color_affine)
+        getattr(ops, entry)(*planes, self.origin, self.voxel_size, depth, old if removes else new, intrinsics, self.trunc, *colour, **kw)
         return True
 
     def deintegrate(self, depth, extM, intrinsics, gate=None, gate_thr=None, weight=None, depth_range=(0., float("inf")), cull=True,
@@ -330,8 +320,8 @@ class TSDFVolume:
         fresh again (0, 0, and colour 0).  An inverse on voxels whose weight never reached w_max; up to rounding, which a voxel whose
         only observation this was does not see: it comes out exactly empty.  Returns False when the frustum box is empty and nothing
         was launched.  Allocates nothing and synchronises nothing."""
-        return self._reintegrate("deintegrate", depth, extM, None, intrinsics, gate, gate_thr, weight, depth_range, cull, color,
-                                 color_intrinsics, color_affine, w_floor)
+        return self._launch("deintegrate", depth, extM, None, intrinsics, gate, gate_thr, weight, depth_range, cull, color,
+                            color_intrinsics, color_affine, w_floor)
 
     def reintegrate(self, depth, extM_old, extM_new, intrinsics, gate=None, gate_thr=None, weight=None, depth_range=(0., float("inf")),
                     cull=True, color=None, color_intrinsics=None, color_affine=None, w_floor=1e-3):
@@ -341,8 +331,8 @@ class TSDFVolume:
         synchronises nothing."""
         if extM_new is None:
             raise ValueError("TSDFVolume.reintegrate: extM_new is the pose to put the frame back at (deintegrate takes it out alone)")
-        return self._reintegrate("reintegrate", depth, extM_old, extM_new, intrinsics, gate, gate_thr, weight, depth_range, cull, color,
-                                 color_intrinsics, color_affine, w_floor)
+        return self._launch("reintegrate", depth, extM_old, extM_new, intrinsics, gate, gate_thr, weight, depth_range, cull, color,
+                            color_intrinsics, color_affine, w_floor)
 
     def _need_color(self, who):
         if self.color is None:
@@ -367,14 +357,10 @@ class TSDFVolume:
         if capacity < 0:
             raise ValueError("TSDFVolume.points: capacity %d" % capacity)
         out = torch.empty((capacity, 3), dtype=torch.float32, device=self.device)
-        if colors:
-            rgb = torch.empty((capacity, 3), dtype=torch.float32, device=self.device)
-            ops.tsdf_extract_points(*args, out if capacity else None, self._counts, color=color, colors=rgb if capacity else None)
-            found, written = (int(v) for v in self._counts.cpu())
-            return out[:written], rgb[:written], found
-        ops.tsdf_extract_points(*args, out if capacity else None, self._counts)
+        rgb = torch.empty_like(out) if colors else None
+        ops.tsdf_extract_points(*args, out if capacity else None, self._counts, color=color, colors=rgb if capacity else None)
         found, written = (int(v) for v in self._counts.cpu())
-        return out[:written], found
+        return (out[:written],) + ((rgb[:written],) if colors else ()) + (found,)
 
     def mesh(self, w_min=1., capacity=None, colors=False):
         """The surface as an indexed triangle mesh: (vertices [n,3] CUDA fp32, faces [m,3] CUDA int32, (vertices found, triangles
@@ -399,15 +385,11 @@ class TSDFVolume:
             raise ValueError("TSDFVolume.mesh: capacity %s" % (capacity,))
         vertices = torch.empty((nv, 3), dtype=torch.float32, device=self.device)
         faces = torch.empty((nf, 3), dtype=torch.int32, device=self.device)
-        if colors:
-            rgb = torch.empty((nv, 3), dtype=torch.float32, device=self.device)
-            ops.tsdf_extract_mesh(*args, vertices if nv else None, faces if nf else None, self._mesh_counts, color=color,
-                                  colors=rgb if nv else None)
-            v_found, v_written, f_found, f_written = (int(v) for v in self._mesh_counts.cpu())
-            return vertices[:v_written], faces[:f_written], rgb[:v_written], (v_found, f_found)
-        ops.tsdf_extract_mesh(*args, vertices if nv else None, faces if nf else None, self._mesh_counts)
+        rgb = torch.empty_like(vertices) if colors else None
+        ops.tsdf_extract_mesh(*args, vertices if nv else None, faces if nf else None, self._mesh_counts, color=color,
+                              colors=rgb if nv else None)
         v_found, v_written, f_found, f_written = (int(v) for v in self._mesh_counts.cpu())
-        return vertices[:v_written], faces[:f_written], (v_found, f_found)
+        return (vertices[:v_written], faces[:f_written]) + ((rgb[:v_written],) if colors else ()) + ((v_found, f_found),)
 
     def raycast(self, extM, intrinsics, size, depth_range=(0., float("inf")), w_min=1., step=None, normals=False, out=None, color=False):
         """The volume seen from a camera at extM (host [3,4] or [4,4] world -> camera), one launch (ops.tsdf_raycast): z-depth [H,W] of
@@ -509,6 +491,39 @@ def filter_depth(depth, pose, sources, poses, intrinsics, rel=0.01, min_views=1,
     return got[1], got[0]
 
 
+class _Frame(typing.NamedTuple):
+    """What FusionVideoStream integrates a frame with: built once per frame, rebuilt from the history's slots for a held one."""
+    depth: torch.Tensor
+    gate: typing.Optional[torch.Tensor]
+    gate_thr: typing.Optional[float]
+    weight: typing.Optional[torch.Tensor]
+    depth_range: tuple
+    color: typing.Optional[torch.Tensor]            # the picture, its intrinsics and affine: None without colour
+    color_intrinsics: typing.Optional[tuple]
+    color_affine: typing.Optional[tuple]
+
+    def fuse_kw(self):
+        """The keywords of TSDFVolume.integrate / deintegrate / reintegrate beside the depth map and the poses."""
+        kw = self._asdict()
+        del kw["depth"]
+        return kw
+
+    def track_kw(self, photo):
+        """The keywords of TSDFVolume.track; photo: with the picture, for the photometric term."""
+        kw = dict(gate=self.gate, gate_thr=self.gate_thr, depth_range=self.depth_range)
+        if photo:
+            kw.update(image=self.color, image_affine=self.color_affine)
+        return kw
+
+
+class _Held(typing.NamedTuple):
+    """A frame of FusionVideoStream's history; a pose correction overwrites `pose` in place."""
+    ref_index: int
+    pose: np.ndarray                                # float64 [4,4]: where the frame is integrated now
+    slot: int                                       # its row of the slot tensors
+    shifts: int                                     # n_shifts when it was integrated
+
+
 class FusionVideoStream(VideoDepthStream):
     """VideoDepthStream + a TSDFVolume: push(frame, extM) returns what VideoDepthStream.push returns, and every depth frame that comes
     out is integrated into `volume` with the extrinsic pushed with its reference frame — one depth-regression launch and one
@@ -607,7 +622,7 @@ class FusionVideoStream(VideoDepthStream):
         self.history = int(history)
         if self.history < 0 or self.history != history:
             raise ValueError("FusionVideoStream: history is a number of frames >= 0, got %r" % (history,))
-        self._held = []                                         # [ref_index, integrated pose, slot], oldest first
+        self._held = []                                         # _Held records, oldest first
         self._slots = None                                      # the maps of the held frames, allocated at the first one
         self._n_held = 0
         self.consistency = int(consistency)
@@ -632,7 +647,6 @@ class FusionVideoStream(VideoDepthStream):
                 raise ValueError("FusionVideoStream: follow_spill is 'mesh', 'points', None or a callable, got %r" % (follow_spill,))
         self.n_shifts = 0
         self.chunks = []                                        # what left the volume, per shift: host arrays (follow_spill)
-        self._held_shift = {}                                   # history slot -> n_shifts when its frame was integrated
         super().__init__(model, cam_intrinsics, d_candi, t_win_r=t_win_r, **video_kwargs)
         if _indexed(volume.device) != _indexed(self.device):
             raise ValueError("FusionVideoStream: the volume is on %s, the stream on %s" % (volume.device, self.device))
@@ -684,41 +698,44 @@ class FusionVideoStream(VideoDepthStream):
         depth, logconf = ops.depth_regress(vol, d_dev, channels_last=cl)
         wmap = ops.export_depth_u16(vol, d_dev, channels_last=cl)[1] if self.weight_mode == "conf" else None
         gate = None if self.gate_thr is None else logconf
-        kw = {}
-        if self.color:
-            # frame ref_index is at most t_win_r + 1 pushes behind the newest (pipeline=True; flush() included) and the ring holds the
-            # last 2 t_win_r + 1 >= t_win_r + 2: its slot still holds its picture, written by an ingest enqueued on this stream
-            kw = dict(color=self.ring[ref_index % self.R], color_intrinsics=intrinsics_at(self.cam, self.H, self.W),
-                      color_affine=(self.std, self.mean))
+        # frame ref_index is at most t_win_r + 1 pushes behind the newest (pipeline=True; flush() included) and the ring holds the
+        # last 2 t_win_r + 1 >= t_win_r + 2: its slot still holds its picture, written by an ingest enqueued on this stream
+        image = self.ring[ref_index % self.R] if self.color else None
         pose = self._ext[slot]
         tracked = self.track and self._prev is not None
         if tracked:
             pose = pose @ np.linalg.solve(self._prev[0], self._prev[1])        # the guess E_i E_prev^-1 T_prev, float64 on the host
         if self.follow is not None:                             # before the frame is tracked or fused: the volume around its focus
             self._follow(pose)
-        raw, gate_thr = None, self.gate_thr
-        if self.consistency:                                    # the gate is folded into the filtered map
-            raw, raw_gate = depth, gate
-            depth, gate, gate_thr = self._consistent(raw, raw_gate, pose), None, None
+        raw = None
+        if self.consistency:
+            raw, depth = depth, self._consistent(depth, gate, pose)
+        fr = self._frame(depth, gate, wmap, image)
         if tracked:
-            photo = dict(image=self.ring[ref_index % self.R], image_affine=(self.std, self.mean)) if self.photo else {}
-            res = self.volume.track(depth, pose, self.cam, gate=gate, gate_thr=gate_thr, depth_range=self.depth_range,
-                                    **photo, **self.track_kwargs)
+            res = self._track(fr, pose)
             self.n_track_lost += 0 if res.ok else 1
             self.tracked_poses.append((ref_index, res.extM, res.ok))
             pose = res.extM                                     # lost: the guess (as the ray casts used it, float32-rounded)
-        if self.volume.integrate(depth, pose, self.cam, gate=gate, gate_thr=gate_thr, weight=wmap,
-                                 depth_range=self.depth_range, **kw):
+        if self.volume.integrate(fr.depth, pose, self.cam, **fr.fuse_kw()):
             self.n_integrated += 1
             self.last_ext = pose
             if self.track:
                 self._prev = (np.asarray(self._ext[slot], dtype=np.float64), np.asarray(pose, dtype=np.float64))
             if self.history:
-                if self.consistency:
-                    self._hold(ref_index, pose, depth, raw_gate, wmap, kw.get("color"), raw)
-                else:
-                    self._hold(ref_index, pose, depth, gate, wmap, kw.get("color"))
+                self._hold(ref_index, pose, fr, gate, raw)
         return out
+
+    def _frame(self, depth, gate, wmap, image):
+        """The record of a frame of this stream from its maps (`gate`: the stream's own, or None) and its picture.  With consistency
+        the gate is already folded into `depth` — the filtered map — and the record takes none: the one place that says so."""
+        if self.consistency:
+            gate = None
+        colour = (image, intrinsics_at(self.cam, self.H, self.W), (self.std, self.mean)) if self.color else (None, None, None)
+        return _Frame(depth, gate, None if gate is None else self.gate_thr, wmap, self.depth_range, *colour)
+
+    def _track(self, fr, pose, **track_kwargs):
+        """The frame registered against the volume from `pose` (with its picture when photo=True): -> tracking.TrackResult."""
+        return self.volume.track(fr.depth, pose, self.cam, **fr.track_kw(self.photo), **dict(self.track_kwargs, **track_kwargs))
 
     def _follow(self, pose):
         """Moves the volume when the focus of `pose` has left its middle (follow_shift), and hands out what leaves."""
@@ -730,9 +747,13 @@ class FusionVideoStream(VideoDepthStream):
         if callable(self.follow_spill):
             self.follow_spill(spill)
         elif self.follow_spill == "mesh":                       # (vertices, faces[, colors]); reads its counts back: synchronises
-            self.chunks.append(tuple(t.cpu().numpy() for t in spill.mesh(w_min=self.follow_w_min, colors=self.color)[:-1]))
+            self.chunks.append(self._on_host(spill.mesh))
         elif self.follow_spill == "points":                     # (points[, colors])
-            self.chunks.append(tuple(t.cpu().numpy() for t in spill.points(w_min=self.follow_w_min, colors=self.color)[:-1]))
+            self.chunks.append(self._on_host(spill.points))
+
+    def _on_host(self, extract):
+        """A volume's `mesh` or `points` at follow_w_min (with colours on a colour stream) as host arrays, without the counts."""
+        return tuple(t.cpu().numpy() for t in extract(w_min=self.follow_w_min, colors=self.color)[:-1])
 
     def world_mesh(self):
         """Everything fused so far as one mesh on the host (follow_spill='mesh'): every chunk in the order it left, then the live
@@ -742,7 +763,7 @@ class FusionVideoStream(VideoDepthStream):
         own.  Synchronises (the live extraction reads its counts back)."""
         if self.follow is not None and self.follow_spill != "mesh":
             raise ValueError("FusionVideoStream.world_mesh: the chunks are meshes only with follow_spill='mesh', got %r" % (self.follow_spill,))
-        parts = list(self.chunks) + [tuple(t.cpu().numpy() for t in self.volume.mesh(w_min=self.follow_w_min, colors=self.color)[:-1])]
+        parts = list(self.chunks) + [self._on_host(self.volume.mesh)]
         base = np.cumsum([0] + [len(p[0]) for p in parts[:-1]])
         out = (np.concatenate([p[0] for p in parts]), np.concatenate([p[1] + np.int32(b) for p, b in zip(parts, base)]).astype(np.int32))
         return out + ((np.concatenate([p[2] for p in parts]),) if self.color else ())
@@ -754,7 +775,7 @@ class FusionVideoStream(VideoDepthStream):
         if self.follow is not None and self.follow_spill not in ("mesh", "points"):
             raise ValueError("FusionVideoStream.world_points: no chunks are kept with follow_spill=%r" % (self.follow_spill,))
         parts = [(p[0], p[-1]) for p in self.chunks]
-        parts.append(tuple(t.cpu().numpy() for t in self.volume.points(w_min=self.follow_w_min, colors=self.color)[:-1]))
+        parts.append(self._on_host(self.volume.points))
         out = (np.concatenate([p[0] for p in parts]),)
         return out + ((np.concatenate([p[-1] for p in parts]),) if self.color else ())
 
@@ -766,8 +787,8 @@ class FusionVideoStream(VideoDepthStream):
         held = self._held[-ops.CONSISTENCY_MAX_SRC:]
         src = dict(src_depth=None, src_T=None)
         if held:
-            src = dict(src_depth=self._slots["raw"], src_gate=self._slots["gate"], src_slots=[h[2] for h in held],
-                       src_T=relative_poses(pose, [h[1] for h in held]))
+            src = dict(src_depth=self._slots["raw"], src_gate=self._slots["gate"], src_slots=[h.slot for h in held],
+                       src_T=relative_poses(pose, [h.pose for h in held]))
         ops.depth_consistency(depth, intrinsics_at(self.cam, *depth.shape), rel_thr=self.consistency_rel,
                               min_views=min(self.consistency, len(held)), depth_range=self.depth_range, gate=gate,
                               gate_thr=0.0 if self.gate_thr is None else self.gate_thr, votes=self._votes, depth_out=self._filtered, **src)
@@ -776,52 +797,49 @@ class FusionVideoStream(VideoDepthStream):
 
     # ---- the history: what the last `history` frames were integrated with, so that a corrected pose can move them ----------------
 
-    def _hold(self, ref_index, pose, depth, gate, wmap, image, raw=None):
-        """Copies the frame's maps into the oldest slot (contiguous fp32 device-to-device copies: memory copies, no kernel) and
-        notes its pose; the frame that held the slot stays fused for good.  raw (consistency > 0): the regressed map before the
-        filter, with `gate` its gate — what later frames are checked against; `depth` is then the filtered map that was integrated."""
+    def _hold(self, ref_index, pose, fr, gate, raw):
+        """Copies what the frame was integrated with into the oldest slot (contiguous fp32 device-to-device copies: memory copies,
+        no kernel) and notes its pose; the frame that held the slot stays fused for good.  gate: the stream's gate of the regressed
+        map, and raw (consistency > 0): that map before the filter — what later frames are checked against; fr.depth is then the
+        filtered map that was integrated."""
+        maps = dict(depth=fr.depth, gate=gate, wmap=fr.weight, image=fr.color, raw=raw)
         if self._slots is None:                                 # once: the maps' size is the source's
-            new = lambda t: None if t is None else torch.empty((self.history,) + tuple(t.shape), dtype=torch.float32, device=self.device)
-            self._slots = dict(depth=new(depth), gate=new(gate), wmap=new(wmap), image=new(image), raw=new(raw))
+            self._slots = {key: None if t is None else torch.empty((self.history,) + tuple(t.shape), dtype=torch.float32, device=self.device)
+                           for key, t in maps.items()}
         slot = self._n_held % self.history
         self._n_held += 1
-        for key, t in (("depth", depth), ("gate", gate), ("wmap", wmap), ("image", image), ("raw", raw)):
+        for key, t in maps.items():
             if t is not None:
                 self._slots[key][slot].copy_(t)
-        self._held = [h for h in self._held if h[2] != slot] + [[ref_index, np.array(pose, dtype=np.float64), slot]]
-        if self.follow is not None:
-            self._held_shift[slot] = self.n_shifts
+        self._held = [h for h in self._held if h.slot != slot] + [_Held(ref_index, np.array(pose, dtype=np.float64), slot, self.n_shifts)]
 
     def history_poses(self):
         """[(ref_index, extM)] of the frames the history holds, oldest first: the poses they are integrated at now."""
-        return [(h[0], h[1].copy()) for h in self._held]
+        return [(h.ref_index, h.pose.copy()) for h in self._held]
 
     def _held_frame(self, ref_index, who):
-        """The history entry of a frame and what it was integrated with: (entry, depth, keywords of integrate / deintegrate)."""
+        """The history entry of a frame and what it was integrated with, its record rebuilt from the slots: (entry, depth, keywords
+        of integrate / deintegrate / reintegrate — with the depth map, a _Frame again)."""
         for h in self._held:
-            if h[0] == ref_index:
+            if h.ref_index == ref_index:
                 break
         else:
             raise KeyError("FusionVideoStream.%s: frame %r is not in the history (history=%d holds %s)"
-                           % (who, ref_index, self.history, [e[0] for e in self._held]))
-        if self.follow is not None and self._held_shift[h[2]] != self.n_shifts:
+                           % (who, ref_index, self.history, [e.ref_index for e in self._held]))
+        if h.shifts != self.n_shifts:
             raise ValueError("FusionVideoStream.%s: frame %r was integrated before the volume shifted: it cannot be taken out exactly "
                              "any more (the region that entered never held it); it still serves as a consistency source"
                              % (who, ref_index))
-        pick = lambda key: None if self._slots[key] is None else self._slots[key][h[2]]
-        kw = dict(gate=pick("gate"), gate_thr=self.gate_thr, weight=pick("wmap"), depth_range=self.depth_range)
-        if self.consistency:                                    # the held map carries its gate; the gate slot is the raw map's
-            kw.update(gate=None, gate_thr=None)
-        if self.color:
-            kw.update(color=pick("image"), color_intrinsics=intrinsics_at(self.cam, self.H, self.W), color_affine=(self.std, self.mean))
-        return h, pick("depth"), kw
+        pick = lambda key: None if self._slots[key] is None else self._slots[key][h.slot]
+        fr = self._frame(pick("depth"), pick("gate"), pick("wmap"), pick("image"))
+        return h, fr.depth, fr.fuse_kw()
 
     def _reposed(self, h, pose):
-        h[1] = np.array(pose, dtype=np.float64)
+        h.pose[...] = pose
         if self._held[-1] is h:                                 # the last frame integrated: tracking goes on from the corrected pose
-            self.last_ext = h[1].copy()
+            self.last_ext = h.pose.copy()
             if self._prev is not None:
-                self._prev = (self._prev[0], h[1].copy())
+                self._prev = (self._prev[0], h.pose.copy())
 
     def repose(self, ref_index, extM):
         """A pose correction for a frame of the history: the frame is taken out of the volume at the pose it was integrated with
@@ -833,7 +851,7 @@ class FusionVideoStream(VideoDepthStream):
         new = self._extrinsic(extM)
         if not np.all(np.isfinite(new)):
             raise ValueError("FusionVideoStream.repose: the pose is not finite")
-        done = self.volume.reintegrate(depth, h[1], new, self.cam, **kw)
+        done = self.volume.reintegrate(depth, h.pose, new, self.cam, **kw)
         self._reposed(h, new)
         return done
 
@@ -846,11 +864,9 @@ class FusionVideoStream(VideoDepthStream):
         if not self.track:
             raise ValueError("FusionVideoStream.retrack: the stream was built with track=False")
         h, depth, kw = self._held_frame(ref_index, "retrack")
-        self.volume.deintegrate(depth, h[1], self.cam, **kw)
-        photo = dict(image=kw["color"], image_affine=(self.std, self.mean)) if self.photo else {}
-        res = self.volume.track(depth, h[1], self.cam, gate=kw["gate"], gate_thr=kw["gate_thr"], depth_range=self.depth_range, **photo,
-                                **dict(self.track_kwargs, **track_kwargs))
-        pose = res.extM if res.ok else h[1]
+        self.volume.deintegrate(depth, h.pose, self.cam, **kw)
+        res = self._track(_Frame(depth, **kw), h.pose, **track_kwargs)
+        pose = res.extM if res.ok else h.pose
         self.volume.integrate(depth, pose, self.cam, **kw)
         self._reposed(h, pose)
         return res

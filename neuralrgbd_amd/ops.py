@@ -1724,16 +1724,8 @@ def tsdf_integrate(tsdf, weight, origin, voxel_size, depth, pose, intrinsics, tr
     contiguous CUDA fp32 [H,W] on the same device; pose: host [3,4] or [4,4] world -> camera, cast to float32; intrinsics =
     (fx, fy, cx, cy) at the depth map's size; depth_range = (d_near, d_far]; box: a half-open voxel box (x0, y0, z0, x1, y1, z1) or
     None for the whole grid.  Nothing is allocated, nothing synchronised."""
-    tsdf, weight, maps, pose, k, o, cbox = _tsdf_frame("tsdf_integrate", tsdf, weight, origin, depth, gate, wmap, pose, intrinsics, box)
-    dev = tsdf.device
-    Z, Y, X = tsdf.shape
-    H, W = maps[0].shape
-    with torch.cuda.device(dev):
-        rc = _lib.load().nrgbd_tsdf_integrate_f32(_p(tsdf), _p(weight), X, Y, Z, o[0], o[1], o[2], float(voxel_size), _p(maps[0]),
-                                                  _p(maps[1]), float(gate_thr), _p(maps[2]), H, W, ctypes.c_void_p(pose.ctypes.data),
-                                                  k[0], k[1], k[2], k[3], float(trunc), float(depth_range[0]), float(depth_range[1]),
-                                                  float(w_max), cbox, _stream(tsdf))
-    _lib.check(rc, "nrgbd_tsdf_integrate_f32")
+    _tsdf_integration("tsdf_integrate", tsdf, weight, origin, voxel_size, depth, pose, intrinsics, trunc, depth_range, w_max, gate, gate_thr,
+                      wmap, box)
 
 
 def _tsdf_color(color, tsdf, who):
@@ -1762,6 +1754,32 @@ def _tsdf_image(who, image, color_intrinsics, color_affine, dev):
     return image, kc, affine
 
 
+def _tsdf_integration(who, tsdf, weight, origin, voxel_size, depth, pose, intrinsics, trunc, depth_range, w_max, gate, gate_thr, wmap, box,
+                      colour=None, remove=None):
+    """The four integration wrappers' checks and call (nrgbd_<who>_f32).  colour = (color, image, color_intrinsics, color_affine): the
+    coloured entries; remove = (pose_add or None, w_floor): the reintegrate family, `pose` being pose_remove."""
+    tsdf, weight, maps, pose, k, o, cbox = _tsdf_frame(who, tsdf, weight, origin, depth, gate, wmap, pose, intrinsics, box)
+    add = None if remove is None or remove[0] is None else _tsdf_pose(who, remove[0])
+    if colour is not None:
+        color = _tsdf_color(colour[0], tsdf, who)
+        image, kc, affine = _tsdf_image(who, colour[1], colour[2], colour[3], tsdf.device)
+    host = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
+    Z, Y, X = tsdf.shape
+    H, W = maps[0].shape
+    d, g, wm = (_p(t) for t in maps)
+    args = [_p(tsdf), _p(weight)] + ([] if colour is None else [_p(color)]) + [X, Y, Z, o[0], o[1], o[2], float(voxel_size)]
+    camera = [k[0], k[1], k[2], k[3], float(trunc), float(depth_range[0]), float(depth_range[1]), float(w_max)]
+    if remove is None:      # (..., depth, gate, gate_thr, wmap, H, W, pose, fx .. w_max, box, ...)
+        args += [d, g, float(gate_thr), wm, H, W, host(pose)] + camera + [cbox]
+    else:                   # (..., depth, gate, wmap, pose_remove, pose_add, H, W, fx .. w_max, w_floor, gate_thr, box, ...)
+        args += [d, g, wm, host(pose), host(add), H, W] + camera + [float(remove[1]), float(gate_thr), cbox]
+    if colour is not None:
+        args += [_p(image), image.shape[1], image.shape[2], kc[0], kc[1], kc[2], kc[3], host(affine)]
+    with torch.cuda.device(tsdf.device):
+        rc = getattr(_lib.load(), "nrgbd_%s_f32" % who)(*args, _stream(tsdf))
+    _lib.check(rc, "nrgbd_%s_f32" % who)
+
+
 def tsdf_integrate_color(tsdf, weight, color, origin, voxel_size, depth, pose, intrinsics, trunc, image, color_intrinsics,
                          color_affine=None, depth_range=(0.0, float("inf")), w_max=64.0, gate=None, gate_thr=0.0, wmap=None, box=None):
     """tsdf_integrate with the frame's colour averaged into the volume's colour planes, one launch (nrgbd_tsdf_integrate_color_f32;
@@ -1770,20 +1788,8 @@ def tsdf_integrate_color(tsdf, weight, color, origin, voxel_size, depth, pose, i
     color: contiguous CUDA fp32 [3,Z,Y,X]; image: contiguous CUDA fp32 [3,Hc,Wc] on the same device, at a size of its own;
     color_intrinsics = (fx, fy, cx, cy) at that size; color_affine = (a [3], b [3]): the colour of a pixel is image * a + b per
     channel (None: a = 1, b = 0).  Everything else as tsdf_integrate.  Nothing is allocated, nothing synchronised."""
-    tsdf, weight, maps, pose, k, o, cbox = _tsdf_frame("tsdf_integrate_color", tsdf, weight, origin, depth, gate, wmap, pose, intrinsics, box)
-    color = _tsdf_color(color, tsdf, "tsdf_integrate_color")
-    dev = tsdf.device
-    image, kc, affine = _tsdf_image("tsdf_integrate_color", image, color_intrinsics, color_affine, dev)
-    Z, Y, X = tsdf.shape
-    H, W = maps[0].shape
-    with torch.cuda.device(dev):
-        rc = _lib.load().nrgbd_tsdf_integrate_color_f32(_p(tsdf), _p(weight), _p(color), X, Y, Z, o[0], o[1], o[2], float(voxel_size),
-                                                        _p(maps[0]), _p(maps[1]), float(gate_thr), _p(maps[2]), H, W,
-                                                        ctypes.c_void_p(pose.ctypes.data), k[0], k[1], k[2], k[3], float(trunc),
-                                                        float(depth_range[0]), float(depth_range[1]), float(w_max), cbox, _p(image),
-                                                        image.shape[1], image.shape[2], kc[0], kc[1], kc[2], kc[3],
-                                                        ctypes.c_void_p(affine.ctypes.data), _stream(tsdf))
-    _lib.check(rc, "nrgbd_tsdf_integrate_color_f32")
+    _tsdf_integration("tsdf_integrate_color", tsdf, weight, origin, voxel_size, depth, pose, intrinsics, trunc, depth_range, w_max, gate,
+                      gate_thr, wmap, box, colour=(color, image, color_intrinsics, color_affine))
 
 
 def tsdf_reintegrate(tsdf, weight, origin, voxel_size, depth, pose_remove, intrinsics, trunc, pose_add=None, w_floor=1e-3,
@@ -1794,19 +1800,8 @@ def tsdf_reintegrate(tsdf, weight, origin, voxel_size, depth, pose_remove, intri
     stay above it after the removal is fresh again (0, 0).  With pose_add the result is bit for bit that of the removal followed by
     tsdf_integrate at pose_add, with every plane read and written once.  The removal inverts the integration on voxels whose
     weight never reached w_max.  Nothing is allocated, nothing synchronised."""
-    tsdf, weight, maps, pose, k, o, cbox = _tsdf_frame("tsdf_reintegrate", tsdf, weight, origin, depth, gate, wmap, pose_remove, intrinsics,
-                                                       box)
-    add = None if pose_add is None else _tsdf_pose("tsdf_reintegrate", pose_add)
-    dev = tsdf.device
-    Z, Y, X = tsdf.shape
-    H, W = maps[0].shape
-    with torch.cuda.device(dev):
-        rc = _lib.load().nrgbd_tsdf_reintegrate_f32(_p(tsdf), _p(weight), X, Y, Z, o[0], o[1], o[2], float(voxel_size), _p(maps[0]),
-                                                    _p(maps[1]), _p(maps[2]), ctypes.c_void_p(pose.ctypes.data),
-                                                    None if add is None else ctypes.c_void_p(add.ctypes.data), H, W, k[0], k[1], k[2],
-                                                    k[3], float(trunc), float(depth_range[0]), float(depth_range[1]), float(w_max),
-                                                    float(w_floor), float(gate_thr), cbox, _stream(tsdf))
-    _lib.check(rc, "nrgbd_tsdf_reintegrate_f32")
+    _tsdf_integration("tsdf_reintegrate", tsdf, weight, origin, voxel_size, depth, pose_remove, intrinsics, trunc, depth_range, w_max, gate,
+                      gate_thr, wmap, box, remove=(pose_add, w_floor))
 
 
 def tsdf_reintegrate_color(tsdf, weight, color, origin, voxel_size, depth, pose_remove, intrinsics, trunc, image, color_intrinsics,
@@ -1815,23 +1810,8 @@ def tsdf_reintegrate_color(tsdf, weight, color, origin, voxel_size, depth, pose_
     """tsdf_reintegrate on a colour volume (nrgbd_tsdf_reintegrate_color_f32): the frame's colour leaves the colour planes with its
     distance — pass the picture, intrinsics and affine it was integrated with — and enters them again at pose_add; an emptied voxel's
     colour is 0.  The arguments are tsdf_integrate_color's and tsdf_reintegrate's.  Nothing is allocated, nothing synchronised."""
-    who = "tsdf_reintegrate_color"
-    tsdf, weight, maps, pose, k, o, cbox = _tsdf_frame(who, tsdf, weight, origin, depth, gate, wmap, pose_remove, intrinsics, box)
-    add = None if pose_add is None else _tsdf_pose(who, pose_add)
-    color = _tsdf_color(color, tsdf, who)
-    dev = tsdf.device
-    image, kc, affine = _tsdf_image(who, image, color_intrinsics, color_affine, dev)
-    Z, Y, X = tsdf.shape
-    H, W = maps[0].shape
-    with torch.cuda.device(dev):
-        rc = _lib.load().nrgbd_tsdf_reintegrate_color_f32(_p(tsdf), _p(weight), _p(color), X, Y, Z, o[0], o[1], o[2], float(voxel_size),
-                                                          _p(maps[0]), _p(maps[1]), _p(maps[2]), ctypes.c_void_p(pose.ctypes.data),
-                                                          None if add is None else ctypes.c_void_p(add.ctypes.data), H, W, k[0], k[1],
-                                                          k[2], k[3], float(trunc), float(depth_range[0]), float(depth_range[1]),
-                                                          float(w_max), float(w_floor), float(gate_thr), cbox, _p(image), image.shape[1],
-                                                          image.shape[2], kc[0], kc[1], kc[2], kc[3], ctypes.c_void_p(affine.ctypes.data),
-                                                          _stream(tsdf))
-    _lib.check(rc, "nrgbd_tsdf_reintegrate_color_f32")
+    _tsdf_integration("tsdf_reintegrate_color", tsdf, weight, origin, voxel_size, depth, pose_remove, intrinsics, trunc, depth_range, w_max,
+                      gate, gate_thr, wmap, box, colour=(color, image, color_intrinsics, color_affine), remove=(pose_add, w_floor))
 
 
 def tsdf_shift(src, dst, shift, spill=False):
@@ -1912,19 +1892,14 @@ def tsdf_extract_points(tsdf, weight, origin, voxel_size, w_min, workspace, poin
     colors = _tsdf_colors(colors, points, color, dev, "tsdf_extract_points")
     o = _vec3(origin, "tsdf_extract_points: origin")
     Z, Y, X = tsdf.shape
-    if color is not None:
-        with torch.cuda.device(dev):
-            rc = _lib.load().nrgbd_tsdf_extract_points_color(_p(tsdf), _p(weight), _p(color), X, Y, Z, o[0], o[1], o[2], float(voxel_size),
-                                                             float(w_min), _p(workspace), workspace.numel() * workspace.element_size(),
-                                                             _p(points if capacity else None), _p(colors if capacity else None),
-                                                             capacity, _p(counts), _stream(tsdf))
-        _lib.check(rc, "nrgbd_tsdf_extract_points_color")
-        return
+    coloured = color is not None                                    # the coloured entry: `color` after weight, `colors` after points
+    name = "nrgbd_tsdf_extract_points_color" if coloured else "nrgbd_tsdf_extract_points"
+    args = ([_p(tsdf), _p(weight)] + [_p(color)] * coloured
+            + [X, Y, Z, o[0], o[1], o[2], float(voxel_size), float(w_min), _p(workspace), workspace.numel() * workspace.element_size(),
+               _p(points if capacity else None)] + [_p(colors if capacity else None)] * coloured + [capacity, _p(counts), _stream(tsdf)])
     with torch.cuda.device(dev):
-        rc = _lib.load().nrgbd_tsdf_extract_points(_p(tsdf), _p(weight), X, Y, Z, o[0], o[1], o[2], float(voxel_size), float(w_min),
-                                                   _p(workspace), workspace.numel() * workspace.element_size(),
-                                                   _p(points if capacity else None), capacity, _p(counts), _stream(tsdf))
-    _lib.check(rc, "nrgbd_tsdf_extract_points")
+        rc = getattr(_lib.load(), name)(*args)
+    _lib.check(rc, name)
 
 
 def tsdf_mesh_workspace(X, Y, Z):
@@ -1966,20 +1941,15 @@ def tsdf_extract_mesh(tsdf, weight, origin, voxel_size, w_min, workspace, vertic
     colors = _tsdf_colors(colors, vertices, color, dev, "tsdf_extract_mesh")
     o = _vec3(origin, "tsdf_extract_mesh: origin")
     Z, Y, X = tsdf.shape
-    if color is not None:
-        with torch.cuda.device(dev):
-            rc = _lib.load().nrgbd_tsdf_extract_mesh_color(_p(tsdf), _p(weight), _p(color), X, Y, Z, o[0], o[1], o[2], float(voxel_size),
-                                                           float(w_min), _p(workspace), workspace.numel() * workspace.element_size(),
-                                                           _p(vertices if caps[0] else None), _p(colors if caps[0] else None), caps[0],
-                                                           _p(faces if caps[1] else None), caps[1], _p(counts), _stream(tsdf))
-        _lib.check(rc, "nrgbd_tsdf_extract_mesh_color")
-        return
+    coloured = color is not None                                    # the coloured entry: `color` after weight, `colors` after vertices
+    name = "nrgbd_tsdf_extract_mesh_color" if coloured else "nrgbd_tsdf_extract_mesh"
+    args = ([_p(tsdf), _p(weight)] + [_p(color)] * coloured
+            + [X, Y, Z, o[0], o[1], o[2], float(voxel_size), float(w_min), _p(workspace), workspace.numel() * workspace.element_size(),
+               _p(vertices if caps[0] else None)] + [_p(colors if caps[0] else None)] * coloured
+            + [caps[0], _p(faces if caps[1] else None), caps[1], _p(counts), _stream(tsdf)])
     with torch.cuda.device(dev):
-        rc = _lib.load().nrgbd_tsdf_extract_mesh(_p(tsdf), _p(weight), X, Y, Z, o[0], o[1], o[2], float(voxel_size), float(w_min),
-                                                 _p(workspace), workspace.numel() * workspace.element_size(),
-                                                 _p(vertices if caps[0] else None), caps[0], _p(faces if caps[1] else None), caps[1],
-                                                 _p(counts), _stream(tsdf))
-    _lib.check(rc, "nrgbd_tsdf_extract_mesh")
+        rc = getattr(_lib.load(), name)(*args)
+    _lib.check(rc, name)
 
 
 TSDF_RAYCAST_TILE = _lib.TSDF_RAYCAST_TILE      # side of the pixel tile a workgroup of nrgbd_tsdf_raycast_f32 owns (a wave: 8 x 8)
@@ -2011,14 +1981,7 @@ def tsdf_raycast(tsdf, weight, origin, voxel_size, pose, intrinsics, size, depth
     if rgb:
         color = _tsdf_color(color, tsdf, "tsdf_raycast")
     H, W = (int(n) for n in size)
-    if isinstance(pose, torch.Tensor):
-        if pose.is_cuda:
-            raise ValueError("tsdf_raycast: pose is a host matrix (it is read at the call)")
-        pose = pose.detach().numpy()
-    pose = np.asarray(pose)
-    if pose.shape not in ((3, 4), (4, 4)):
-        raise ValueError("tsdf_raycast: pose is [3,4] or [4,4] world -> camera, got %s" % (pose.shape,))
-    pose = np.ascontiguousarray(pose[:3, :4], dtype=np.float32)
+    pose = _tsdf_pose("tsdf_raycast", pose)
     centre = np.ascontiguousarray(camera_centre(pose))
     k = tuple(float(x) for x in intrinsics)
     if len(k) != 4:
@@ -2038,28 +2001,18 @@ def tsdf_raycast(tsdf, weight, origin, voxel_size, pose, intrinsics, size, depth
             t = _need(t, nm, shape, strided=True)
             if t.device != dev or not t.is_contiguous():
                 raise ValueError("tsdf_raycast: %s must be contiguous and on %s" % (nm, dev))
-    depth, normal = outs[0], (outs[1] if normals else None)
+    normal = outs[1] if normals else None
     Z, Y, X = tsdf.shape
-    if rgb:
-        return _tsdf_raycast_color(tsdf, weight, color, X, Y, Z, o, voxel_size, pose, centre, k, H, W, depth_range, w_min, step, outs, normal)
+    name = "nrgbd_tsdf_raycast_color_f32" if rgb else "nrgbd_tsdf_raycast_f32"        # `color` after weight, the rgb output after normal
+    rgb = bool(rgb)
+    args = ([_p(tsdf), _p(weight)] + [_p(color)] * rgb
+            + [X, Y, Z, o[0], o[1], o[2], float(voxel_size), ctypes.c_void_p(pose.ctypes.data), ctypes.c_void_p(centre.ctypes.data), k[0],
+               k[1], k[2], k[3], H, W, float(depth_range[0]), float(depth_range[1]), float(w_min),
+               float(voxel_size if step is None else step), _p(outs[0]), _p(normal)] + [_p(outs[-1])] * rgb + [_stream(tsdf)])
     with torch.cuda.device(dev):
-        rc = _lib.load().nrgbd_tsdf_raycast_f32(_p(tsdf), _p(weight), X, Y, Z, o[0], o[1], o[2], float(voxel_size),
-                                                ctypes.c_void_p(pose.ctypes.data), ctypes.c_void_p(centre.ctypes.data), k[0], k[1], k[2],
-                                                k[3], H, W, float(depth_range[0]), float(depth_range[1]), float(w_min),
-                                                float(voxel_size if step is None else step), _p(depth), _p(normal), _stream(tsdf))
-    _lib.check(rc, "nrgbd_tsdf_raycast_f32")
-    return (depth, normal) if normals else depth
-
-
-def _tsdf_raycast_color(tsdf, weight, color, X, Y, Z, o, voxel_size, pose, centre, k, H, W, depth_range, w_min, step, outs, normal):
-    with torch.cuda.device(tsdf.device):
-        rc = _lib.load().nrgbd_tsdf_raycast_color_f32(_p(tsdf), _p(weight), _p(color), X, Y, Z, o[0], o[1], o[2], float(voxel_size),
-                                                      ctypes.c_void_p(pose.ctypes.data), ctypes.c_void_p(centre.ctypes.data), k[0], k[1],
-                                                      k[2], k[3], H, W, float(depth_range[0]), float(depth_range[1]), float(w_min),
-                                                      float(voxel_size if step is None else step), _p(outs[0]), _p(normal), _p(outs[-1]),
-                                                      _stream(tsdf))
-    _lib.check(rc, "nrgbd_tsdf_raycast_color_f32")
-    return tuple(outs)
+        rc = getattr(_lib.load(), name)(*args)
+    _lib.check(rc, name)
+    return tuple(outs) if len(outs) > 1 else outs[0]
 
 
 # ---- frame-to-model tracking (icp.hip; neuralrgbd_amd/tracking.py) --------------------------------------------------------------

@@ -262,7 +262,7 @@ def test_the_history_across_a_shift():
                         use_graph=False, **FOLLOW)
     assert fs.n_shifts >= 2
     held = [i for i, _ in fs.history_poses()]
-    before = [i for i in held if fs._held_shift[[h[2] for h in fs._held if h[0] == i][0]] != fs.n_shifts]
+    before = [i for i in held if [h.shifts for h in fs._held if h.ref_index == i][0] != fs.n_shifts]
     after = [i for i in held if i not in before]
     print("[follow] history: held %s, integrated before the last shift %s" % (held, before))
     assert before and after == held[len(before):]
@@ -285,7 +285,7 @@ def test_a_pre_shift_frame_is_still_a_consistency_source():
     order = sorted(maps)
     last = order[-1]
     sources = order[max(0, len(order) - 1 - fcons.HISTORY):-1]       # the frames held when the last one came out
-    assert fs.n_shifts >= 2 and fs._held_shift[[h[2] for h in fs._held if h[0] == sources[1]][0]] < fs.n_shifts
+    assert fs.n_shifts >= 2 and [h.shifts for h in fs._held if h.ref_index == sources[1]][0] < fs.n_shifts
     want = fcons._hand_filter(maps, last, sources, {i: extMs[i] for i in order}, 0.0)[0]
     assert torch.equal(fs.last_votes.view(torch.int32), want.view(torch.int32)) and float(want.max()) >= 1
 
@@ -298,7 +298,7 @@ def test_follow_none_is_the_stream_without_the_argument():
         fs, outs = fsn._stream(R, frames, extMs, vol, use_graph=False, **extra)
         fsn._same_maps(outs, maps)
         assert fs.follow is None and fs.n_shifts == 0 and fs.chunks == [] and vol._spare is None and vol.offset == (0, 0, 0)
-        assert vol.origin == tuple(fsn.ORIGIN) and fs._held_shift == {}
+        assert vol.origin == tuple(fsn.ORIGIN) and [h.shifts for h in fs._held if h.shifts] == []
         runs.append(vol)
     for vol in runs[1:]:
         frp._same_buf(vol, runs[0])
