@@ -70,7 +70,8 @@ extern "C" {
  * fused volume), and for nrgbd_icp_terms_photo_f32 (the same with a photometric term against the volume's rendered colour), and for
  * nrgbd_tsdf_reintegrate_f32 and nrgbd_tsdf_reintegrate_color_f32 (a fused frame taken out of the volume and put back at a corrected
  * pose), and for nrgbd_depth_consistency_f32 (a depth map cross-checked against other views' maps before it is fused), and for nrgbd_tsdf_shift_f32
- * (the TSDF volume moved by whole voxels so that it follows the camera, with the leaving part handed out). */
+ * (the TSDF volume moved by whole voxels so that it follows the camera, with the leaving part handed out), and for
+ * nrgbd_tsdf_blocks_gather_f32 and nrgbd_tsdf_blocks_scatter_f32 (8^3 voxel blocks paged out of the moving volume and back in). */
 #define NRGBD_INTERFACE_VERSION "0.10"
 const char* nrgbd_version(void);
 const char* nrgbd_strerror(int code);
@@ -1434,6 +1435,48 @@ int nrgbd_depth_consistency_f32(const float* depth, const float* gate, float gat
  *   else runs the element form: the same bits.
  */
 int nrgbd_tsdf_shift_f32(float* src, float* dst, int planes, int X, int Y, int Z, int sx, int sy, int sz, int spill, void* stream);
+
+/*
+ * The moving TSDF volume paged (tsdf_page.hip; neuralrgbd_amd/fusion.py: BlockStore, TSDFVolume.shift(store=...), paged_extract,
+ * FusionVideoStream(follow_spill="page")): blocks of NRGBD_TSDF_BLOCK^3 voxels copied between a volume and a dense staging tensor, so
+ * that what leaves the window can be kept on the host and put back, bit for bit, when the window covers it again — the re-entry of
+ * Kintinuous and the streaming of voxel hashing.  No counterpart in the reference.  Pure copies: no arithmetic touches a value, so NaN
+ * payloads, signed zeros and denormals come through bit for bit; no atomics, no workspace, the same bits in every run.  One launch
+ * each on the caller's stream, capturable; one workgroup per block, the blocks on the grid's x dimension.
+ *
+ * nrgbd_tsdf_blocks_gather_f32 — no counterpart in the reference: n blocks read out of a volume, with a flag per block.
+ *   vol          device fp32 [planes][Z][Y][X]: planes = 2 (tsdf, weight) or 5 (tsdf, weight, r, g, b), as nrgbd_tsdf_shift_f32 takes it;
+ *                only read
+ *   origins      device int32 [n][3]: (ox, oy, oz) of block b in grid voxels, any integers with |o| <= 2^30; a block need not be aligned
+ *                to anything and may lie partly or wholly outside the grid
+ *   n            the number of blocks, 0 <= n <= NRGBD_TSDF_MAX_BLOCKS; n = 0 launches nothing (origins, blocks may then be NULL)
+ *   blocks       device fp32 [n][planes][8][8][8], indexed (z, y, x) inside a block, 16-byte aligned; every word is written:
+ *     blocks[b][p][k][j][i] = vol[p][oz + k][oy + j][ox + i], the bits unchanged, where 0 <= ox + i < X, 0 <= oy + j < Y and
+ *     0 <= oz + k < Z; else +0.0f, and nothing is loaded
+ *   nonempty     device int32 [n] or NULL: nonempty[b] = 1 where some in-grid word of some plane of block b has a non-zero bit pattern
+ *                (-0.0 and NaN count), else 0.  A block whose flag is 0 holds +0.0f throughout — what a region that enters after a
+ *                shift holds —, so it can be dropped without loss
+ *   errors       NRGBD_E_NULL: vol NULL, or origins or blocks NULL with n != 0;  NRGBD_E_SHAPE: planes not 2 or 5, a dimension <= 0 or
+ *                X Y Z > 2^31, n < 0 or n > NRGBD_TSDF_MAX_BLOCKS;  NRGBD_E_ARG: blocks not 16-byte aligned.  Checked in this order,
+ *                before anything touches the device.
+ *   The vector form (16-byte accesses of the volume) needs X % 4 == 0, a 16-byte aligned vol and, per block, ox % 4 == 0; anything
+ *   else runs the element form: the same bits.
+ *
+ * nrgbd_tsdf_blocks_scatter_f32 — no counterpart in the reference: the inverse — n blocks written into a volume.
+ *   vol          device fp32 [planes][Z][Y][X], as above: vol[p][oz + k][oy + j][ox + i] = blocks[b][p][k][j][i], the bits unchanged,
+ *                for every voxel of every block that lies in the grid; the part of a block outside the grid is ignored, and every
+ *                voxel outside all the blocks keeps its bits
+ *   origins n    as above.  The blocks of one call must not overlap inside the grid (two origins closer than 8 along all three
+ *                axes): which block's words such a voxel ends up with is not defined.  The caller's contract; not checked here
+ *   blocks       device fp32 [n][planes][8][8][8], 16-byte aligned; only read
+ *   errors       as above
+ */
+#define NRGBD_TSDF_BLOCK        8
+#define NRGBD_TSDF_MAX_BLOCKS   (1 << 20)
+int nrgbd_tsdf_blocks_gather_f32(const float* vol, int planes, int X, int Y, int Z, const int* origins, int n, float* blocks,
+                                 int* nonempty, void* stream);
+int nrgbd_tsdf_blocks_scatter_f32(float* vol, int planes, int X, int Y, int Z, const int* origins, int n, const float* blocks,
+                                  void* stream);
 
 #ifdef __cplusplus
 }

@@ -168,6 +168,8 @@ SIGNATURES = {
     "nrgbd_icp_update": (_I, [_P, _P, _I, _P, _I, _c.c_longlong, _D, _P, _P]),
     "nrgbd_depth_consistency_f32": (_I, [_P, _P, _F, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P, _L, _P, _P, _I, _F, _I, _P, _P, _P]),
     "nrgbd_tsdf_shift_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "nrgbd_tsdf_blocks_gather_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
+    "nrgbd_tsdf_blocks_scatter_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P]),
     "nrgbd_nhwc_stats_workgroups": (_I, [_L]),
     "nrgbd_nhwc_stats": (_I, [_P, _L, _I, _P, _P]),
     "nrgbd_nhwc_act": (_I, [_P, _P, _I, _P, _P, _I, _P, _L, _I, _I, _P]),

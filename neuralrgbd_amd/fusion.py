@@ -33,8 +33,13 @@ conventions (lattice, projection, update rule, crossings) are written out in inc
     what enters is empty, what leaves is handed out as a spill volume), `follow_shift` says when and by how much from a camera pose,
     and `FusionVideoStream(follow=distance)` keeps the volume around the camera's focus, extracts every spill (`chunks`) and
     stitches them with the live mesh (`world_mesh`, `world_points`) — the scheme of Kintinuous and large-scale KinFu.  Not built:
-    exact `repose` of frames integrated before a shift (it would clip the removal to the region that has existed since), swapping
-    spilled slabs back in when the camera returns, circular addressing in place of the copy, a sparse block volume;
+    exact `repose` of frames integrated before a shift (it would clip the removal to the region that has existed since), circular
+    addressing in place of the copy, a sparse block volume;
+  * paging: `TSDFVolume.shift(store=BlockStore)` keeps what leaves as 8^3 voxel blocks on the host (ops.tsdf_blocks_gather) and puts
+    back, bit for bit, what the store holds of the region that enters (ops.tsdf_blocks_scatter), so a camera that returns finds the
+    model it left; `paged_extract` reads the whole world — live window and store — as one mesh or point set, tile by tile, and
+    `FusionVideoStream(follow_spill="page")` does both for a stream.  Not built: compressed or device-resident blocks, prefetch ahead
+    of the motion, exact `repose` across shifts;
   * `fuse_sequence`, `save_ply`.
 """
 import math
@@ -139,6 +144,168 @@ def follow_shift(extM, volume, distance, margin=0.25, step=8):
     return tuple(out)
 
 
+BLOCK = ops.TSDF_BLOCK                                              # voxels along the edge of a paged block
+
+
+def _block_keys(keys):
+    """Block indices as an int64 array [n,3]."""
+    k = np.asarray(list(keys) if not isinstance(keys, np.ndarray) else keys, dtype=np.int64)
+    return k.reshape(-1, 3)
+
+
+class BlockStore:
+    """What a paged volume keeps on the host: a dict from the world block index (bx, by, bz) — any integers, negative ones too; the
+    block covers the world voxels 8 b .. 8 b + 7 of the volume's construction lattice — to the block's [planes,8,8,8] fp32 words,
+    indexed (plane, z, y, x).  Pure numpy: no GPU is needed to fill, query, save or load one.  `n_put`, `n_dropped` and `n_taken`
+    count, over the store's life, the blocks `put` kept, the all-zero ones it dropped and the ones `take` handed back."""
+
+    def __init__(self, planes, block=BLOCK):
+        if planes not in (2, 5):
+            raise ValueError("BlockStore: planes is 2 (tsdf, weight) or 5 (with r, g, b), got %r" % (planes,))
+        if block != BLOCK:
+            raise ValueError("BlockStore: blocks are %d voxels wide (NRGBD_TSDF_BLOCK), got %r" % (BLOCK, block))
+        self.planes, self.block = int(planes), BLOCK
+        self._blocks = {}
+        self.n_put = self.n_dropped = self.n_taken = 0
+
+    def _shape(self):
+        return (self.planes,) + (self.block,) * 3
+
+    def put(self, keys, data, nonempty=None):
+        """keys [n,3] block indices, data [n,planes,8,8,8] fp32, nonempty [n] (ops.tsdf_blocks_gather's flags; None: every block
+        counts): the flagged blocks are copied in, the others — +0.0 throughout, what an entering region holds anyway — dropped.
+        A key the store already holds is refused (ValueError) before anything is stored: a block is paged out once before it is
+        paged in again.  Returns the number of blocks kept."""
+        keys = _block_keys(keys)
+        data = np.asarray(data)
+        if data.dtype != np.float32 or tuple(data.shape) != (len(keys),) + self._shape():
+            raise ValueError("BlockStore.put: data is fp32 [%d,%s], got %s %s" % (len(keys), ",".join(str(n) for n in self._shape()),
+                                                                                  data.dtype, data.shape))
+        flags = np.ones(len(keys), bool) if nonempty is None else np.asarray(nonempty).reshape(-1) != 0
+        if len(flags) != len(keys):
+            raise ValueError("BlockStore.put: %d flags for %d blocks" % (len(flags), len(keys)))
+        rows = np.flatnonzero(flags)
+        kept = list(zip(map(tuple, keys[rows].tolist()), rows.tolist()))
+        names = [k for k, _ in kept]
+        if len(set(names)) != len(names) or any(k in self._blocks for k in names):
+            raise ValueError("BlockStore.put: a block is already in the store (%s)"
+                             % ([k for k in names if k in self._blocks or names.count(k) > 1][:4],))
+        for k, b in kept:
+            self._blocks[k] = data[b].copy()
+        self.n_put += len(kept)
+        self.n_dropped += len(keys) - len(kept)
+        return len(kept)
+
+    def get(self, keys):
+        """(found [m,3] int64, data [m,planes,8,8,8] fp32): the blocks of `keys` the store holds, in `keys`' order, copied."""
+        found = [k for k in map(tuple, _block_keys(keys).tolist()) if k in self._blocks]
+        data = np.empty((len(found),) + self._shape(), np.float32)
+        for b, k in enumerate(found):
+            data[b] = self._blocks[k]
+        return np.asarray(found, dtype=np.int64).reshape(-1, 3), data
+
+    def take(self, keys):
+        """`get`, and the blocks it returns leave the store."""
+        found, data = self.get(keys)
+        for k in map(tuple, found.tolist()):
+            del self._blocks[k]
+        self.n_taken += len(found)
+        return found, data
+
+    def keys(self):
+        """The block indices held, as a sorted list of (bx, by, bz)."""
+        return sorted(self._blocks)
+
+    def __len__(self):
+        return len(self._blocks)
+
+    def __contains__(self, key):
+        return tuple(int(v) for v in key) in self._blocks
+
+    @property
+    def nbytes(self):
+        return len(self._blocks) * self.planes * self.block ** 3 * 4
+
+    def bounds(self):
+        """((bx0, by0, bz0), (bx1, by1, bz1)): the half-open box of block indices held; None for an empty store."""
+        if not self._blocks:
+            return None
+        k = np.asarray(list(self._blocks), dtype=np.int64)
+        return tuple(int(v) for v in k.min(axis=0)), tuple(int(v) + 1 for v in k.max(axis=0))
+
+    def clear(self):
+        self._blocks.clear()
+
+    def save(self, path):
+        """One .npz: the keys [n,3] int64 in sorted order, the blocks [n,planes,8,8,8] as their int32 bit patterns, planes and the
+        block width.  `load` gives every word back bit for bit (NaN payloads included)."""
+        found, data = self.get(self.keys())
+        with open(path, "wb") as f:
+            np.savez(f, keys=found, bits=data.view(np.int32), planes=np.int64(self.planes), block=np.int64(self.block))
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            out = cls(int(z["planes"]), int(z["block"]))
+            out.put(z["keys"], np.ascontiguousarray(z["bits"]).view(np.float32))
+        out.n_put = 0                                               # the counters count paging, not loading
+        return out
+
+
+def _window_blocks(offset, dims):
+    """The world block indices of the window [offset, offset + dims) — both multiples of 8 —: (lo [3], hi [3]) half-open."""
+    lo = np.asarray(offset, dtype=np.int64) // BLOCK
+    return lo, lo + np.asarray(dims, dtype=np.int64) // BLOCK
+
+
+def _box_keys(lo, hi):
+    """Every block index of the half-open box, [n,3] int64 in ascending (z, y, x) order."""
+    if any(h <= l for l, h in zip(lo, hi)):
+        return np.zeros((0, 3), np.int64)
+    z, y, x = np.meshgrid(*(np.arange(lo[k], hi[k], dtype=np.int64) for k in (2, 1, 0)), indexing="ij")
+    return np.stack([x.ravel(), y.ravel(), z.ravel()], axis=1)
+
+
+def _outside(keys, lo, hi):
+    """The rows of keys [n,3] that do not lie in the half-open box."""
+    return keys[~((keys >= lo) & (keys < hi)).all(axis=1)]
+
+
+def _in_calls(entry, buf, origins, blocks, *flags):
+    """ops.tsdf_blocks_gather / _scatter over any number of blocks: calls of at most NRGBD_TSDF_MAX_BLOCKS."""
+    for at in range(0, len(origins), ops.TSDF_MAX_BLOCKS):
+        part = slice(at, min(len(origins), at + ops.TSDF_MAX_BLOCKS))
+        entry(buf, origins[part], blocks[part], *(f[part] for f in flags))
+
+
+class _Staging:
+    """Device staging for paged blocks — [capacity,planes,8,8,8] fp32 and the int32 flags —, allocated once and grown only when a
+    call needs more; on a GPU also the pinned host mirror the blocks are read back through."""
+
+    def __init__(self, planes, device):
+        self.planes, self.device = planes, device
+        self.blocks = self.flags = self._host = None
+
+    def need(self, n):
+        if self.blocks is None or self.blocks.shape[0] < n:
+            self.blocks = torch.empty((n, self.planes) + (BLOCK,) * 3, dtype=torch.float32, device=self.device)
+            self.flags = torch.empty(n, dtype=torch.int32, device=self.device)
+            self._host = None
+        return self.blocks, self.flags
+
+    def to_host(self, n):
+        """(blocks [n,...], flags [n]) as numpy arrays, views of buffers the next call overwrites; the one synchronisation."""
+        if self.device.type != "cuda":
+            return self.blocks[:n].numpy(), self.flags[:n].numpy()
+        if self._host is None:
+            self._host = (torch.empty(self.blocks.shape, dtype=torch.float32, pin_memory=True),
+                          torch.empty(self.flags.shape, dtype=torch.int32, pin_memory=True))
+        for h, d in zip(self._host, (self.blocks, self.flags)):
+            h[:n].copy_(d[:n], non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        return self._host[0][:n].numpy(), self._host[1][:n].numpy()
+
+
 class TSDFVolume:
     """A dense TSDF volume on the device: `tsdf` and `weight`, fp32 [Z,Y,X]; lattice point (ix, iy, iz) lies at
     origin + voxel_size (ix, iy, iz).  color=True: also `color`, fp32 [3,Z,Y,X] (r, g, b), the running average of the colours of
@@ -166,6 +333,8 @@ class TSDFVolume:
         self._spare = None                                          # the second buffer, allocated at the first shift
         self._generation = 0                                        # counts the shifts: a spill volume is valid for one
         self._parent = None                                         # a spill volume: (the volume it came from, its generation then)
+        self._page_out = self._page_in = None                       # block staging, allocated at the first shift with a store
+        self._page_scratch = None                                   # paged_extract's tile volume, allocated at its first call
         self._point(self._buf)
         self._scratch()
 
@@ -191,7 +360,7 @@ class TSDFVolume:
         self._live("reset")
         self._buf.zero_()
 
-    def shift(self, voxels, spill=False):
+    def shift(self, voxels, spill=False, store=None):
         """The volume moved by voxels = (sx, sy, sz) whole voxels, one launch (ops.tsdf_shift): `offset` grows by it, `origin` becomes
         origin0 + voxel_size * offset (formed in float64 from the construction origin: rounding does not accumulate over many
         shifts), the voxels that stay keep their bits at their new indices, the region that enters is empty, and what leaves is gone
@@ -203,7 +372,19 @@ class TSDFVolume:
         The volume keeps two buffers of the same shape and the launch copies from one into the other, then they swap roles: the
         second is allocated at the first shift (the one allocation; a volume that is never shifted never has it).  `tsdf`, `weight`
         and `color` are re-pointed: tensors fetched from these attributes BEFORE a shift are the spill buffer afterwards.
-        A zero shift launches nothing and returns None; without spill the result is None.  Synchronises nothing."""
+        A zero shift launches nothing and returns None; without spill the result is None.  Synchronises nothing.
+        store=BlockStore: the shift is paged.  The volume is seen as 8^3 voxel blocks; the world index of the block at grid voxel o
+        is (offset + o) / 8, on the construction lattice, so every dimension, every component of `voxels` and `offset` must be
+        multiples of 8, the store's planes the volume's, and spill False (ValueError otherwise).  After the shift launch — the same
+        launch, the old buffer intact — the blocks of the old window that are not in the new one are gathered out of the old
+        buffer (ops.tsdf_blocks_gather; the set difference of block indices is formed on the host, which also covers a shift past
+        the whole grid), whatever the store holds of the blocks of the new window that were not in the old one is taken from it
+        and scattered into the new buffer (ops.tsdf_blocks_scatter), and the gathered blocks and their flags are copied to the host
+        and `put`: a block that holds nothing but +0.0 is dropped, as an entering region is +0.0 anyway.  Everything runs on the
+        current stream; the read-back synchronises once per shift, as the mesh spill does.  The staging tensors are allocated at
+        the first such shift and grown only when a larger one needs it.  Returns None.  What the live window and the store hold
+        together is then, bit for bit, what an unbounded static volume would hold, as long as no frame updates voxels outside
+        the window."""
         self._live("shift")
         try:
             s = tuple(int(v) for v in voxels)
@@ -212,27 +393,62 @@ class TSDFVolume:
             whole = False
         if not whole:
             raise ValueError("TSDFVolume.shift: voxels = (sx, sy, sz), whole voxels; got %r" % (voxels,))
+        if store is not None:
+            self._paged("shift", store)
+            if spill:
+                raise ValueError("TSDFVolume.shift: spill=True hands the leaving part out as a volume, store= keeps it as blocks: one of the two")
+            if any(v % BLOCK for v in s):
+                raise ValueError("TSDFVolume.shift: with a store the shift is whole blocks of %d voxels, got %r" % (BLOCK, s))
         if s == (0, 0, 0):
             return None
         if self._spare is None:
             self._spare = torch.empty_like(self._buf)
         ops.tsdf_shift(self._buf, self._spare, s, spill=spill)
-        old_buf, old_origin = self._buf, self.origin
+        old_buf, old_origin, old_offset = self._buf, self.origin, self.offset
         self._point(self._spare)
         self._spare = old_buf
         self._generation += 1                                       # whatever spill volume viewed the spare is stale from here
         self.offset = tuple(o + v for o, v in zip(self.offset, s))
         self.origin = tuple(o + self.voxel_size * k for o, k in zip(self._origin0, self.offset))       # Python floats: float64
+        if store is not None:
+            self._page(store, old_buf, old_offset)
         if not spill:
             return None
         out = object.__new__(TSDFVolume)
         out.dims, out.voxel_size, out.trunc, out.w_max, out.device = self.dims, self.voxel_size, self.trunc, self.w_max, self.device
         out.origin = out._origin0 = old_origin
         out.offset, out._spare, out._generation = (0, 0, 0), None, 0
+        out._page_out = out._page_in = out._page_scratch = None
         out._parent = (self, self._generation)
         out._point(old_buf)
         out._scratch()
         return out
+
+    def _paged(self, who, store):
+        """The conditions of a paged volume: the store's planes, and the window on the block lattice."""
+        if not isinstance(store, BlockStore) or store.planes != self._buf.shape[0]:
+            raise ValueError("TSDFVolume.%s: store is a BlockStore of %d planes, got %r" % (who, self._buf.shape[0], getattr(
+                store, "planes", store)))
+        if any(n % BLOCK for n in self.dims) or any(o % BLOCK for o in self.offset):
+            raise ValueError("TSDFVolume.%s: a paged volume's dims %s and offset %s are multiples of %d voxels"
+                             % (who, self.dims, self.offset, BLOCK))
+
+    def _page(self, store, old_buf, old_offset):
+        """After a shift's launch: the blocks that left, out of the old buffer into `store`; the blocks that entered, out of it."""
+        old_lo, old_hi = _window_blocks(old_offset, self.dims)
+        new_lo, new_hi = _window_blocks(self.offset, self.dims)
+        leaving = _outside(_box_keys(old_lo, old_hi), new_lo, new_hi)
+        entering = _outside(_box_keys(new_lo, new_hi), old_lo, old_hi)
+        if self._page_out is None:
+            self._page_out, self._page_in = _Staging(self._buf.shape[0], self.device), _Staging(self._buf.shape[0], self.device)
+        blocks, flags = self._page_out.need(len(leaving))
+        _in_calls(ops.tsdf_blocks_gather, old_buf, leaving * BLOCK - np.asarray(old_offset, np.int64), blocks, flags)
+        found, data = store.take(entering)
+        if len(found):
+            staged = self._page_in.need(len(found))[0]
+            staged[:len(found)].copy_(torch.from_numpy(data))
+            _in_calls(ops.tsdf_blocks_scatter, self._buf, found * BLOCK - np.asarray(self.offset, np.int64), staged)
+        store.put(leaving, *self._page_out.to_host(len(leaving)))
 
     def _frame(self, who, depth, intrinsics, gate, gate_thr, weight, color, color_intrinsics, color_affine):
         """What integrate, deintegrate and reintegrate check and prepare alike: -> (depth [H,W], gate, weight, (fx, fy, cx, cy),
@@ -491,6 +707,69 @@ def filter_depth(depth, pose, sources, poses, intrinsics, rel=0.01, min_views=1,
     return got[1], got[0]
 
 
+def paged_extract(volume, store, what="mesh", w_min=1., colors=False):
+    """The whole world of a paged volume — the live window and what `store` holds — as one mesh or point set on the host:
+    (vertices [n,3] fp32, faces [m,3] int32[, colors [n,3] fp32]) for what='mesh', (points [n,3] fp32[, colors]) for 'points', numpy
+    arrays.  The world's voxel bounds — the window and the store's blocks — are cut into tiles of volume.dims voxels whose origins
+    are dims - 1 apart, so that every mesh cell (eight neighbouring voxels) lies in exactly one tile; the tiles are visited in
+    ascending (z, y, x) order.  A tile is assembled in one scratch TSDFVolume of the volume's shape (allocated at the first call,
+    zeroed per tile): the store's blocks that touch it go host -> staging, the live window's by ops.tsdf_blocks_gather from the live
+    buffer, and one ops.tsdf_blocks_scatter writes both — tile origins are not block-aligned, so the blocks are clipped at the tile's
+    faces.  The tile is then extracted with TSDFVolume.mesh / points at w_min, and the parts are concatenated with each part's face
+    rows offset by the vertices before it, as FusionVideoStream.world_mesh does for chunks.  A tile that no block touches is
+    skipped.  The vertices on a face two tiles share exist in both, each part being a mesh of its own; a point set holds such a
+    crossing twice.  A vertex is origin + voxel_size (i + q) with the TILE's origin and index: the same surface comes out within a
+    few ulp of, not bit for bit as, one large volume's.  Neither the store nor the live volume is modified.  Synchronises (every
+    extraction reads its counts back)."""
+    if what not in ("mesh", "points"):
+        raise ValueError("paged_extract: what is 'mesh' or 'points', got %r" % (what,))
+    volume._live("paged_extract")
+    volume._paged("paged_extract", store)
+    dims, offset = np.asarray(volume.dims, np.int64), np.asarray(volume.offset, np.int64)
+    live_lo, live_hi = _window_blocks(offset, dims)
+    lo, hi = offset, offset + dims
+    if len(store):
+        b = store.bounds()
+        lo, hi = np.minimum(lo, np.asarray(b[0]) * BLOCK), np.maximum(hi, np.asarray(b[1]) * BLOCK)
+    if volume._page_scratch is None:
+        volume._page_scratch = (TSDFVolume(volume.dims, volume.voxel_size, volume.origin, trunc=volume.trunc, w_max=volume.w_max,
+                                           device=volume.device, color=volume.color is not None),
+                                _Staging(volume._buf.shape[0], volume.device))
+    tile, staging = volume._page_scratch
+    starts = [list(range(int(lo[k]), max(int(hi[k]) - 1, int(lo[k]) + 1), max(int(dims[k]) - 1, 1))) for k in range(3)]
+    parts = []
+    for tz in starts[2]:
+        for ty in starts[1]:
+            for tx in starts[0]:
+                t = np.array([tx, ty, tz], np.int64)
+                keys = _box_keys(t // BLOCK, (t + dims - 1) // BLOCK + 1)
+                live = keys[((keys >= live_lo) & (keys < live_hi)).all(axis=1)]
+                found, data = store.get(_outside(keys, live_lo, live_hi))
+                n = len(live) + len(found)
+                if n == 0:
+                    continue
+                blocks = staging.need(n)[0]
+                if len(live):
+                    _in_calls(ops.tsdf_blocks_gather, volume._buf, live * BLOCK - offset, blocks[:len(live)], staging.flags[:len(live)])
+                if len(found):
+                    blocks[len(live):n].copy_(torch.from_numpy(data))
+                tile.offset = tuple(int(v) for v in t)
+                tile.origin = tuple(o + volume.voxel_size * int(k) for o, k in zip(volume._origin0, t))    # as shift forms it
+                tile.reset()
+                _in_calls(ops.tsdf_blocks_scatter, tile._buf, np.concatenate([live, found]) * BLOCK - t, blocks[:n])
+                got = (tile.mesh if what == "mesh" else tile.points)(w_min=w_min, colors=colors)[:-1]
+                parts.append(tuple(a.cpu().numpy() for a in got))
+    empty = (np.zeros((0, 3), np.float32),) + ((np.zeros((0, 3), np.int32),) if what == "mesh" else ()) + (
+        (np.zeros((0, 3), np.float32),) if colors else ())
+    if not parts:
+        return empty
+    out = (np.concatenate([p[0] for p in parts]),)
+    if what == "mesh":
+        base = np.cumsum([0] + [len(p[0]) for p in parts[:-1]])
+        out += (np.concatenate([p[1] + np.int32(b) for p, b in zip(parts, base)]).astype(np.int32),)
+    return out + ((np.concatenate([p[-1] for p in parts]),) if colors else ())
+
+
 class _Frame(typing.NamedTuple):
     """What FusionVideoStream integrates a frame with: built once per frame, rebuilt from the history's slots for a held one."""
     depth: torch.Tensor
@@ -575,7 +854,13 @@ class FusionVideoStream(VideoDepthStream):
     follow_spill says what becomes of the part that leaves: 'mesh' (the default) or 'points' — the stream extracts the spill volume
     with w_min = follow_w_min (with colours on a colour stream) and appends the result as host numpy arrays to `chunks`, which
     synchronises once per shift (shifts are rare, and the extraction reads its counts back anyway) —, a callable that is handed the
-    spill volume (valid until the next shift), or None: what leaves is dropped and nothing is spilled.  `n_shifts` counts the shifts;
+    spill volume (valid until the next shift), or None: what leaves is dropped and nothing is spilled.  follow_spill='page': nothing
+    is extracted and `chunks` stays empty; what leaves is kept as 8^3 voxel blocks in `store` — a BlockStore the stream builds, or
+    the one passed as follow_store=, which lets a saved map continue — and what the store holds of the region that enters comes
+    back bit for bit (TSDFVolume.shift(store=...): the camera that returns tracks against, and fuses into, the model it left);
+    `n_paged_out` and `n_paged_in` count the blocks; `world_mesh()` / `world_points()` are then paged_extract over the live window
+    and the store at follow_w_min; follow_step and the volume's dims must be multiples of 8 (refused at construction otherwise);
+    reset() keeps the store, as it keeps the chunks.  `n_shifts` counts the shifts;
     `world_mesh()` / `world_points()` return every chunk followed by the live volume's extraction.  reset() keeps the chunks, as
     the volume keeps accumulating across it.  A held frame (history=N) that was integrated before a shift can no longer be taken out
     exactly — the region that entered never held it —: `repose` and `retrack` of such a frame raise ValueError; it still serves as
@@ -585,7 +870,7 @@ class FusionVideoStream(VideoDepthStream):
     def __init__(self, model, cam_intrinsics, d_candi, volume, t_win_r=2, source="refined", conf_threshold=0., weight="uniform",
                  depth_range=None, color=False, track=False, track_kwargs=None, photo=False, history=0, consistency=0,
                  consistency_rel=0.01, follow=None, follow_margin=0.25, follow_step=8, follow_spill="mesh", follow_w_min=1.,
-                 **video_kwargs):
+                 follow_store=None, **video_kwargs):
         from .nets import require_volume_refiner
         require_volume_refiner(model, "FusionVideoStream")
         if source not in ("refined", "dpv"):
@@ -643,8 +928,19 @@ class FusionVideoStream(VideoDepthStream):
         self.follow_margin, self.follow_step, self.follow_spill, self.follow_w_min = follow_margin, follow_step, follow_spill, float(follow_w_min)
         if self.follow is not None:
             follow_shift(np.eye(4), volume, self.follow, follow_margin, follow_step)      # the parameter refusals, at construction
-            if not (follow_spill is None or follow_spill in ("mesh", "points") or callable(follow_spill)):
-                raise ValueError("FusionVideoStream: follow_spill is 'mesh', 'points', None or a callable, got %r" % (follow_spill,))
+            if not (follow_spill is None or follow_spill in ("mesh", "points", "page") or callable(follow_spill)):
+                raise ValueError("FusionVideoStream: follow_spill is 'mesh', 'points', 'page', None or a callable, got %r" % (follow_spill,))
+        paged = self.follow is not None and follow_spill == "page"
+        if follow_store is not None and not paged:
+            raise ValueError("FusionVideoStream: follow_store comes with follow=distance and follow_spill='page'")
+        self.store = None                                       # follow_spill='page': what left the volume, as blocks on the host
+        self.n_paged_out = self.n_paged_in = 0                  # blocks this stream put into the store / took out of it
+        if paged:
+            if int(follow_step) % BLOCK:
+                raise ValueError("FusionVideoStream: follow_spill='page' moves the volume by whole blocks: follow_step is a multiple "
+                                 "of %d, got %r" % (BLOCK, follow_step))
+            self.store = BlockStore(volume._buf.shape[0]) if follow_store is None else follow_store
+            volume._paged("shift", self.store)                  # the planes, and dims and offset on the block lattice
         self.n_shifts = 0
         self.chunks = []                                        # what left the volume, per shift: host arrays (follow_spill)
         super().__init__(model, cam_intrinsics, d_candi, t_win_r=t_win_r, **video_kwargs)
@@ -742,6 +1038,13 @@ class FusionVideoStream(VideoDepthStream):
         s = follow_shift(pose, self.volume, self.follow, self.follow_margin, self.follow_step)
         if s == (0, 0, 0):
             return
+        if self.store is not None:                              # 'page': what leaves goes to the store, what it holds comes back
+            before = (self.store.n_put, self.store.n_taken)
+            self.volume.shift(s, store=self.store)
+            self.n_shifts += 1
+            self.n_paged_out += self.store.n_put - before[0]
+            self.n_paged_in += self.store.n_taken - before[1]
+            return
         spill = self.volume.shift(s, spill=self.follow_spill is not None)
         self.n_shifts += 1
         if callable(self.follow_spill):
@@ -761,6 +1064,8 @@ class FusionVideoStream(VideoDepthStream):
         fp32, faces [m,3] int32[, colors [n,3] fp32 on a colour stream]) as numpy arrays.  The parts partition the model's cells:
         no triangle is missing and none occurs twice; the seam vertices exist in both neighbours, each part being a mesh of its
         own.  Synchronises (the live extraction reads its counts back)."""
+        if self.store is not None:
+            return paged_extract(self.volume, self.store, "mesh", w_min=self.follow_w_min, colors=self.color)
         if self.follow is not None and self.follow_spill != "mesh":
             raise ValueError("FusionVideoStream.world_mesh: the chunks are meshes only with follow_spill='mesh', got %r" % (self.follow_spill,))
         parts = list(self.chunks) + [self._on_host(self.volume.mesh)]
@@ -772,6 +1077,8 @@ class FusionVideoStream(VideoDepthStream):
         """The same for points: every chunk's points (a mesh chunk's vertices ARE its points), then the live volume's
         points(w_min=follow_w_min): (points [n,3] fp32[, colors [n,3] fp32]) as numpy arrays.  A crossing between two rim voxels
         occurs in the chunk and in what follows it."""
+        if self.store is not None:
+            return paged_extract(self.volume, self.store, "points", w_min=self.follow_w_min, colors=self.color)
         if self.follow is not None and self.follow_spill not in ("mesh", "points"):
             raise ValueError("FusionVideoStream.world_points: no chunks are kept with follow_spill=%r" % (self.follow_spill,))
         parts = [(p[0], p[-1]) for p in self.chunks]

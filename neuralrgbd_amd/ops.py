@@ -5,6 +5,7 @@ launches hand-written gfx950 kernels.  Inputs must be CUDA fp32 tensors — ther
 path: a CPU tensor raises.
 """
 import ctypes
+import typing
 
 import numpy as np
 import torch
@@ -1841,6 +1842,132 @@ def tsdf_shift(src, dst, shift, spill=False):
     with torch.cuda.device(src.device):
         rc = _lib.load().nrgbd_tsdf_shift_f32(_p(src), _p(dst), planes, X, Y, Z, s[0], s[1], s[2], 1 if spill else 0, _stream(src))
     _lib.check(rc, "nrgbd_tsdf_shift_f32")
+
+
+TSDF_BLOCK = 8                                                      # NRGBD_TSDF_BLOCK: voxels along a paged block's edge
+TSDF_MAX_BLOCKS = 1 << 20                                           # NRGBD_TSDF_MAX_BLOCKS: blocks in one call
+
+
+class BlockOrigins(typing.NamedTuple):
+    """Block origins on both sides: what tsdf_block_origins returns and the two block wrappers take in a host array's place."""
+    host: np.ndarray                                                # int32 [n,3]
+    dev: torch.Tensor                                               # the same on the device
+
+
+def tsdf_block_origins(origins, device):
+    """origins: a host int array [n,3] of (ox, oy, oz) in grid voxels, |o| <= 2^30 -> BlockOrigins(the int32 array, its copy on
+    `device`).  The upload the block wrappers do per call, done once: for a caller that uses the same blocks again, or that captures
+    the launches into a graph (an upload from pageable host memory is not a graph node)."""
+    if isinstance(origins, BlockOrigins):
+        return origins
+    if isinstance(origins, torch.Tensor):
+        raise TypeError("tsdf_block_origins: origins is a host int array [n,3], not a tensor")
+    a = np.asarray(origins)
+    if a.size == 0:
+        a = np.zeros((0, 3), np.int32)
+    if a.ndim != 2 or a.shape[1] != 3 or a.dtype.kind not in "iu":
+        raise ValueError("tsdf_block_origins: origins is an int array [n,3], got %s %s" % (a.dtype, a.shape))
+    if len(a) > TSDF_MAX_BLOCKS:
+        raise ValueError("tsdf_block_origins: %d blocks, at most %d in one call" % (len(a), TSDF_MAX_BLOCKS))
+    if len(a) and int(np.abs(a.astype(np.int64)).max()) > 2 ** 30:
+        raise ValueError("tsdf_block_origins: an origin beyond 2^30 voxels")
+    host = np.ascontiguousarray(a, dtype=np.int32)
+    return BlockOrigins(host, torch.from_numpy(host).to(device))
+
+
+def _tsdf_blocks(who, buf, origins, blocks):
+    """What the two block wrappers check alike: -> (buf, BlockOrigins, n, blocks or None)."""
+    buf = _need(buf, "buf", strided=True)
+    if buf.dim() != 4 or buf.shape[0] not in (2, 5) or not buf.is_contiguous():
+        raise ValueError("%s: buf must be a contiguous [2|5,Z,Y,X] tensor, got %s" % (who, tuple(buf.shape)))
+    o = tsdf_block_origins(origins, buf.device)
+    if o.dev.device != buf.device:
+        raise ValueError("%s: the origins are on %s, buf on %s" % (who, o.dev.device, buf.device))
+    n = len(o.host)
+    if blocks is not None:
+        blocks = _need(blocks, "blocks", strided=True)
+        if (blocks.dim() != 5 or tuple(blocks.shape[1:]) != (buf.shape[0],) + (TSDF_BLOCK,) * 3 or blocks.shape[0] < n
+                or not blocks.is_contiguous() or blocks.device != buf.device or blocks.data_ptr() % 16):
+            raise ValueError("%s: blocks must be a contiguous 16-byte aligned [>= %d,%d,8,8,8] tensor on %s, got %s"
+                             % (who, n, buf.shape[0], buf.device, tuple(blocks.shape)))
+    return buf, o, n, blocks
+
+
+def tsdf_blocks_gather(buf, origins, out=None, nonempty=None):
+    """n blocks of 8^3 voxels read out of a TSDF volume, one launch (nrgbd_tsdf_blocks_gather_f32; the semantics are written out in
+    include/nrgbd.h): blocks[b][p][k][j][i] = buf[p][oz + k][oy + j][ox + i] bit for bit where that voxel lies in the grid and +0.0
+    where it does not.  buf: contiguous CUDA fp32 [2,Z,Y,X] or [5,Z,Y,X] (TSDFVolume's buffer); origins: a host int array [n,3] of
+    (ox, oy, oz) in grid voxels, uploaded here — any integers up to 2^30 either way, aligned to nothing —, or tsdf_block_origins'
+    result; out: contiguous CUDA fp32 [>= n,planes,8,8,8] to write the first n blocks of (allocated when None); nonempty: CUDA int32
+    [>= n] to write the flags into (allocated when None): 1 where some in-grid word of the block has a non-zero bit pattern (-0.0 and
+    NaN count).  Returns (blocks [n,planes,8,8,8], nonempty [n]).  Synchronises nothing."""
+    who = "tsdf_blocks_gather"
+    buf, o, n, out = _tsdf_blocks(who, buf, origins, out)
+    if out is None:
+        out = torch.empty((n, buf.shape[0]) + (TSDF_BLOCK,) * 3, dtype=torch.float32, device=buf.device)
+    if nonempty is None:
+        nonempty = torch.empty(n, dtype=torch.int32, device=buf.device)
+    elif (not isinstance(nonempty, torch.Tensor) or nonempty.dtype != torch.int32 or nonempty.dim() != 1 or nonempty.shape[0] < n
+          or not nonempty.is_contiguous() or nonempty.device != buf.device):
+        raise ValueError("%s: nonempty must be a contiguous int32 tensor [>= %d] on %s" % (who, n, buf.device))
+    planes, Z, Y, X = buf.shape
+    with torch.cuda.device(buf.device):
+        rc = _lib.load().nrgbd_tsdf_blocks_gather_f32(_p(buf), planes, X, Y, Z, _p(o.dev), n, _p(out), _p(nonempty), _stream(buf))
+    _lib.check(rc, "nrgbd_tsdf_blocks_gather_f32")
+    return out[:n], nonempty[:n]
+
+
+def tsdf_blocks_scatter(buf, origins, blocks):
+    """The inverse of tsdf_blocks_gather, one launch (nrgbd_tsdf_blocks_scatter_f32): every voxel of block b that lies in the grid
+    gets blocks[b]'s word, the part of a block outside the grid is ignored, and every voxel outside all the blocks keeps its bits.
+    buf, origins: as tsdf_blocks_gather's; blocks: contiguous CUDA fp32 [>= n,planes,8,8,8], the first n are used.  Two blocks of one
+    call must not overlap inside the grid — the launch has no order between them —: origins closer than 8 along all three axes whose
+    common part reaches into the grid raise ValueError, checked on the host before anything is launched.  Synchronises nothing."""
+    who = "tsdf_blocks_scatter"
+    buf, o, n, blocks = _tsdf_blocks(who, buf, origins, blocks)
+    if blocks is None:
+        raise TypeError("%s: blocks must be a torch.Tensor" % who)
+    planes, Z, Y, X = buf.shape
+    pair = tsdf_blocks_overlap(o.host, (X, Y, Z))
+    if pair is not None:
+        raise ValueError("%s: blocks %d and %d (origins %s and %s) overlap inside the grid" % ((who,) + pair + tuple(
+            tuple(int(v) for v in o.host[k]) for k in pair)))
+    with torch.cuda.device(buf.device):
+        rc = _lib.load().nrgbd_tsdf_blocks_scatter_f32(_p(buf), planes, X, Y, Z, _p(o.dev), n, _p(blocks), _stream(buf))
+    _lib.check(rc, "nrgbd_tsdf_blocks_scatter_f32")
+
+
+def tsdf_blocks_overlap(origins, dims):
+    """The first pair (a, b) of rows of the int array origins [n,3] whose 8^3 blocks share a voxel of the dims = (X, Y, Z) grid, or
+    None.  Host only.  Blocks on one 8-voxel lattice — what a paged shift moves — overlap only where two are the same: one sort.
+    Otherwise the blocks that touch the grid are sorted into the cells of an 8-voxel lattice; two blocks can share a voxel only from
+    the same or a neighbouring cell, so the work grows with n, not n^2."""
+    o = np.asarray(origins, dtype=np.int64).reshape(-1, 3)
+    dims = np.asarray(dims, dtype=np.int64)
+    touching = np.flatnonzero(((o + TSDF_BLOCK > 0) & (o < dims)).all(axis=1))
+    if len(touching) < 2:
+        return None
+    if not ((o[touching] - o[touching[0]]) % TSDF_BLOCK).any():
+        rows, first, count = np.unique(o[touching], axis=0, return_index=True, return_counts=True)
+        if count.max() == 1:
+            return None
+        twice = touching[(o[touching] == rows[np.flatnonzero(count > 1)[first[count > 1].argmin()]]).all(axis=1)]
+        return (int(twice[0]), int(twice[1]))
+    cells = {}
+    for b in touching:
+        cells.setdefault(tuple(o[b] // TSDF_BLOCK), []).append(int(b))
+    for b in touching:
+        c = o[b] // TSDF_BLOCK
+        for dz in (-1, 0, 1):
+            for dy in (-1, 0, 1):
+                for dx in (-1, 0, 1):
+                    for a in cells.get((int(c[0]) + dx, int(c[1]) + dy, int(c[2]) + dz), ()):
+                        if a >= b or (np.abs(o[a] - o[b]) >= TSDF_BLOCK).any():
+                            continue
+                        lo, hi = np.maximum(np.maximum(o[a], o[b]), 0), np.minimum(np.minimum(o[a], o[b]) + TSDF_BLOCK, dims)
+                        if (lo < hi).all():
+                            return (a, int(b))
+    return None
 
 
 def tsdf_extract_workspace(X, Y, Z):
