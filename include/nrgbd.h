@@ -562,6 +562,22 @@ int nrgbd_conv_wino_rnet_f32(const float* x, const float* w_wino, const float* b
  * 96-wide concat buffers whose padding channels stay zero. */
 int nrgbd_conv_wino_rnet_ex_f32(const float* x, const float* w_wino, const float* bias, int out_lrelu, float* y,
                                 int N, int H, int W, int Cin, int Cout, int ldy, int ycoff, int cout_valid, void* stream);
+/* Deconv form of the same kernel: nn.ConvTranspose2d(kernel 4, stride 2, padding 1) + bias + LeakyReLU (m_submodule.py:36-45;
+ * Refine.py:57,64 trans_conv0 / trans_conv1) of ONE 64-column output slice, x [N][H][W][Cin] -> y [N][2H][2W][ldy].  The four sub-pixel
+ * phases (a, b) are 3x3 kernels that are non-zero in a 2x2 corner, stacked phase-major along the output channels (256 columns, phase
+ * 2a + b = column group): of the 16 transform points of U = G g G^T a phase has 9 non-zero ones (xi_y = a .. a+2, xi_x = b .. b+2);
+ * the kernel skips the other 7 (2.25 multiplies per output and input channel) and stores phase pixel (y, x) at pixel (2y + a, 2x + b),
+ * columns ycoff .. ycoff + cout_valid - 1 (ldy = 0: 64, cout_valid = 0: 64).  Bit-equal to nrgbd_conv_wino_rnet_ex_f32 on the stacked
+ * weights followed by the pixel shuffle (finite inputs).
+ *   w_masked: [4 phases][stage = Cin/16][9 live points][4 waves][64 lanes][4] floats: nrgbd_conv_wino_rnet_deconv_pack copies them out of
+ *             the 256-column stream w_wino that nrgbd_conv_wino_pack makes of the stacked weights [256][Cin][3][3]
+ *   errors    NRGBD_E_NULL: x, w_masked or y NULL;  NRGBD_E_SHAPE: a dimension <= 0, Cin < 32, Cin % 32 != 0 (an even number of
+ *             16-channel stages), Cout != 64, N H W Cin >= 2^30, 4 N H W ldy >= 2^31;  NRGBD_E_ARG: cout_valid outside 0 .. 64,
+ *             ycoff < 0, ldy < ycoff + cout_valid;  NRGBD_E_ALIGN: x or w_masked not 16-byte aligned, y or bias not 4-byte aligned.
+ *             Checked in this order, before anything is launched. */
+int nrgbd_conv_wino_rnet_deconv_f32(const float* x, const float* w_masked, const float* bias, int out_lrelu, float* y,
+                                    int N, int H, int W, int Cin, int Cout, int ldy, int ycoff, int cout_valid, void* stream);
+int nrgbd_conv_wino_rnet_deconv_pack(const float* w_wino, float* w_masked, int Cin, void* stream);
 /* w [Cout][Cin][kd][3][3] (torch layout) -> w_wino [Cout*Cin*kd*16] floats in the order described above (on the device).
  * transposed = 1: the DATA-GRADIENT weights of w [Cin][Cout][kd][3][3] (roles of the channel axes swapped, every tap flipped),
  * i.e. what the same kernel needs to turn dL/dy into dL/dx — without materialising w.transpose(0,1).flip(...) first.

@@ -4,7 +4,8 @@
 //
 // Serves  (a) the K-Net's ten 64 -> 64 3x3x3 layers (models/basic.py:71-94): KD = 3 depth taps, each a 2-D Winograd problem;
 //         (b) the 3x3 stride-1 layers of the feature CNN (models/psm_submodule.py:10-16,31-50,100-134), dilation 1 or 2:
-//             KD = 1, any Cin % 16 == 0, Cout % 64 == 0 (a tile is repeated per 64-column group of outputs)
+//             KD = 1, any Cin % 16 == 0, Cout % 64 == 0 (a tile is repeated per 64-column group of outputs);
+//         (c) the R-Net's 3x3 layers (EPI = 1) and its two transposed convolutions (EPI = 2: the deconv form, see pc_dc_*)
 // with the same fused BatchNorm work around them as conv3d.hip / conv2d.hip: statistics of the raw output in the epilogue,
 // normalise + ReLU + residual add (+ materialise) while the input is loaded.
 //
@@ -58,6 +59,7 @@ namespace nrgbd {
 // lines of it); statistics rows are (tile, row block).  The producers are unchanged — they now set the pace (a stage's MFMAs
 // take 0.85 us): 2.25x fewer multiplies than conv2d.hip's direct form of these layers.
 // EPI = 1: the R-Net form (bias + LeakyReLU in the epilogue, no prologue, no statistics).  ODD: an odd stage count per tile.
+// EPI = 2: the R-Net's transposed convolutions on that form: four sub-pixel phases, dead transform points skipped (pc_dc_*).
 namespace {
 
 // ======================================================= consumer steps =====================================================
@@ -271,6 +273,202 @@ __device__ __forceinline__ void pc_epilogue(const PcAcc<HALF>& acc, const WinoPc
     if (a.stats) pc_store_stats<HALF>(a, tl, c, co, s1, s2);
 }
 
+// ============================================ consumer steps of the deconv form (EPI = 2) ====================================
+// ConvTranspose2d(k4, s2, p1) as four sub-pixel phases (a, b), each a 3x3 kernel that is non-zero in one 2x2 corner (phase-stacked
+// along the output channels, autograd.conv_transpose2d_module): column group cg of the Cout = 256 launch = phase 2a + b.  A zero last
+// (first) kernel row makes row 3 (0) of U = G g G^T zero, the same for columns: a phase has 9 live transform points of the 16, the
+// 3 x 3 block xi_y = a .. a+2, xi_x = b .. b+2.  The consumers skip the weight line, the A reads and the MFMAs of the 7 dead points
+// (2.25 instead of 4 multiplies per output and channel); the weight stream carries the 9 live lines per (stage, phase); the
+// producers are the R-Net form's.  The phase is a template parameter of a whole tile (four straight-line bodies): a dead
+// accumulator does not exist, the inverse transform takes the exact zero the unmasked evaluation computes there.
+constexpr int kPcDcPts = 9;                     // live transform points per phase = weight lines per stage; also the weight ring's slots
+template <int PH> __device__ constexpr int pc_dc_xi(int p) { return 4 * (p / 3 + (PH >> 1)) + p % 3 + (PH & 1); }   // p-th live point
+template <int PH> __device__ constexpr bool pc_dc_live(int xi) {
+    return (xi >> 2) >= (PH >> 1) && (xi >> 2) < (PH >> 1) + 3 && (xi & 3) >= (PH & 1) && (xi & 3) < (PH & 1) + 3;
+}
+__device__ __forceinline__ int pc_dc_first(int ph) { return (4 * (ph >> 1) + (ph & 1)) * (kPcTiles * kCB); }   // V offset of a phase's first live point
+
+// the lane's output addressing: phase pixel (y, x) is full-resolution pixel (2y + a, 2x + b) of the [N][2H][2W][ldy] buffer, so a
+// step in x is 2 ldy floats and a step in y 2 W of those; c.ldy holds the doubled stride
+__device__ __forceinline__ PcLane pc_dc_lane(const WinoPcArgs& a, int lane, int wv) {
+    PcLane c;
+    c.kq = lane >> 4; c.jj = lane & 15;
+    c.msel = 0; c.cwv = wv;
+    c.a0 = pc_slot(0, c.jj, c.kq); c.a1 = pc_slot(0, 16 + c.jj, c.kq);
+    c.ldy = 2u * (unsigned)a.ldy;
+    c.lane_yoff = (unsigned)c.jj + (unsigned)((2 * (c.kq >> 1)) * (2 * a.W) + 8 * (c.kq & 1)) * c.ldy;
+    return c;
+}
+
+// one stage = 9 live points x (2 A reads + 1 weight line + 8 MFMAs).  Rings whose length divides 9, so that a point's slots are
+// the same in every stage: A operands two points ahead in 3 slots, weight lines 7 ahead in 9.  nx0: V offset of the first live
+// point of the NEXT stage (the next tile's phase behind a tile's last stage); its second one is the point after it.
+template <int PH, bool FIRST>
+__device__ __forceinline__ void pc_dc_stage(PcAcc<false>& acc, f32x4 (&An)[3][2], f32x4 (&Bn)[kPcDcPts], const float* Vc, const float* Vn, int nx0,
+                                            const f32x4* wcur, const f32x4* wnx, const PcLane& c) {
+    const int a0 = c.a0, a1 = c.a1;
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int p = 0; p < kPcDcPts; ++p) {
+        const int xi = pc_dc_xi<PH>(p), cur = p % 3, nxt = (p + 2) % 3;
+        if (p + 2 < kPcDcPts) {
+            An[nxt][0] = *reinterpret_cast<const f32x4*>(Vc + a0 + pc_dc_xi<PH>(p + 2) * (kPcTiles * kCB));
+            An[nxt][1] = *reinterpret_cast<const f32x4*>(Vc + a1 + pc_dc_xi<PH>(p + 2) * (kPcTiles * kCB));
+        } else {   // the first two operands of the next stage: its buffer was completed before the previous barrier
+            An[nxt][0] = *reinterpret_cast<const f32x4*>(Vn + a0 + nx0 + (p + 2 - kPcDcPts) * (kPcTiles * kCB));
+            An[nxt][1] = *reinterpret_cast<const f32x4*>(Vn + a1 + nx0 + (p + 2 - kPcDcPts) * (kPcTiles * kCB));
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            acc[xi][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(An[cur][0][e], Bn[p][e], FIRST && e == 0 ? zero4 : acc[xi][0], 0, 0, 0);
+            acc[xi][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(An[cur][1][e], Bn[p][e], FIRST && e == 0 ? zero4 : acc[xi][1], 0, 0, 0);
+            if (e == kPcWPos) Bn[(p + kPcBD) % kPcDcPts] = p + kPcBD < kPcDcPts ? wcur[(p + kPcBD) * 256] : wnx[(p + kPcBD - kPcDcPts) * 256];
+            __builtin_amdgcn_sched_barrier(0);   // as in pc_mfma_stage: the row blocks alternate, the operand streams keep their distances
+        }
+    }
+}
+
+// the epilogues of pc_epilogue_interior / pc_epilogue_edge with a dead point's M = 0, bias + LeakyReLU as EPI = 1, the phase's
+// scattered addresses, no statistics.  The additions are those of the unmasked form, zeros included (0 + x is not x for x = -0).
+template <int PH>
+__device__ __forceinline__ void pc_dc_epilogue_interior(const PcAcc<false>& acc, const WinoPcArgs& a, const PcLane& c, float* ybase, bool cok, float bval) {
+    const unsigned ldy = c.ldy, lane_yoff = c.lane_yoff;
+    const size_t W2 = 2 * (size_t)a.W;
+    float neg1 = -1.f;
+    asm volatile("" : "+v"(neg1));
+    const f32x2 n1 = {neg1, neg1};
+    const f32x2 bias2 = {bval, bval};
+    const f32x2 z2 = {0.f, 0.f};
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+#pragma unroll
+        for (int rp = 0; rp < 2; ++rp) {
+            f32x2 tr[2][4];
+#pragma unroll
+            for (int xx = 0; xx < 4; ++xx) {
+                const f32x2 m0 = !pc_dc_live<PH>(0 + xx) ? z2 : rp ? acc[0 + xx][m].hi : acc[0 + xx][m].lo;
+                const f32x2 m1 = !pc_dc_live<PH>(4 + xx) ? z2 : rp ? acc[4 + xx][m].hi : acc[4 + xx][m].lo;
+                const f32x2 m2 = !pc_dc_live<PH>(8 + xx) ? z2 : rp ? acc[8 + xx][m].hi : acc[8 + xx][m].lo;
+                const f32x2 m3 = !pc_dc_live<PH>(12 + xx) ? z2 : rp ? acc[12 + xx][m].hi : acc[12 + xx][m].lo;
+                tr[0][xx] = (m0 + m1) + m2;
+                tr[1][xx] = __builtin_elementwise_fma(m3, n1, __builtin_elementwise_fma(m2, n1, m1));   // (m1 - m2) - m3
+            }
+#pragma unroll
+            for (int aa = 0; aa < 2; ++aa) {
+                f32x2 o0 = (tr[aa][0] + tr[aa][1]) + tr[aa][2];
+                f32x2 o1 = __builtin_elementwise_fma(tr[aa][3], n1, __builtin_elementwise_fma(tr[aa][2], n1, tr[aa][1]));
+                o0 = o0 + bias2; o1 = o1 + bias2;
+                if (a.out_lrelu) {
+                    const f32x2 sl = {0.01f, 0.01f};
+                    o0 = __builtin_elementwise_max(o0, o0 * sl); o1 = __builtin_elementwise_max(o1, o1 * sl);
+                }
+                float* oa = ybase + ((size_t)(4 * m + aa) * W2 + (size_t)(2 * (2 * rp))) * ldy;       // tile r = 2 rp
+                float* ob = ybase + ((size_t)(4 * m + aa) * W2 + (size_t)(2 * (2 * rp + 1))) * ldy;   // tile r + 1
+                if (cok) {
+                    oa[lane_yoff] = o0.x; oa[lane_yoff + ldy] = o1.x;
+                    ob[lane_yoff] = o0.y; ob[lane_yoff + ldy] = o1.y;
+                }
+            }
+        }
+    }
+}
+
+template <int PH>
+__device__ __forceinline__ void pc_dc_epilogue_edge(const PcAcc<false>& acc, const WinoPcArgs& a, const PcTile& tl, const PcLane& c, float* ybase,
+                                                    bool cok, float bval) {
+    const unsigned ldy = c.ldy, lane_yoff = c.lane_yoff;
+    const size_t W2 = 2 * (size_t)a.W;
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float tr[2][4];
+#pragma unroll
+            for (int xx = 0; xx < 4; ++xx) {
+                const float m0 = pc_dc_live<PH>(0 + xx) ? acc[0 + xx][m][r] : 0.f, m1 = pc_dc_live<PH>(4 + xx) ? acc[4 + xx][m][r] : 0.f;
+                const float m2 = pc_dc_live<PH>(8 + xx) ? acc[8 + xx][m][r] : 0.f, m3 = pc_dc_live<PH>(12 + xx) ? acc[12 + xx][m][r] : 0.f;
+                tr[0][xx] = (m0 + m1) + m2;
+                tr[1][xx] = (m1 - m2) - m3;
+            }
+#pragma unroll
+            for (int aa = 0; aa < 2; ++aa) {
+                float o0 = (tr[aa][0] + tr[aa][1]) + tr[aa][2];
+                float o1 = (tr[aa][1] - tr[aa][2]) - tr[aa][3];
+                o0 += bval; o1 += bval;
+                if (a.out_lrelu) { o0 = fmaxf(o0, 0.01f * o0); o1 = fmaxf(o1, 0.01f * o1); }
+                float* o = ybase + ((size_t)(4 * m + aa) * W2 + (size_t)(2 * r)) * ldy;   // uniform
+                const int tile = 16 * m + 4 * c.kq + r;
+                const int gy = tl.y0 + 2 * (tile >> 3) + aa, gx = tl.x0 + 2 * (tile & 7);   // phase (= input grid) coordinates
+                if (gy < a.H && cok) {
+                    if (gx < a.W) o[lane_yoff] = o0;
+                    if (gx + 1 < a.W) o[lane_yoff + ldy] = o1;
+                }
+            }
+        }
+    }
+}
+
+// a whole tile of phase PH: its stages (each up to its barrier) and its epilogue.  nph: the next tile's phase.
+template <int PH>
+__device__ __forceinline__ void pc_dc_tile(const WinoPcArgs& a, const PcTile& tl, int nph, int NS, f32x4 (&An)[3][2], f32x4 (&Bn)[kPcDcPts],
+                                           const float* Vb, int& buf, const f32x4* wt, const f32x4* wt_next, const PcLane& c) {
+    PcAcc<false> acc;
+    for (int s = 0; s < NS; ++s) {
+        const float* Vc = Vb + buf * kPcV;
+        const int nbuf = buf == kPcNBuf - 1 ? 0 : buf + 1;
+        const float* Vn = Vb + nbuf * kPcV;
+        const f32x4* wcur = wt + (size_t)s * (kPcDcPts * 256);
+        const bool last = s + 1 == NS;
+        const f32x4* wnx = last ? wt_next : wcur + kPcDcPts * 256;
+        const int nx0 = pc_dc_first(last ? nph : PH);
+        if (s == 0) pc_dc_stage<PH, true>(acc, An, Bn, Vc, Vn, nx0, wcur, wnx, c);
+        else pc_dc_stage<PH, false>(acc, An, Bn, Vc, Vn, nx0, wcur, wnx, c);
+        __syncthreads();
+        buf = nbuf;
+    }
+    const int co = c.cwv * 16 + c.jj;     // every phase writes the slice's 64 columns
+    float* ybase = a.y + (((size_t)tl.n * (2 * a.H) + 2 * tl.y0 + (PH >> 1)) * (2 * (size_t)a.W) + 2 * tl.x0 + (PH & 1)) * a.ldy + a.ycoff + c.cwv * 16;
+    const bool cok = co < a.cout_valid;   // a padded output column is not stored
+    const bool inside = tl.y0 + (kPcTH - 1) < a.H && tl.x0 + (kPcTW - 1) < a.W;
+    const float bval = a.bias ? a.bias[co] : 0.f;
+    if (inside) pc_dc_epilogue_interior<PH>(acc, a, c, ybase, cok, bval);
+    else pc_dc_epilogue_edge<PH>(acc, a, tl, c, ybase, cok, bval);
+}
+
+// the consumer role of the deconv form: the barrier protocol of conv_wino_pc_kernel's consumers
+__device__ __forceinline__ void pc_dc_consumer(const WinoPcArgs& a, const float* Vb, int NS, int first, int step, int count, int lane, int wv) {
+    const PcLane c = pc_dc_lane(a, lane, wv);
+    const f32x4* wbase = reinterpret_cast<const f32x4*>(a.wp) + wv * 64 + lane;
+    const size_t wgroup = (size_t)NS * kPcDcPts * 256;                  // f32x4 per phase
+    PcTile tl = pc_decode<1, 1>(first, a);
+    const f32x4* wt = wbase + (size_t)tl.cg * wgroup;
+    f32x4 Bn[kPcDcPts], An[3][2];
+#pragma unroll
+    for (int b = 0; b < kPcBD; ++b) Bn[b] = wt[b * 256];
+    __syncthreads();
+    __syncthreads();
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        An[i][0] = *reinterpret_cast<const f32x4*>(Vb + c.a0 + pc_dc_first(tl.cg) + i * kPcTiles * kCB);
+        An[i][1] = *reinterpret_cast<const f32x4*>(Vb + c.a1 + pc_dc_first(tl.cg) + i * kPcTiles * kCB);
+    }
+    int buf = 0;
+    for (int it = 0; it < count; ++it) {
+        const int tnext = first + (it + 1 < count ? it + 1 : it) * step;
+        const PcTile tn = pc_decode<1, 1>(tnext, a);
+        const f32x4* wt_next = wbase + (size_t)tn.cg * wgroup;
+        switch (__builtin_amdgcn_readfirstlane(tl.cg)) {   // uniform: the barriers inside are reached by whole waves
+            case 0: pc_dc_tile<0>(a, tl, tn.cg, NS, An, Bn, Vb, buf, wt, wt_next, c); break;
+            case 1: pc_dc_tile<1>(a, tl, tn.cg, NS, An, Bn, Vb, buf, wt, wt_next, c); break;
+            case 2: pc_dc_tile<2>(a, tl, tn.cg, NS, An, Bn, Vb, buf, wt, wt_next, c); break;
+            default: pc_dc_tile<3>(a, tl, tn.cg, NS, An, Bn, Vb, buf, wt, wt_next, c); break;
+        }
+        tl = tn;
+        wt = wt_next;
+    }
+}
+
 // ======================================================= producer steps =====================================================
 // A producer lane's items.  Load / publish item u = 192 pw + lane + 64 u over the whole 10-row halo (every halo word has ONE
 // loader) -> strip pixel pi = item >> 2 in (row, de-interleaved column) order, 16-byte word w4; row and column are recomputed
@@ -398,7 +596,7 @@ __device__ __forceinline__ void pc_activate_publish(const WinoPcArgs& a, const P
     const bool wmat = MAT && (KD != 3 || kd == 1) && P.tl.cg == 0;
     constexpr int NU = kPcNPF;
     f32x2 lo[NU], hi[NU];
-    if constexpr (EPI == 1) {   // the R-Net form has no prologue: no identity FMAs (x * 1 + 0 is not folded: -0)
+    if constexpr (EPI >= 1) {   // the R-Net forms have no prologue: no identity FMAs (x * 1 + 0 is not folded: -0)
 #pragma unroll
         for (int i = 0; i < NU; ++i) { lo[i] = r.pre[i].lo; hi[i] = r.pre[i].hi; }
     } else {
@@ -543,6 +741,9 @@ __global__ __launch_bounds__(512) void conv_wino_pc_kernel(const WinoPcArgs a) {
 
     // Producers are waves 0-3: VALU issue on a SIMD is arbitrated by age, and the producers' (few) VALU instructions have to
     // get through beside the consumer's continuous MFMA stream (measured: 3.58 -> 3.38 ms per layer from this alone)
+    if constexpr (EPI == 2) {   // the deconv form has its own consumers (pc_dc_consumer); the producers below are the R-Net form's
+        if (wave >= 4) { pc_dc_consumer(a, Vb, NS, first, step, count, lane, wv); return; }
+    }
     if (wave >= 4) {
         // =========================================== consumer: 16 output channels x 16 xi x 32 tiles ====================
         const PcLane c = pc_lane<DIL, EPI, HALF>(a, lane, wv);
@@ -691,6 +892,21 @@ __global__ __launch_bounds__(256) void conv_wino_pack_kernel(const float* __rest
     wp[idx] = (float)u;
 }
 
+// The deconv form's stream: the lines of the 9 live points of every (phase, stage) of the unmasked 256-column stream, copied
+// [4 phases][stage][9][4 waves][64 lanes][4] (the dropped lines are the transforms of zero kernel rows / columns: exact zeros)
+__global__ __launch_bounds__(256) void conv_wino_deconv_pack_kernel(const f32x4* __restrict__ wp, f32x4* __restrict__ wm, int NS) {
+    const long total = 4L * NS * kPcDcPts * 256;
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int in = (int)(idx & 255);
+    long t = idx >> 8;
+    const int p = (int)(t % kPcDcPts); t /= kPcDcPts;
+    const int s = (int)(t % NS);
+    const int ph = (int)(t / NS);
+    const int xi = 4 * (p / 3 + (ph >> 1)) + p % 3 + (ph & 1);
+    wm[idx] = wp[(((long)ph * NS + s) * 16 + xi) * 256 + in];
+}
+
 // ---- host side of conv_wino_pc_kernel, shared by nrgbd_conv_wino_f32 and nrgbd_conv_wino_rnet_ex_f32 ----
 // persistent workgroups: one per CU, or one per tile where the list is shorter
 static int pc_workgroups(long ntiles, int* nwg) {
@@ -825,6 +1041,48 @@ extern "C" int nrgbd_conv_wino_rnet_ex_f32(const float* x, const float* w_wino, 
     else if (odd) e = pc_launch<1, 1, false, true, 1, false, false>(L, a);
     else if (half) e = pc_launch<1, 1, false, false, 1, false, true>(L, a);
     else e = pc_launch<1, 1, false, false, 1, false, false>(L, a);
+    if (e != hipSuccess) return (int)e;
+    NRGBD_CHECK_LAUNCH();
+    return NRGBD_OK;
+}
+
+// Deconv form: ConvTranspose2d(k4, s2, p1) + bias + LeakyReLU of one 64-column output slice, all four sub-pixel phases in one launch
+extern "C" int nrgbd_conv_wino_rnet_deconv_pack(const float* w_wino, float* w_masked, int Cin, void* stream) {
+    using namespace nrgbd;
+    if (!w_wino || !w_masked) return NRGBD_E_NULL;
+    if (Cin <= 0 || Cin % kCB) return NRGBD_E_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(w_wino) | reinterpret_cast<uintptr_t>(w_masked)) & 15) return NRGBD_E_ALIGN;
+    const int NS = Cin / kCB;
+    const long total = 4L * NS * kPcDcPts * 256;
+    hipLaunchKernelGGL(conv_wino_deconv_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const f32x4*>(w_wino), reinterpret_cast<f32x4*>(w_masked), NS);
+    NRGBD_CHECK_LAUNCH();
+    return NRGBD_OK;
+}
+
+extern "C" int nrgbd_conv_wino_rnet_deconv_f32(const float* x, const float* w_masked, const float* bias, int out_lrelu, float* y, int N,
+                                               int H, int W, int Cin, int Cout, int ldy, int ycoff, int cout_valid, void* stream) {
+    using namespace nrgbd;
+    if (!x || !w_masked || !y) return NRGBD_E_NULL;
+    if (N <= 0 || H <= 0 || W <= 0 || Cin < 32 || Cin % kCB || ((Cin / kCB) & 1) || Cout != 64) return NRGBD_E_SHAPE;   // an even stage count >= 2
+    if ((long)N * H * W * Cin >= (1L << 30)) return NRGBD_E_SHAPE;
+    if (ldy == 0) ldy = Cout;
+    if (cout_valid == 0) cout_valid = Cout;
+    if (cout_valid < 0 || cout_valid > Cout || ycoff < 0 || ldy < ycoff + cout_valid) return NRGBD_E_ARG;
+    if (4L * N * H * W * ldy >= (1L << 31)) return NRGBD_E_SHAPE;        // 32-bit lane offsets inside a tile's rows of y [N][2H][2W][ldy]
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w_masked)) & 15) return NRGBD_E_ALIGN;   // 16-byte loads
+    if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(bias)) & 3) return NRGBD_E_ALIGN;
+    const int rows = nrgbd_conv_wino_tiles(N, H, W, 1);
+    const long nt = (long)rows * 4;                                     // a tile per sub-pixel phase: the kernel's four column groups
+    if (nt >= (1L << 30)) return NRGBD_E_SHAPE;
+    WinoPcArgs a{x, nullptr, nullptr, nullptr, nullptr, w_masked, y, nullptr, 0, 0, N, H, W, Cin, 4 * Cout, (int)nt, rows,
+                 bias, out_lrelu, ldy, ycoff, cout_valid};
+    int nwg = 0;
+    const int rc = pc_workgroups(nt, &nwg);
+    if (rc != NRGBD_OK) return rc;
+    const size_t lds = (size_t)(kPcNBuf * kPcV + kPcStrips) * sizeof(float);
+    const PcLaunch L{nwg, lds, (int)lds, (hipStream_t)stream};
+    const hipError_t e = pc_launch<1, 1, false, false, 2, false, false>(L, a);
     if (e != hipSuccess) return (int)e;
     NRGBD_CHECK_LAUNCH();
     return NRGBD_OK;

@@ -814,12 +814,17 @@ class DPVUpsampleNet(_PackedWeightsMixin, nn.Module):
             and self.trans_conv1[0].out_channels == D1 and self.conv2[0].in_channels == D1 + 3 and self.conv2_1[0].out_channels == D1
         return ((D, 64), (D0, D0), (D1, D1)) if ok else None
 
+    # Candidate kernels of the two transposed convolutions in order of preference: "wino" = the Winograd kernel's deconv form (dead
+    # transform points skipped; shapes it refuses take the next candidate), "direct" = conv2d.hip's four-tap form.  The A/B switch is an
+    # edit of this tuple (profiles/deconv_wino.txt)
+    deconv_kernels = ("wino", "direct")
     _FEATS = (64, 32, 3)        # image-feature channels behind the candidates at the three levels (every script of the reference)
 
     def mfma_ok(self, dpv):
         """Inference on the GPU -> the hand-written kernels (forward_log), at EVERY grid and candidate count the reference's
         scripts use: the six conv2d_leakyRelu layers and conv2_2 on the Winograd kernel's R-Net form (csrc/wino_pc.hip, 8x16-pixel
-        tiles of a persistent launch), the transposed convolutions on csrc/conv2d.hip, the log-softmax on csrc/softmax.hip."""
+        tiles of a persistent launch), the transposed convolutions on its deconv form (`deconv_kernels`; csrc/conv2d.hip for shapes
+        that form refuses), the log-softmax on csrc/softmax.hip."""
         return dpv.is_cuda and not torch.is_grad_enabled() and dpv.dtype == torch.float32
 
     def _embedded(self):
@@ -881,6 +886,16 @@ class DPVUpsampleNet(_PackedWeightsMixin, nn.Module):
             # all four phases for one launch (mode 3): per 64-column slice, the phases' streams back to back
             res["all"] = [(torch.cat([res[(pa, pb)][i][0] for pa in (0, 1) for pb in (0, 1)]),) + res[(0, 0)][i][1:]
                           for i in range(len(res[(0, 0)]))]
+            # the same launches on the Winograd kernel's deconv form (csrc/wino_pc.hip, EPI = 2): per slice the phases embedded in
+            # 3x3 kernels as the autograd path embeds them, their 256-column stream, its live lines.  None where the form has no
+            # instantiation (an odd number of 16-channel stages, a slice short of 64 columns): the direct kernel serves those
+            cin_p = pad16(w.shape[0])
+            res["wino"] = None
+            if cin_p % 32 == 0 and w.shape[1] % 64 == 0:
+                wi = w.new_zeros((cin_p,) + tuple(w.shape[1:]))
+                wi[:w.shape[0]] = w
+                res["wino"] = [(ops.conv_wino_rnet_deconv_pack(ops.conv_wino_pack(ops.deconv_phase_weights(wi[:, c0:c0 + 64])), cin_p),
+                                b[c0:c0 + 64].contiguous(), 64, c0, 64) for c0 in range(0, w.shape[1], 64)]
             return res
 
         def wino(name):
@@ -972,9 +987,15 @@ class DPVUpsampleNet(_PackedWeightsMixin, nn.Module):
         pk, buf = self._rnet_packed(), self._rnet_buffers(n, h, w, dev)
 
         def deconv(x, layer, out):
-            """ConvTranspose2d(k4, s2, p1) + bias + LeakyReLU: all four sub-pixel phases of every 64-column slice in one launch each."""
-            for wp, bias, wdt, c0, valid in layer:
-                ops.conv2d_rnet(x, wp, wdt, bias=bias, out=out, ldy=out.shape[-1], ycoff=c0, cout_valid=valid, mode=3)
+            """ConvTranspose2d(k4, s2, p1) + bias + LeakyReLU: all four sub-pixel phases of every 64-column slice in one launch each,
+            on the first kernel of `deconv_kernels` that takes the shape."""
+            wino = self.deconv_kernels[0] == "wino" and layer["wino"] is not None \
+                and ops.conv_wino_rnet_deconv_supported(x.shape[0], x.shape[1], x.shape[2], x.shape[3], out.shape[-1])
+            for wp, bias, wdt, c0, valid in layer["wino" if wino else "all"]:
+                if wino:
+                    ops.conv_wino_rnet_deconv(x, wp, out, bias=bias, ycoff=c0, cout_valid=valid)
+                else:
+                    ops.conv2d_rnet(x, wp, wdt, bias=bias, out=out, ldy=out.shape[-1], ycoff=c0, cout_valid=valid, mode=3)
             return out
 
         def conv_w(x, name, out=None, lrelu=True):
@@ -1005,12 +1026,12 @@ class DPVUpsampleNet(_PackedWeightsMixin, nn.Module):
         x = conv_w(conv_w(x, "conv0", buf["a0"]), "conv0_1", buf["b0"])
         # level 1/2: transposed conv (4 sub-pixel phases) straight into channels 0..Dp-1 of the concat buffer; features behind
         c1 = buf["c1"]
-        deconv(x, pk["t0"]["all"], c1)
+        deconv(x, pk["t0"], c1)
         ops.scatter_channels(half[0], c1, Dp1)         # the 1/2-resolution features behind the candidates of every sample (csrc/glue.hip)
         x = conv_w(conv_w(c1, "conv1", buf["a1"]), "conv1_1", buf["b1"])
         # full resolution: Dp + 3 channels in 16-aligned pixels (padding channels zero, with zero weights)
         c2 = buf["c2"]
-        deconv(x, pk["t1"]["all"], c2)
+        deconv(x, pk["t1"], c2)
         ops.scatter_channels(full[0], c2, Dpl)
         x = conv_w(conv_w(c2, "conv2", buf["g2"]), "conv2_1", buf["h2"])
         # conv2_2 + bias on the Winograd kernel (pixels channels-last), then log-softmax over the channels of every pixel in place:

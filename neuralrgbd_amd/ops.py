@@ -1090,6 +1090,57 @@ def conv_wino_rnet(x, w_wino, cout, bias=None, lrelu=True, out=None, ycoff=0, co
     return out
 
 
+def deconv_phase_weights(w):
+    """ConvTranspose2d(k4, s2, p1) weight [Cin, Cout, 4, 4] -> the four sub-pixel phases as 3x3 kernels (non-zero in a 2x2 corner)
+    stacked phase-major along the output channels, [4 Cout, Cin, 3, 3], rows (2a + b) * Cout + co: the embedding of
+    autograd.conv_transpose2d_module."""
+    from .autograd import _tap_select
+    cin, cout = w.shape[:2]
+    idx, msk = _tap_select("t2", w.device)
+    w4 = w.detach().permute(1, 0, 2, 3).reshape(cout, cin, 16).index_select(2, idx) * msk
+    return w4.reshape(cout, cin, 4, 9).permute(2, 0, 1, 3).reshape(4 * cout, cin, 3, 3).contiguous()
+
+
+def deconv_live_points(phase):
+    """The 9 transform points xi = 4 xi_y + xi_x of F(2x2, 3x3) at which phase 2a + b of deconv_phase_weights is non-zero."""
+    a, b = phase >> 1, phase & 1
+    return [4 * (r + a) + c + b for r in range(3) for c in range(3)]
+
+
+def conv_wino_rnet_deconv_pack(w_wino, Cin):
+    """The 256-column stream conv_wino_pack makes of deconv_phase_weights (ONE 64-column slice: [256, Cin, 3, 3]) -> the masked
+    stream of conv_wino_rnet_deconv, [4 phases][Cin/16 stages][9 live points][1024] floats (the dropped lines are exact zeros)."""
+    w_wino = _need(w_wino, "w_wino")
+    if w_wino.numel() != 256 * Cin * 16:
+        raise ValueError("conv_wino_rnet_deconv_pack: a 256-column stream of %d input channels expected" % Cin)
+    wm = torch.empty(4 * (Cin // 16) * 9 * 1024, dtype=torch.float32, device=w_wino.device)
+    with torch.cuda.device(w_wino.device):
+        rc = _lib.load().nrgbd_conv_wino_rnet_deconv_pack(_p(w_wino), _p(wm), int(Cin), _stream(w_wino))
+    _lib.check(rc, "nrgbd_conv_wino_rnet_deconv_pack")
+    return wm
+
+
+def conv_wino_rnet_deconv_supported(N, H, W, Cin, ldy):
+    """Shapes nrgbd_conv_wino_rnet_deconv_f32 accepts (per 64-column slice; the caller takes the direct kernel otherwise)."""
+    return Cin >= 32 and Cin % 32 == 0 and N * H * W * Cin < (1 << 30) and 4 * N * H * W * ldy < (1 << 31)
+
+
+def conv_wino_rnet_deconv(x, w_masked, out, bias=None, lrelu=True, ycoff=0, cout_valid=64):
+    """ConvTranspose2d(k4, s2, p1) + bias + LeakyReLU(0.01) of one 64-column slice in the Winograd domain, dead transform points
+    skipped: x [N,H,W,Cin] -> out[..., ycoff:ycoff+cout_valid] of a contiguous [N,2H,2W,ldy] buffer; the rest of a pixel is left alone."""
+    x = _need(x, "x")
+    N, H, W, Cin = x.shape
+    if tuple(out.shape[:3]) != (N, 2 * H, 2 * W) or not out.is_contiguous() or out.shape[3] < ycoff + cout_valid:
+        raise ValueError("conv_wino_rnet_deconv: out must be a contiguous [N,2H,2W,>= ycoff + cout_valid] tensor")
+    if w_masked.numel() != 4 * (Cin // 16) * 9 * 1024:
+        raise ValueError("conv_wino_rnet_deconv: the masked stream does not belong to %d input channels" % Cin)
+    with torch.cuda.device(x.device):
+        rc = _lib.load().nrgbd_conv_wino_rnet_deconv_f32(_p(x), _p(w_masked), _p(bias), int(bool(lrelu)), _p(out), N, H, W, Cin, 64,
+                                                          int(out.shape[3]), int(ycoff), int(cout_valid), _stream(x))
+    _lib.check(rc, "nrgbd_conv_wino_rnet_deconv_f32")
+    return out
+
+
 def conv2d_few(x, w_few, bias=None, lrelu=True, out=None, ycoff=0):
     """3x3 convolution with 1-4 output channels on the vector ALUs (nrgbd_conv2d_few_f32): x [N,H,W,ldx] channels-last, w_few
     [Cin/16, 9, Cout, 16] (= w [Cout, Cin, 3, 3] with ci -> (block, lane) and (ky, kx) -> tap; Cin % 16 == 0 <= ldx) ->
