@@ -45,6 +45,8 @@ struct WinoPcArgs {
                           // clamp of the packed FMA; the weight stream carries the factor 2^k (see nrgbd_conv_wino_dw_unit_f32)
 };
 
+// pc_decode and pc_tile_share have a host mirror, tests/wino_walk.py (decode, share), from which the walking tests take their grids
+// and assert that their launches walk: change the tile order or the split on both sides.
 struct PcTile { int n, y0, x0, py, px, cg, row; };
 
 template <int KD, int DIL>

@@ -199,6 +199,8 @@ def test_conv_wino_pc_2d_plain_vs_torch(N, H, W, Cin, Cout, dil):
 
 @pytest.mark.parametrize("Cin,Cout,dil", [(64, 64, 1), (128, 128, 2)])
 def test_conv_wino_pc_2d_fused_prologue_materialize(Cin, Cout, dil):
+    # at most 48 tiles: one tile per workgroup.  The fused forms where every workgroup hands a tile over to a next one (next-tile
+    # book, owner bits, weight ring into the next tile), against float64, are in tests/test_gpu_wino_pc_walk.py
     from neuralrgbd_amd import ops
     N, H, W = 2, 19, 35
     g = torch.Generator().manual_seed(Cin + dil)
@@ -222,7 +224,8 @@ def test_conv_wino_pc_2d_fused_prologue_materialize(Cin, Cout, dil):
 @pytest.mark.parametrize("N,H,W,fused", [(1, 16, 16, False), (3, 21, 37, False), (5, 48, 64, True), (2, 19, 35, True), (5, 96, 128, False)])
 def test_conv_wino_pc_half_form_32_channels(N, H, W, fused):
     """The HALF form of wino_pc.hip (Cout = 32: firstconv.1/.2 and layer1 of the trunk, psm_submodule.py:90-103) vs F.conv2d in
-    float64 — plain, and with the fused prologue (BatchNorm apply + ReLU, residual, materialise); statistics = two rows per tile."""
+    float64 — plain, and with the fused prologue (BatchNorm apply + ReLU, residual, materialise); statistics = two rows per tile.
+    The fused cases have at most 120 tiles (one per workgroup); the walking regime of the fused HALF forms: tests/test_gpu_wino_pc_walk.py."""
     from neuralrgbd_amd import ops
     C = 32
     g = torch.Generator().manual_seed(N * 100 + H)

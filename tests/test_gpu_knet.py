@@ -177,6 +177,8 @@ def test_conv_wino_pc_3d_plain_vs_torch(D, H, W):
 
 
 def test_conv_wino_pc_3d_fused_prologue_and_materialize():
+    # 54 tiles: one tile per workgroup.  The fused 3-D forms where every workgroup walks several tiles, against float64, are in
+    # tests/test_gpu_wino_pc_walk.py (as are wino_dw4.hip's input forms on its 280-tile grid)
     from neuralrgbd_amd import ops
     D, H, W, C = 6, 18, 36, 64
     g = torch.Generator().manual_seed(5)
